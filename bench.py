@@ -4,9 +4,14 @@ A "step" is one pass of the hot path over one batch of synthetic input: per rank
 independent subproblems (default 1), each a full bellman_TRM! (DP over nt=65536 steps x 4096 levels
 x B+1=257 budget rows) followed by eval_u_TRM! (backtrack), inputs already resident in HBM.
 
-Alongside the headline it measures the batch config C5 (`batch`: `--batch-size` random restarts of the
-36-level heat-shaped subproblem per GPU, the fused small-state DP), the same config at a fixed total
-(`batch_strong`: `--batch-total` restarts split over the ranks, strong scaling) and the p=Inf variant of C4.
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps of the headline, writes
+its outputs if `--dump-outputs DIR` is given and prints the result line; nothing else.
+
+With `--full` it also measures, alongside the headline, the batch config C5 (`batch`: `--batch-size` random restarts
+of the 36-level heat-shaped subproblem per GPU, the fused small-state DP), the same config at a fixed total
+(`batch_strong`: `--batch-total` restarts split over the ranks, strong scaling), the p=Inf variant of C4, the p=2 and
+p=Inf batch lines, the single-subproblem lines, the PDE heat gradient line, every line's rooflines and the CPU
+baselines.
 
 Multi-GPU: `python bench.py --gpus N` launches N ranks itself (one process per GPU, before anything
 touches a GPU); under torchrun it uses the given RANK / WORLD_SIZE.  The problem descriptor is broadcast
@@ -15,9 +20,13 @@ work is fixed, no data-path collective), and the controls (uint16 level ranks fr
 are gathered to rank 0 over RCCL at the end of every step.  `value` = subproblems of all ranks / the
 max-over-ranks time.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel, measured with HIP events on the
-library's stream; `roofline_valu` gives the FP64-VALU view; `cpu_baseline` times the C restatement of the
+Prints ONE JSON line (rank 0).  With `--full`: `roofline` is for the dominant kernel, measured with HIP events on
+the library's stream; `roofline_valu` gives the FP64-VALU view; `cpu_baseline` times the C restatement of the
 reference loop (oracle/) on a bounded sample, on this job's host cores.
+
+`--dump-outputs DIR` writes what the headline's last timed step returned to its caller (the controls u, Φ* and the
+status of every subproblem; over several ranks, what rank 0 gathered) as DIR/<name>.npy.  The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 
 `--solver oracle --backend gloo` (CPU only, tests): the same launcher, sharding and gather, with the CPU
 oracle as the per-rank solver on truncated inputs -- the product path on GPUs is libmioc.
@@ -50,6 +59,12 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: the other lines (--variant, --batch-config, "
+                         "--p2-batch-config, --pinf-batch-config, --single-configs, --heat-restarts), the rooflines "
+                         "and the CPU baselines (default: the headline's timed steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the headline's last timed step returned (u, Φ*, status) as DIR/<name>.npy")
     ap.add_argument("--config", default="C4")
     ap.add_argument("--p", default=None, help="override p: 1 or inf")
     ap.add_argument("--batch", type=int, default=1, help="subproblems per rank per step (headline config)")
@@ -147,6 +162,10 @@ class NativeSolver:
         self.ctx.synchronize()
         return self.d_rk.to(self.torch.int16), self.d_phi
 
+    def outputs(self):
+        """What the last solve() returned to its caller: u [K, nt, nx], Φ* [K], status [K] (host copies)."""
+        return {"u": self.d_u.cpu().numpy(), "phi": self.d_phi.cpu().numpy(), "status": self.d_st.cpu().numpy()}
+
     def sync(self):
         self.ctx.synchronize()
         self.torch.cuda.synchronize(self.device)
@@ -193,6 +212,9 @@ class OracleSolver:
     def results(self):
         return self._r
 
+    def outputs(self):
+        return {"ranks": self._r[0].numpy(), "phi": self._r[1].numpy()}
+
     def sync(self):
         pass
 
@@ -205,9 +227,28 @@ class OracleSolver:
 
 
 # ------------------------------------------------------------------------------------------------------
-def run(args, cfg_name, K, p_over, nt_over, rank, world, device, dist, torch, steps, warmup, total=None):
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy: integers and float16/32 as float32, everything else as float64.  An array
+    over its share of DUMP_MAX_BYTES is cut to a fixed, seeded sample of its flattened elements (in index order)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        small = a.dtype.kind in "iub" and a.dtype.itemsize <= 2 or a.dtype in (np.float16, np.float32)
+        a = np.ascontiguousarray(a, dtype=np.float32 if small else np.float64)
+        if a.nbytes > share:
+            pick = np.random.Generator(np.random.PCG64(0xD0)).choice(a.size, size=share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def run(args, cfg_name, K, p_over, nt_over, rank, world, device, dist, torch, steps, warmup, total=None, dump=None):
     """One config: `steps` timed + `warmup` untimed steps, each a global batch of world*K subproblems (weak
-    scaling), or of `total` subproblems split over the ranks (strong scaling)."""
+    scaling), or of `total` subproblems split over the ranks (strong scaling).  `dump`: a directory for the last
+    timed step's outputs (dump_outputs)."""
     from mioc.batch import gather_results, shard
     from mioc.synth import CONFIGS, make_inputs
 
@@ -271,6 +312,10 @@ def run(args, cfg_name, K, p_over, nt_over, rank, world, device, dist, torch, st
     elif world == 1:
         r, ph = solver.results()
         res["gathered_checksum"] = float(ph.double().sum().item()) + float(r.double().sum().item())
+    if dump and rank == 0 and steps > 0:
+        # one rank: what the last solve() handed back; several: what rank 0 gathered from all of them in that step
+        dump_outputs(dump, solver.outputs() if world == 1 else
+                     {"ranks": gathered[-1][0].cpu().numpy(), "phi": gathered[-1][1].cpu().numpy()})
     solver.finish(res)
     return res
 
@@ -300,7 +345,7 @@ def pmc_traffic(kernel, cfg=None, K=None):
                 ks = json.load(fh)["kernels"]
         except (OSError, ValueError, KeyError):
             continue
-        # entries recorded from a single-config pass are qualified "kernel@CFG"; plain names come from the default
+        # entries recorded from a single-config pass are qualified "kernel@CFG"; plain names come from the --full
         # bench passes, where each kernel belongs to one line (C4 headline / its p=Inf variant / the C5 batch).
         # A batch size qualifier first ("k_fsep2@C5x128": the grid-size split of scripts/pmc_traffic.py --qualify);
         # an unqualified "@CFG" entry is a batch pass's, so a one-subproblem line (K = 1) never takes it.  `kernel` is
@@ -721,8 +766,13 @@ def main():
         else:
             dist.init_process_group("gloo")
     device = local
+    if not args.full:  # a plain run: the headline's timed steps only -- no other line, roofline or CPU baseline
+        args.variant = args.batch_config = args.p2_batch_config = args.pinf_batch_config = "none"
+        args.single_configs = "none"
+        args.heat_restarts = 0
+        args.no_cpu_baseline = True
     res = run(args, args.config, args.batch, args.p, args.nt, rank, world, device, dist, torch, args.steps,
-              args.warmup, total=args.total or None)
+              args.warmup, total=args.total or None, dump=args.dump_outputs)
     variant = batch = None
     if args.variant == "pinf" and args.p is None and args.nt is None and math.isfinite(res["p"]):
         r2 = run(args, args.config, args.batch, "inf", None, rank, world, device, dist, torch,
@@ -823,8 +873,9 @@ def main():
             "algorithm": {native_name(res["algo"]): res["dom_name"]},
             "checksum": res.get("gathered_checksum"),
         }
-        if args.solver == "native":
+        if args.solver == "native" and args.full:
             out["roofline"], out["roofline_valu"] = roofline_of(res)
+        if args.solver == "native":
             out["backtrack_ms"] = round(res["walk_ms"] / max(1, args.steps), 3)
             out["exact_scan_targets"] = {"near_tie": res["diag"][0], "direct_rows": res["diag"][1],
                                          "of_cells": res["K"] * (res["nt"] - 1) * (res["B"] + 1) * res["levels"].L,

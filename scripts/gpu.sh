@@ -4,7 +4,8 @@
 # step that fails, times out or dies ends the call (no GPU step after a fault).  Arguments inside a step are separated
 # by commas (a step is one shell word).
 #   tests              pytest -m gpu over tests/ (tests:f1.py,f2.py[::name]: only those files / tests)
-#   bench[:args]       python bench.py args                       -> bench.json
+#   bench[:args]       python bench.py args                       -> bench.json  (bench:--full for every line,
+#                      the rooflines and the CPU baselines; without it the headline only -- prof and pmc likewise)
 #   smoke              __graft_entry__.smoke()
 #   prof[:args]        rocprofv3 --kernel-trace --stats over bench.py args   -> prof/ (kernel_stats.csv)
 #   pmc:c1+c2[:args]   ONE rocprofv3 --pmc pass (counters joined by +) over bench.py args -> pmc_<c1>/

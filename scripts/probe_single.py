@@ -1,5 +1,5 @@
-"""The single-subproblem bench lines (bench.py single_C2 / single_C3: one subproblem per step, bellman + backtrack
-through the device-tensor entry points, no host sync inside the timed loop), timed alone.
+"""The single-subproblem bench lines (bench.py --full, single_C2 / single_C3: one subproblem per step, bellman +
+backtrack through the device-tensor entry points, no host sync inside the timed loop), timed alone.
 Usage: python scripts/probe_single.py [CFG] [steps]   (MIOC_LIB selects a library build)
 Under rocprofv3 --kernel-trace the per-kernel durations and the gaps between them show where a step goes."""
 import json
