@@ -192,7 +192,8 @@ int32_t mioc_tv_device(mioc_ctx *ctx, int64_t K, const double *d_u, int64_t nx, 
  *     (offset 0: gate word, 4: any-active word, 8: copy word; then K doubles Δᵏ, K doubles TV_old, K int32 k,
  *     K int32 flags (1 inner, 2 halved, 4 stopped), K int32 outer iterations per restart).
  *   mioc_trm_attach(ctx, d_state): while the gate word is 0, the kernels of mioc_backtrack_batch*_device,
- *     mioc_pred_batch_device, mioc_ode_eval_device and mioc_heat_eval_device return at once; NULL detaches.
+ *     mioc_pred_batch_device, mioc_ode_eval_device, mioc_heat_eval_device and mioc_conv_eval_device return at once;
+ *     NULL detaches.
  *   mioc_trm_outer_begin_device: multi-trust.jl:99-107 (TV_old = TV_p(u), Δᵏ = Δ⁰, k = 1, budgets = B, every
  *     restart not stopped enters its inner loop; the gate opens if any did).
  *   mioc_trm_inner_end_device: multi-trust.jl:117-158 for the restarts inside their inner loop: pred (with TV_old),
@@ -267,6 +268,28 @@ int32_t mioc_heat_setup(mioc_ctx *ctx, int64_t N, int64_t nx, int64_t nt, double
 int32_t mioc_heat_eval_device(mioc_ctx *ctx, int64_t K, const double *d_x, double *d_J, double *d_df);
 /* The same from host arrays (the Julia objective's x / df, K x nx x nt column-major; J: K), synchronous. */
 int32_t mioc_heat_eval(mioc_ctx *ctx, int64_t K, const double *x, double *J, double *df);
+
+/*
+ * The signal-reconstruction (convolution) objective's gradient producer, batched on the device (Marko / Wachsmuth
+ * §6.2; the reference's main("convolution"), multi-trust.jl:190-192): eval_f_helper / eval_df_helper of
+ * julia_opt/example_convolution.jl:128-141, v = K·xᵀ − fvec, J = ½·vᵀ·M·v, df = (Kᵀ·(M·v))ᵀ, with
+ *   K    (nt+1) x nt, toeplitz (:104-125): K[r,c] = κ[r−c] for r−c >= 1 and 0 otherwise (1-based) -- strictly lower
+ *        triangular Toeplitz, row 1 and the diagonal are zero.  kappa = K[2:nt+1, 1] (nt values) defines it; the
+ *        matrix is never stored;
+ *   fvec nt+1 values, f_to_vec (:73-81): fvec[i] = target(T0 + τ·i), i = 1..nt+1 -- the grid starts one step AFTER
+ *        T0 (the reference's offset, kept: the caller passes obj.fvec as it is);
+ *   M    (nt+1)² tridiagonal, Mmat (:85-100): τ/3 at both ends of the diagonal, (2/3)·τ inside, τ/6 beside it;
+ *        built here from τ = (T1 − T0) / nt.
+ * One control with signed levels (𝓥 = [[-2,-1,0,1,2]]).  1 <= nt <= 16384 (κ is held in LDS).  mioc_conv_eval_device:
+ * d_x = K x 1 x nt controls (the DP's input layout), d_J (K, nullable: no value), d_df (K x 1 x nt, nullable: stops
+ * after J).  Enqueued.  A restart's J and df do not depend on K or on its position in the batch.  Errors:
+ * MIOC_EINVAL (nt out of range, T1 <= T0, NULL pointers, non-finite κ / fvec), MIOC_ESTATE (eval before a successful
+ * setup), MIOC_ENOMEM (the v scratch, K x (nt+1) doubles, cannot grow).
+ */
+int32_t mioc_conv_setup(mioc_ctx *ctx, int64_t nt, double T0, double T1, const double *kappa, const double *fvec);
+int32_t mioc_conv_eval_device(mioc_ctx *ctx, int64_t K, const double *d_x, double *d_J, double *d_df);
+/* The same from host arrays (the Julia objective's x / df, K x 1 x nt; J: K), synchronous. */
+int32_t mioc_conv_eval(mioc_ctx *ctx, int64_t K, const double *x, double *J, double *df);
 
 /* The HIP stream the context enqueues on (hipStream_t), for callers that order their own work. */
 void *mioc_stream(mioc_ctx *ctx);

@@ -181,4 +181,55 @@ function heat_eval!(ctx::Context, x::Matrix{Float64}, df::Union{Matrix{Float64},
     J[]
 end
 
+"""
+    conv_setup(ctx, obj)
+
+Hands the data of the convolution objective (example_convolution.jl's ConvObj) to the device: κ = obj.K[2:end, 1],
+obj.fvec, T0, T1.  The device never stores K: it relies on K being strictly lower triangular Toeplitz
+(toeplitz, example_convolution.jl:104-125), which is checked here.  Call again whenever K or fvec change.
+"""
+function conv_setup(ctx::Context, obj)
+    K = obj.K
+    nt = Int(size(K, 2))
+    size(K, 1) == nt + 1 || throw(DimensionMismatch("K must be (nt+1) x nt"))
+    kappa = Vector{Float64}(K[2:end, 1])
+    for c in 1:nt, r in 1:nt+1
+        K[r, c] == (r - c >= 1 ? kappa[r - c] : 0.0) ||
+            throw(ArgumentError("obj.K is not strictly lower triangular Toeplitz at ($r, $c)"))
+    end
+    fvec = Vector{Float64}(obj.fvec)
+    length(fvec) == nt + 1 || throw(DimensionMismatch("fvec must have nt+1 entries"))
+    check(ctx, ccall((:mioc_conv_setup, libmioc), Int32,
+                     (Ptr{Cvoid}, Int64, Float64, Float64, Ptr{Float64}, Ptr{Float64}),
+                     ctx.ptr, nt, obj.T0, obj.T1, kappa, fvec))
+    nothing
+end
+
+"""
+    conv_eval!(ctx, x, df) -> fval
+
+eval_f_helper + eval_df_helper of example_convolution.jl:128-141 for the control x (1 × nt) in one device call:
+returns the objective value and, unless `df` is `nothing`, writes the gradient at x into df (1 × nt).
+"""
+function conv_eval!(ctx::Context, x::Matrix{Float64}, df::Union{Matrix{Float64},Nothing})
+    df === nothing || size(df) == size(x) || throw(DimensionMismatch("df and x differ in shape"))
+    J = Ref{Float64}(0.0)
+    check(ctx, ccall((:mioc_conv_eval, libmioc), Int32,
+                     (Ptr{Cvoid}, Int64, Ptr{Float64}, Ref{Float64}, Ptr{Float64}), ctx.ptr, 1, x, J,
+                     df === nothing ? Ptr{Float64}(C_NULL) : df))
+    J[]
+end
+
+"""
+    conv_eval_device!(ctx, K, d_x, d_J, d_df)
+
+The batched device entry (mioc_conv_eval_device): K controls already in device memory (K × 1 × nt), enqueued on the
+context's stream; d_J / d_df may be C_NULL.
+"""
+function conv_eval_device!(ctx::Context, K::Integer, d_x::Ptr{Float64}, d_J::Ptr{Float64}, d_df::Ptr{Float64})
+    check(ctx, ccall((:mioc_conv_eval_device, libmioc), Int32,
+                     (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ctx.ptr, K, d_x, d_J, d_df))
+    nothing
+end
+
 end # module

@@ -140,6 +140,8 @@ void free_all(mioc_ctx *ctx) {
   if (ctx->h_flags) hipHostFree(ctx->h_flags);
   heat_free(ctx->heat);
   ctx->heat = nullptr;
+  conv_free(ctx->conv);
+  ctx->conv = nullptr;
   ev_collect(ctx);
   for (auto &pr : ctx->ev_pool) hipEventDestroy(pr.begin), hipEventDestroy(pr.end);
   if (ctx->ev_dp) hipEventDestroy(ctx->ev_dp);

@@ -279,6 +279,8 @@ int join_bt(mioc_ctx *ctx);
 
 struct HeatState;  // mioc_heat.hip: the PDE heat objective's device matrices (mioc_heat_setup)
 void heat_free(HeatState *h);
+struct ConvState;  // mioc_conv.hip: the convolution objective's device tables (mioc_conv_setup)
+void conv_free(ConvState *c);
 
 }  // namespace mioc
 
@@ -322,6 +324,7 @@ struct mioc_ctx {
   double *d_ode_state = nullptr;   // [K][nt][2] forward states of mioc_ode_eval_device
   size_t ode_cap = 0;
   mioc::HeatState *heat = nullptr; // mioc_heat_setup / mioc_heat_eval_device
+  mioc::ConvState *conv = nullptr; // mioc_conv_setup / mioc_conv_eval_device
   int64_t costlut_len = 0;
 
   // owned problem inputs (device)

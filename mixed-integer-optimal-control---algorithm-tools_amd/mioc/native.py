@@ -43,6 +43,7 @@ EXPORTED = [
     "mioc_pred", "mioc_pred_batch_device", "mioc_tv_device", "mioc_trm_decide_device", "mioc_batch_multi",
     "mioc_ode_eval_device", "mioc_rand_start_device", "mioc_backtrack_batch_budgets_device",
     "mioc_heat_setup", "mioc_heat_eval_device", "mioc_heat_eval",
+    "mioc_conv_setup", "mioc_conv_eval_device", "mioc_conv_eval",
     "mioc_trm_state_bytes", "mioc_trm_attach", "mioc_trm_outer_begin_device", "mioc_trm_inner_end_device",
     "mioc_trm_poll",
 ]
@@ -111,6 +112,9 @@ def load_library(path=None):
         "mioc_heat_setup": (i32, [vp, i64, i64, i64, dbl, dbl, dbl, vp, vp, vp, vp, vp]),
         "mioc_heat_eval_device": (i32, [vp, i64, vp, vp, vp]),
         "mioc_heat_eval": (i32, [vp, i64, vp, vp, vp]),
+        "mioc_conv_setup": (i32, [vp, i64, dbl, dbl, vp, vp]),
+        "mioc_conv_eval_device": (i32, [vp, i64, vp, vp, vp]),
+        "mioc_conv_eval": (i32, [vp, i64, vp, vp, vp]),
         "mioc_trm_state_bytes": (i64, [i64]),
         "mioc_trm_attach": (i32, [vp, vp]),
         "mioc_trm_outer_begin_device": (i32, [vp, i64, vp, vp, dbl, i64, vp]),
@@ -464,6 +468,47 @@ class Context:
         J = np.empty(K)
         df = np.empty_like(x)
         self._check(self.lib.mioc_heat_eval(self.h, K, _p(x), _p(J), _p(df)))
+        return J, df.transpose(0, 2, 1)
+
+    def conv_setup(self, kappa, fvec, T0, T1):
+        """Hand the convolution objective's data to the device (mioc_conv_setup; example_convolution.jl:67,47):
+        kappa = K[2:nt+1, 1] (nt,) and fvec (nt+1,) as numpy arrays; nt = kappa.size."""
+        kap = np.ascontiguousarray(kappa, dtype=np.float64)
+        fv = np.ascontiguousarray(fvec, dtype=np.float64)
+        if kap.ndim != 1 or fv.shape != (kap.size + 1,):
+            raise ValueError("convolution data: kappa (nt,), fvec (nt+1,)")
+        nt = kap.size
+        self._check(self.lib.mioc_conv_setup(self.h, nt, float(T0), float(T1), _p(kap), _p(fv)))
+        self.conv_shape = (1, nt)
+
+    def conv_eval_tensors(self, x, J=None, df=None):
+        """eval_f / eval_df of the convolution objective for K controls x (K, nt, 1) float64 CUDA tensor into J (K,)
+        and df (K, nt, 1) float64 CUDA tensors (each optional; without df the call stops after J); enqueued
+        (mioc_conv_eval_device)."""
+        if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
+            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
+        K, nt, nx = x.shape
+        if getattr(self, "conv_shape", None) is None or self.conv_shape != (nx, nt):
+            raise ValueError("x does not match the (nx = 1, nt) given to conv_setup")
+        for name, t, n in (("J", J, K), ("df", df, x.numel())):
+            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or
+                                  t.numel() != n):
+                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries")
+        self._check(self.lib.mioc_conv_eval_device(
+            self.h, K, ctypes.c_void_p(x.data_ptr()),
+            ctypes.c_void_p(J.data_ptr()) if J is not None else None,
+            ctypes.c_void_p(df.data_ptr()) if df is not None else None))
+
+    def conv_eval(self, xs):
+        """Host entry (mioc_conv_eval): xs (K, 1, nt) numpy controls (Julia's per-restart layout) -> J (K,),
+        df (K, 1, nt)."""
+        x = np.ascontiguousarray(np.asarray(xs, dtype=np.float64).transpose(0, 2, 1))  # K x (nx x nt col-major)
+        K, nt, nx = x.shape
+        if getattr(self, "conv_shape", None) is None or self.conv_shape != (nx, nt):
+            raise ValueError("xs does not match the (nx = 1, nt) given to conv_setup")
+        J = np.empty(K)
+        df = np.empty_like(x)
+        self._check(self.lib.mioc_conv_eval(self.h, K, _p(x), _p(J), _p(df)))
         return J, df.transpose(0, 2, 1)
 
     def rand_start_tensor(self, out, seed, jumps=-1):

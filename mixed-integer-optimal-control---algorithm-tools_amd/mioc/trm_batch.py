@@ -10,7 +10,8 @@ The control flow is multi-trust.jl:53-170 per restart, run for K restarts in loc
 
 Device kernels do all O(nt) work: the random starts (mioc_rand_start_device, HelpFunctions.jl:204-225), the ODE
 objective and adjoint gradient (mioc_ode_eval_device, ODEObjective.jl:125-184) or the PDE heat objective's
-(mioc_heat_eval_device, PDEObjective.jl:129-199), the DP and backtrack with one budget per restart after halving
+(mioc_heat_eval_device, PDEObjective.jl:129-199) or the convolution objective's (mioc_conv_eval_device,
+example_convolution.jl:128-141), the DP and backtrack with one budget per restart after halving
 (mioc_backtrack_batch_budgets_device), pred and TV_p -- and the control itself: Δᵏ, k, the inner / halved / stopped
 flags, the decision, obj.x = trial, the accept bookkeeping and the next budgets live in a device state block
 (mioc_trm_outer_begin_device / mioc_trm_inner_end_device).  Everything is enqueued on the context's stream; the
@@ -47,17 +48,33 @@ def TRM_batch(problem, par, K=None, x0=None, seed=0, nt=None, device=0, log=None
     """Run TRM (multi-trust.jl:53-170) for K restarts of an ODE example, or of the PDE heat example, on the device.
 
     problem: "fishing" / "doubletank" / "vanderpol", or a mioc.heat.HeatProblem (example_heat.jl: 6 x 6 product
-    levels, gradient from mioc_heat_eval_device; its nt is the problem's).
+    levels, gradient from mioc_heat_eval_device; its nt is the problem's), or a mioc.conv.ConvProblem / the string
+    "convolution" = ConvProblem(nt = nt or 2048) (example_convolution.jl: one control, levels -2..2, gradient from
+    mioc_conv_eval_device).
     x0: a (K, nt, nx) float64 CUDA tensor of starts, or None for K device random starts (rand_func_int with `seed`).
     log: a list to receive (inner iteration, decisions (K,)) after every inner iteration (debugging: one stream
     synchronisation each).  inner_chunk: inner iterations enqueued between two read-backs of the control flags.
-    stats: a dict to receive {"polls": read-backs, "outer": outer iterations}.
+    stats: a dict to receive {"polls": read-backs, "outer": outer iterations, "algo": the DP that served the last
+    bellman (mioc_last_algo), "diagnostics": its counters (mioc_diagnostics)}.
     Returns (values (K,) numpy: J + β·TV_p(u) per restart, u (K, nt, nx) CUDA tensor: obj.x of each restart,
     iterations (K,) numpy)."""
     import torch
 
+    from .conv import ConvProblem
+    if isinstance(problem, str) and problem == "convolution":
+        problem = ConvProblem(nt=nt or 2048)
     ctx = Context(device)
-    if isinstance(problem, str):
+    if isinstance(problem, ConvProblem):  # the signal reconstruction objective (example_convolution.jl:128-141)
+        cp = problem
+        nt_def, T0, T1 = cp.nt, cp.T0, cp.T1
+        if nt is not None and int(nt) != cp.nt:
+            raise ValueError("the convolution problem fixes nt")
+        lt = LevelTable(cp.levels)
+        cp.setup(ctx)
+
+        def evalf(x, J, df):
+            ctx.conv_eval_tensors(x, J, df)
+    elif isinstance(problem, str):
         prob, nt_def, T0, T1 = PROBLEMS[problem]
         lt = sos1_levels()
 
@@ -146,6 +163,6 @@ def TRM_batch(problem, par, K=None, x0=None, seed=0, nt=None, device=0, log=None
     st = ctx.trm_state_arrays(state, K)
     iters = st["iters"].astype(np.int64)
     if stats is not None:
-        stats.update(polls=polls, outer=it - 1)
+        stats.update(polls=polls, outer=it - 1, algo=ctx.last_algo(), diagnostics=ctx.diagnostics())
     ctx.close()
     return values, u, iters
