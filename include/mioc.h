@@ -119,6 +119,25 @@ int32_t mioc_set_cost(mioc_ctx *ctx, int32_t p_kind, int64_t p_int, double beta,
  * called at multi-trust.jl:112.  U and Φ live in the context (device memory), not on the host:
  * the reference layout would be 2.21 TB for nt=65536, 4096 levels, B=256.
  * Host buffers df (∇f) and u_old: nx x nt column-major.  B = floor(Δ⁰/Δt) (multi-trust.jl:69).
+ *
+ * Accepted arguments: nx equal to the levels' number of controls, 1 <= K <= 4096 (batch entries),
+ * 1 <= nt <= 2^30, 0 <= B <= 2^20, dt finite.  Within that range each algorithm has a budget limit of its own:
+ *   MIOC_ALGO_PINF             B + 1 <= 7936 after rounding up to a multiple of 64 (B <= 7935), and at most 64
+ *                              budget classes (max_l |nu_l - u_old|_1 <= 63 at every step);
+ *   MIOC_ALGO_FUSED            (B + 1 rounded up to 64)/64 * L <= 192 and the front within one CU's 160 KiB of
+ *                              LDS (B <= 3390 at L = 2, 3387 at L = 3, 2024 at L = 5);
+ *   MIOC_ALGO_FUSED_SEPARABLE  B < 512;
+ *   the others                 B <= 2^20, as far as device memory holds the tables.
+ * MIOC_ALGO_AUTO takes another algorithm beyond such a limit; a forced algorithm returns MIOC_EINVAL.
+ *
+ * What a failed call leaves behind (mioc_bellman, mioc_bellman_batch_device and mioc_batch_multi alike):
+ *   - A call rejected for its arguments (MIOC_EINVAL for nx, K, nt, B or dt, or a NULL pointer) changes nothing:
+ *     the previous DP, its inputs and its last backtrack stay valid, and mioc_backtrack*, mioc_pred* and
+ *     mioc_get_argmin_table answer from them exactly as before the call.
+ *   - A call that fails after that (MIOC_ENONFINITE, MIOC_EINEXACT, a forced algorithm that does not support the
+ *     problem: MIOC_EINVAL from the algorithm's own check, MIOC_ENOMEM, MIOC_EHIP) has given up the previous DP
+ *     and holds none: mioc_backtrack*, mioc_pred* and mioc_get_argmin_table return MIOC_ESTATE until a bellman
+ *     call succeeds.
  */
 int32_t mioc_bellman(mioc_ctx *ctx, const double *df, const double *u_old, int64_t nx, int64_t nt, int64_t B,
                      double dt);

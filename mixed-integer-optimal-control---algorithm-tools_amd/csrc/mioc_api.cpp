@@ -105,12 +105,15 @@ void slot_load(mioc_ctx *ctx) {
   ctx->pinf.kmin = q.kmin, ctx->pinf.k2 = q.k2, ctx->pinf.kfirst = q.kfirst, ctx->pinf.R = q.R, ctx->pinf.kabs = q.kabs;
   ctx->pinf_cap_k = q.cap_k, ctx->pinf_cap_R = q.cap_R, ctx->pinf_cap_kabs = q.cap_kabs;
 }
-// a new DP: the other slot, once the backtracks that read it are done (on the device: the stream waits)
+// a new DP: the other slot, once the backtracks that read it are done (on the device: the stream waits).
+// Called only with arguments that check_problem accepted, and the wait (the one step that can fail) comes before the
+// swap: a call that returns an error from here or earlier leaves the context's slot, inputs and tables as they were.
 int begin_dp(mioc_ctx *ctx) {
+  const int other = ctx->slot ^ 1;
+  if (ctx->bt_rec[other]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_bt[other], 0));
   slot_save(ctx);
-  ctx->slot ^= 1;
+  ctx->slot = other;
   slot_load(ctx);
-  if (ctx->bt_rec[ctx->slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_bt[ctx->slot], 0));
   return MIOC_OK;
 }
 
@@ -702,12 +705,20 @@ int check_ready(mioc_ctx *ctx) {
   return MIOC_OK;
 }
 
-int set_problem(mioc_ctx *ctx, int64_t K, int64_t nx, int64_t nt, int64_t B, double dt) {
+// The argument checks of a bellman call.  They run before begin_dp swaps the DP slot, so that a call rejected here
+// changes nothing: the previous DP, its inputs and its backtrack result stay readable (include/mioc.h, mioc_bellman).
+int check_problem(mioc_ctx *ctx, int64_t K, int64_t nx, int64_t nt, int64_t B, double dt) {
   if (nx != ctx->M) return fail(ctx, MIOC_EINVAL, "nx does not match the number of controls in the level table");
   if (K < 1 || K > 4096) return fail(ctx, MIOC_EINVAL, "batch size must be in [1, 4096]");
   if (nt < 1 || nt > (1 << 30)) return fail(ctx, MIOC_EINVAL, "nt out of range");
   if (B < 0 || B > (1 << 20)) return fail(ctx, MIOC_EINVAL, "B out of range");
   if (!std::isfinite(dt)) return fail(ctx, MIOC_EINVAL, "dt must be finite");
+  return MIOC_OK;
+}
+
+// The accepted problem becomes the context's (after begin_dp).  From here on the previous DP is gone: have_dp and
+// have_path stay false until run_bellman / run_backtrack have succeeded again.
+int set_problem(mioc_ctx *ctx, int64_t K, int64_t nx, int64_t nt, int64_t B, double dt) {
   ctx->K = (int)K;
   ctx->nt = (int)nt;
   ctx->B = (int)B;
@@ -715,6 +726,7 @@ int set_problem(mioc_ctx *ctx, int64_t K, int64_t nx, int64_t nt, int64_t B, dou
   ctx->dt = dt;
   ctx->have_dp = false;
   ctx->have_path = false;
+  ctx->run_pending = false;  // a superseded DP's timeout word concerns nobody (run_bellman arms it again)
   size_t need = (size_t)K * nx * nt * sizeof(double);
   size_t cap = ctx->in_cap, cap2 = ctx->in_cap;
   int rc = grow(ctx, &ctx->d_df, &cap, need, "df copy");
@@ -960,6 +972,8 @@ int32_t mioc_bellman_batch_device(mioc_ctx *ctx, int64_t K, const double *d_df, 
   int rc = check_ready(ctx);
   if (rc) return rc;
   if (!d_df || !d_u_old) return fail(ctx, MIOC_EINVAL, "null input pointer");
+  rc = check_problem(ctx, K, nx, nt, B, dt);
+  if (rc) return rc;
   rc = begin_dp(ctx);
   if (rc) return rc;
   rc = set_problem(ctx, K, nx, nt, B, dt);
@@ -975,6 +989,8 @@ int32_t mioc_bellman(mioc_ctx *ctx, const double *df, const double *u_old, int64
   int rc = check_ready(ctx);
   if (rc) return rc;
   if (!df || !u_old) return fail(ctx, MIOC_EINVAL, "null input pointer");
+  rc = check_problem(ctx, 1, nx, nt, B, dt);
+  if (rc) return rc;
   rc = begin_dp(ctx);
   if (rc) return rc;
   rc = set_problem(ctx, 1, nx, nt, B, dt);
@@ -1056,6 +1072,8 @@ int32_t mioc_backtrack(mioc_ctx *ctx, int64_t B_use, double *u_out, double *phi_
 static int32_t batch_host(mioc_ctx *ctx, int64_t K, const double *df, const double *u_old, int64_t nx, int64_t nt,
                           int64_t B, double dt, int64_t B_use, double *u_out, double *phi_star, int32_t *status) {
   int rc = check_ready(ctx);
+  if (rc) return rc;
+  rc = check_problem(ctx, K, nx, nt, B, dt);
   if (rc) return rc;
   rc = begin_dp(ctx);
   if (rc) return rc;

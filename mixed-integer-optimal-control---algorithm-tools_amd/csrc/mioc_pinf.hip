@@ -1822,11 +1822,15 @@ hipError_t launch_pinf_fwalk(hipStream_t s, const ProblemDev &P, const LevelsDev
 
 // The walk's chunk and LDS row width: a band covering two chunks of budget descent plus one class window when that
 // is at most half a row (the narrow class windows of SOS1 problems: C1-C3 have BW = 4, W = 106 of RP = 832), else
-// whole rows with the largest chunk that fits 96 KB.
+// whole rows with the largest chunk that fits 96 KB.  A band of 16-step chunks needs 2·16·(8 W + 20 BWP) bytes of
+// LDS, which passes a workgroup's 160 KiB from about 18 classes on (BW = 61: 537 KiB; such a band is at most half a
+// row only once RP >= 2 W, so B in the thousands): then the chunk is halved until the band fits (BW = 61: 8 steps).
 void pinf_plan(int RP, int nt, PinfDev &D) {
   (void)nt;
-  const int ch = 16, w = (2 * ch * (D.BW - 1) + D.BWP + 2 + 1) & ~1;
-  if (2 * w <= RP) {
+  for (int ch = 16; ch >= 1; ch /= 2) {
+    const int w = (2 * ch * (D.BW - 1) + D.BWP + 2 + 1) & ~1;
+    if (2 * w > RP) break;  // (only where the 16-step band is at most half a row: else whole rows, as below)
+    if ((size_t)2 * ch * ((size_t)w * 8 + (size_t)D.BWP * 20) + 32 > 160 * 1024) continue;
     D.CH = ch;
     D.W = w;
     return;

@@ -253,8 +253,8 @@ class Context:
         if df.shape != u_old.shape:
             raise ValueError("df and u_old must have the same shape (nx, nt)")
         nx, nt = df.shape
-        self.nt, self.B = nt, int(B)
         self._check(self.lib.mioc_bellman(self.h, _p(df), _p(u_old), nx, nt, int(B), float(dt)))
+        self.nt, self.B = nt, int(B)  # after success: a rejected call leaves the previous DP (and its sizes) in place
 
     def backtrack(self, B_use=None):
         if self.nt is None:  # no DP yet: let the library report the state error (MIOC_ESTATE)
@@ -270,10 +270,10 @@ class Context:
 
     # -- device-resident batch API (pointers are device addresses, e.g. torch .data_ptr()) ----
     def bellman_batch_device(self, K, df_ptr, uold_ptr, nx, nt, B, dt):
-        self.nt, self.B = nt, int(B)
         self._check(self.lib.mioc_bellman_batch_device(self.h, int(K), ctypes.c_void_p(df_ptr),
                                                        ctypes.c_void_p(uold_ptr), int(nx), int(nt), int(B),
                                                        float(dt)))
+        self.nt, self.B = nt, int(B)
 
     def backtrack_batch_device(self, B_use, u_ptr, phi_ptr=0, status_ptr=0):
         self._check(self.lib.mioc_backtrack_batch_device(self.h, int(B_use), ctypes.c_void_p(u_ptr),

@@ -472,6 +472,111 @@ def test_error_codes():
     ctx.close()
 
 
+@pytest.mark.parametrize("p", [math.inf, 1], ids=["pinf", "p1_generic"])
+def test_rejected_bellman_keeps_previous_dp(oracle_c, p):
+    """What a failed bellman call leaves behind (include/mioc.h, mioc_bellman).
+
+    A call rejected for its arguments (MIOC_EINVAL for nx, K, B, dt) changes nothing: backtrack at two budgets, pred
+    and (p = 1) the argmin table are bit-identical to a fresh context that ran only the previous problem.  The
+    context has run two problems A, A' of one shape before, so both DP slots hold valid, equally sized inputs and
+    tables: a library that swapped the slot for the rejected call would answer from A's inputs, in bounds, and
+    fail the comparison.  A call that fails later (non-finite df, non-integral u_old, a forced algorithm that does not
+    support the problem) holds no DP: backtrack, pred and argmin_table return MIOC_ESTATE; the next good call is right
+    again."""
+    import torch
+    pk = P_INF if p == math.inf else P_ONE
+    algo = native.MIOC_ALGO_PINF if p == math.inf else native.MIOC_ALGO_GENERIC
+    lv = Levels.product([[0, 1, 2], [0, 1]])
+    lt = LevelTable(lv.nu, [tuple(t) for t in lv.tuples])
+    nt, B, beta, dt = 40, 12, 0.1, 0.25
+    rng = np.random.default_rng(77)
+    A, A2 = [(rng.standard_normal((lv.M, nt)),
+              np.array([lv.nuval[rng.integers(lv.L)] for _ in range(nt)], dtype=np.float64).T.copy()) for _ in range(2)]
+    budgets = (B, B // 2)
+
+    def answers(ctx):
+        out = [ctx.backtrack(Bp) for Bp in budgets]
+        out.append(ctx.pred())
+        out.append(ctx.argmin_table(0) if p == 1 else None)
+        return out
+
+    def same(a, b):
+        for (u, ps, sw), (u2, ps2, sw2) in zip(a[:2], b[:2]):
+            assert np.array_equal(u, u2) and ps == ps2 and np.array_equal(sw, sw2)
+        assert a[2] == b[2]
+        if p == 1:
+            assert np.array_equal(a[3], b[3])
+
+    def right(ctx, df, uo):  # the oracle's answer for the problem the context holds
+        phi, U = oracle_c.bellman(lv, df, uo, B, pk, beta, dt)
+        for Bp in budgets:
+            ou, ops = oracle_c.backtrack(lv, uo, phi, U, B, Bp)
+            u, ps, _ = ctx.backtrack(Bp)
+            assert np.array_equal(u, ou) and ps == ops
+
+    fresh = _ctx(lt, pk, beta, algo)
+    fresh.bellman(*A2, B, dt)
+    ref = answers(fresh)
+    assert not np.array_equal(ref[0][0], A2[1])  # the path moves: u is not a copy of u_old
+    right(fresh, *A2)
+    fresh.close()
+
+    ctx = _ctx(lt, pk, beta, algo)
+    ctx.bellman(*A, B, dt)
+    firstA = answers(ctx)
+    assert not np.array_equal(firstA[0][0], ref[0][0])  # A and A' differ in their answers
+    ctx.bellman(*A2, B, dt)
+    same(answers(ctx), ref)
+    dummy = torch.zeros(lv.M * nt, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    rejected = {
+        "nx": lambda: ctx.bellman(np.zeros((lv.M + 1, nt)), np.zeros((lv.M + 1, nt)), B, dt),
+        "K=0": lambda: ctx.bellman_batch_device(0, dummy.data_ptr(), dummy.data_ptr(), lv.M, nt, B, dt),
+        "B=-1": lambda: ctx.bellman(*A, -1, dt),
+        "B=2^20+1": lambda: ctx.bellman(*A, (1 << 20) + 1, dt),
+        "dt=inf": lambda: ctx.bellman(*A, B, math.inf),
+    }
+    for name, call in rejected.items():
+        with pytest.raises(native.MiocNativeError) as e:
+            call()
+        assert e.value.code == native.MIOC_EINVAL, name
+        same(answers(ctx), ref)
+
+    def no_dp():
+        for call in (lambda: ctx.backtrack(B), ctx.pred, lambda: ctx.argmin_table(0)):
+            with pytest.raises(native.MiocNativeError) as e:
+                call()
+            assert e.value.code == native.MIOC_ESTATE
+
+    bad_df = A[0].copy()
+    bad_df[1, 17] = np.nan
+    with pytest.raises(native.MiocNativeError) as e:
+        ctx.bellman(bad_df, A[1], B, dt)
+    assert e.value.code == native.MIOC_ENONFINITE
+    no_dp()
+    ctx.bellman(*A, B, dt)
+    same(answers(ctx), firstA)
+    right(ctx, *A)
+    bad_uo = A[1].copy()
+    bad_uo[0, 3] = 0.5
+    with pytest.raises(native.InexactError):
+        ctx.bellman(A[0], bad_uo, B, dt)
+    no_dp()
+    ctx.bellman(*A2, B, dt)
+    same(answers(ctx), ref)
+    # a forced algorithm that does not support the problem fails after the arguments were accepted
+    ctx.set_option(native.MIOC_OPT_ALGO, native.MIOC_ALGO_SEPARABLE if p == math.inf else native.MIOC_ALGO_PINF)
+    with pytest.raises(native.MiocNativeError) as e:
+        ctx.bellman(*A, B, dt)
+    assert e.value.code == native.MIOC_EINVAL
+    no_dp()
+    ctx.set_option(native.MIOC_OPT_ALGO, algo)
+    ctx.bellman(*A, B, dt)
+    same(answers(ctx), firstA)
+    right(ctx, *A)
+    ctx.close()
+
+
 def test_trm_on_gpu_matches_trm_on_oracle():
     """TRM driver end to end (fishing, p=Inf and doubletank-shaped p=1): GPU solver == oracle solver."""
     import mioc
