@@ -363,8 +363,9 @@ __device__ __forceinline__ void sd_perm_load(SdPerm &pm, const uint32_t *__restr
 
 // The first phase of row c' of step i: its loaded Ψ (v: this thread's eight positions, + the straddle element srank / xs)
 // into the LDS by rank (psi, for the winners and exact scans) and raw into the transform buffer (stamped by pass 0); the
-// wave's min and max of Ψ and its counts (targets in the trust region, low 16 bits; finite sources, high 16 bits) into
-// sh.rmn / rmx / rnv[w].  Returns this lane's trust-region targets (bit x: target tid | x << 3(M-1) has c' + b̃ <= B).
+// wave's min and max of Ψ and its counts (targets in the trust region, low 16 bits, per-step driver only; finite sources,
+// high 16 bits, exact where the wave holds a +Inf and L / NW otherwise) into sh.rmn / rmx / rnv[w].  Returns this lane's
+// trust-region targets (bit x: target tid | x << 3(M-1) has c' + b̃ <= B).
 // The persistent driver runs it for the NEXT row at the end of a row (the next row's loads have landed by then: the
 // row's late drain waited for them), where the row's stores leave the SIMDs idle; the row body then starts at the
 // barrier that publishes these statistics.
@@ -383,6 +384,76 @@ __device__ __forceinline__ unsigned sdt_stats(const ProblemDev &P, const PyrGeom
                                     (2 * M + 2) * (threadIdx.x >> 6) + M
                               : uo_all + ((size_t)k * P.nt + i) * M;
   (void)df_all;
+  unsigned valid = 0;  // target inside the trust region: c' + b̃_l(i) <= B
+  // finite sources of the wave (high 16 bits) and, per-step driver only, its targets in the trust region (low 16 bits)
+  int nv = 0;
+  double pmn = INFINITY, pmx = -INFINITY;
+  if constexpr (PERSIST) {
+    // ---- valid: bit x is set iff |x - c| <= rr, c = u_old[M-1] - base[M-1], rr = B - c' - bpre: an interval of x,
+    // built from its two ends.  The persistent driver runs only where b̃ <= 7·M everywhere (its dependency window,
+    // mioc_api.cpp), so rows with B - c' >= 7·M have every target inside (workgroup-uniform) and need no u_old at all.
+    // The number of targets inside is not counted here: the row body reads it off the sphere order (sdt_body).
+    const int t = B - cp;
+    valid = 0xFFu;
+    if (t < 7 * M) {
+      int bpre = 0;
+#pragma unroll
+      for (int m = 0; m < M - 1; ++m)
+        bpre += abs(G.base[m] + ((tid >> (3 * m)) & 7) - __builtin_amdgcn_readfirstlane((int)uoi[m]));
+      const int c = __builtin_amdgcn_readfirstlane((int)uoi[M - 1]) - G.base[M - 1], rr = t - bpre;
+      const int lo = min(max(c - rr, 0), 8), hi1 = min(max(c + rr + 1, 0), 8);  // rr < 0: hi1 <= lo
+      valid = hi1 > lo ? (1u << hi1) - (1u << lo) : 0u;
+    }
+    // ---- Ψ into the LDS; min and max over the wave's values.  (sd_strad) a straddling second element arrives as a
+    // quiet NaN (sd_take: its value comes with the seam lane, which overwrites it in the LDS): v_min_f64 / v_max_f64
+    // ignore it, as they do the NaN standing for "no seam element" below.
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const double x = v[2 * q + hh];
+        const int j = (int)((hh ? ein[q].y : ein[q].x) & 0xFFFFu);
+        psi[j] = x;
+        dtv[sd_swz(j)] = x;  // raw, stamped by pass 0
+      }
+    double xe = __longlong_as_double(0x7FF8000000000000ll);
+    if constexpr (sd_strad<M>()) {  // this lane's straddle element
+      const double x = (srank & 0x10000) ? INFINITY : xs;
+      if (srank >= 0) {
+        psi[srank & 0xFFFF] = x;
+        dtv[sd_swz(srank & 0xFFFF)] = x;
+        xe = x;
+      }
+    }
+    // one statement: no wait state between the dependent v_min_f64 / v_max_f64 (v[0] is never the NaN)
+    asm("v_min_f64 %0, %2, %3\n\tv_max_f64 %1, %2, %3\n\t"
+        "v_min_f64 %0, %0, %4\n\tv_max_f64 %1, %1, %4\n\t"
+        "v_min_f64 %0, %0, %5\n\tv_max_f64 %1, %1, %5\n\t"
+        "v_min_f64 %0, %0, %6\n\tv_max_f64 %1, %1, %6\n\t"
+        "v_min_f64 %0, %0, %7\n\tv_max_f64 %1, %1, %7\n\t"
+        "v_min_f64 %0, %0, %8\n\tv_max_f64 %1, %1, %8\n\t"
+        "v_min_f64 %0, %0, %9\n\tv_max_f64 %1, %1, %9\n\t"
+        "v_min_f64 %0, %0, %10\n\tv_max_f64 %1, %1, %10"
+        : "=&v"(pmn), "=&v"(pmx)
+        : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(xe));
+    // ---- finite sources: the count matters only up to SD_SPARSE, and pmx must skip +Inf -- both only where the wave
+    // holds a +Inf at all (rows c' < 7·M and the first steps); otherwise all its L / NW sources are finite
+    nv = (L / ((L / 8) / 64)) << 16;
+    if (__any(pmx == INFINITY)) {
+      nv = 0;
+      pmx = -INFINITY;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const double x = v[q];
+        const bool fin = x < INFINITY;  // (false for the NaN)
+        nv += __popcll(__ballot(fin)) << 16;
+        pmx = sd_max(pmx, fin ? x : -INFINITY);
+      }
+      const bool fin = xe < INFINITY;
+      nv += __popcll(__ballot(fin)) << 16;
+      pmx = sd_max(pmx, fin ? xe : -INFINITY);
+    }
+  } else {
   int lb[M], uo[M];
 #pragma unroll
   for (int m = 0; m < M; ++m) {
@@ -393,17 +464,14 @@ __device__ __forceinline__ unsigned sdt_stats(const ProblemDev &P, const PyrGeom
   int bpre = 0;
 #pragma unroll
   for (int m = 0; m < M - 1; ++m) bpre += abs(lb[m] + ((tid >> (3 * m)) & 7) - uo[m]);
-  unsigned valid = 0;  // target inside the trust region: c' + b̃_l(i) <= B
   // targets in the trust region (low 16 bits) + finite sources (high 16 bits) of the wave: ballots counted on the
   // scalar unit
-  int nv = 0;
 #pragma unroll
   for (int x = 0; x < 8; ++x) {
     const bool in = bpre <= B - cp - abs(lb[M - 1] + x - uo[M - 1]);  // right side wave-uniform
     valid |= (unsigned)in << x;
     nv += __popcll(__ballot(in));
   }
-  double pmn = INFINITY, pmx = -INFINITY;
 #pragma unroll
   for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -418,16 +486,6 @@ __device__ __forceinline__ unsigned sdt_stats(const ProblemDev &P, const PyrGeom
       pmn = sd_min(pmn, x);  // +Inf is neutral
       pmx = sd_max(pmx, __hiloint2double(fin ? __double2hiint(x) : (int)0xFFF00000, __double2loint(x)));  // +Inf -> -Inf
     }
-  if constexpr (sd_strad<M>()) {  // this lane's straddle element
-    const double x = (srank & 0x10000) ? INFINITY : xs;
-    const bool fin = srank >= 0 && x < INFINITY;
-    nv += __popcll(__ballot(fin)) << 16;
-    if (srank >= 0) {
-      psi[srank & 0xFFFF] = x;
-      dtv[sd_swz(srank & 0xFFFF)] = x;
-    }
-    pmn = sd_min(pmn, fin ? x : INFINITY);
-    pmx = sd_max(pmx, fin ? x : -INFINITY);
   }
   sd_wave_stats(pmn, pmx);
   if (lane == 0) {
@@ -448,7 +506,9 @@ __device__ __forceinline__ unsigned sdt_stats(const ProblemDev &P, const PyrGeom
 //            loads, the next step's sphere order and df / u_old); h.late_drain() before the barrier after the winners
 //            (this wave's stores of the previous row have landed), h.publish() after it (the previous row is done).  A
 //            timed-out wait sets sh.stop, which the driver reads after the row; h.tail(empty, outv) once the row's
-//            outputs are final, before its stores (the persistent driver runs the next row's sdt_stats there).
+//            outputs are final, before its stores (the persistent driver runs the next row's sdt_stats there);
+//            h.store16(Sout, e, lo, hi): elements e, e + 1 of the output row (the persistent driver forms the row's
+//            address from its byte offset in the region, Sout unused).
 //   smask, srank: (sd_strad) the pairs q whose second element straddles a sphere seam (bit 3q+2 of smask: not
 //            this lane's to store), and the rank of this lane's straddle element (srank < 0: none)
 // Returns 1 if the row is all +Inf (no target in the trust region or no finite source), else 0.
@@ -555,18 +615,14 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
     // in place: after the forward sweep o[x] covers the sources at <= x; a backward merge of o[x] with
     // o[x+1] + 1 compares a source at <= x with itself shifted by >= 2, never within tol, so every
     // flagged tie is between two distinct sources (as in a merge of disjoint sets)
-    auto merge = [&](double a, double b) {
-      if constexpr (COUNT) {
-        return sd_merge(a, b, tol);
-      } else {
-        dmin = sd_min_abs(dmin, a - b);
-        return sd_min(a, b);
-      }
-    };
+    if constexpr (COUNT) {
 #pragma unroll
-    for (int x = 1; x < 8; ++x) o[x] = merge(o[x], o[x - 1] + 1.0);
+      for (int x = 1; x < 8; ++x) o[x] = sd_merge(o[x], o[x - 1] + 1.0, tol);
 #pragma unroll
-    for (int x = 6; x >= 0; --x) o[x] = merge(o[x], o[x + 1] + 1.0);
+      for (int x = 6; x >= 0; --x) o[x] = sd_merge(o[x], o[x + 1] + 1.0, tol);
+    } else {
+      sd_sweeps(o, dmin);  // both sweeps, |a - b| of every merge folded into dmin
+    }
     if (m + 1 < M) {
 #pragma unroll
       for (int x = 0; x < 8; ++x) dtv[pos[x]] = o[x];
@@ -646,6 +702,15 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
         mx[q] = sh.rmx[q];
         cn[q] = sh.rnv[q];
       }
+      // (persistent driver) the row's targets inside the trust region, as far as the row body asks (none, at most
+      // SD_FEW, more): the sphere order of step i ascends in b̃, so at most q levels have b̃ <= B - c' iff entry q has
+      // b̃ > B - c' -- two broadcast reads in the same batch instead of eight ballots per wave (sdt_stats)
+      [[maybe_unused]] uint32_t e0 = 0, ef = 0;
+      if constexpr (PERSIST) {
+        static_assert(SD_FEW < L, "entry SD_FEW of the sphere order");
+        e0 = pout[0];
+        ef = pout[SD_FEW];
+      }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
       for (int h = NW / 2; h >= 1; h >>= 1)
@@ -657,10 +722,10 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
         }
       pmn = mn[0];
       pmx = mx[0];
-      nv = cn[0];
+      nf = cn[0] >> 16;
+      nv = cn[0] & 0xFFFF;
+      if constexpr (PERSIST) nv = (int)(e0 >> 16) > P.B - cp ? 0 : (int)(ef >> 16) > P.B - cp ? SD_FEW : SD_FEW + 1;
     }
-    nf = nv >> 16;
-    nv &= 0xFFFF;
     SD_STAMP(1);
     // no target in the trust region, or nothing reachable: the row is +Inf and U unwritten (0xFFFF)
     empty = __builtin_amdgcn_readfirstlane((int)(nv == 0 || !(pmn < INFINITY))) != 0;  // uniform
@@ -794,8 +859,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
   h.tail(empty, outv);
 #pragma unroll
   for (int q = 0; q < 4; ++q)
-    sd_store16<PERSIST>(Sout, L * 8, sd_p2<M>(tid, q), __double_as_longlong(go[2 * q]),
-                        __double_as_longlong(go[2 * q + 1]));
+    h.store16(Sout, sd_p2<M>(tid, q), __double_as_longlong(go[2 * q]), __double_as_longlong(go[2 * q + 1]));
   *reinterpret_cast<ulonglong2 *>(UU + 8 * tid) = ut;  // read by later launches only (backtrack)
   SD_STAMP(9);
   SD_RSTAMP(14);
@@ -1006,6 +1070,9 @@ struct SdHooksNone {
   __device__ __forceinline__ void late_drain() {}
   __device__ __forceinline__ void publish() {}
   __device__ __forceinline__ void tail(bool, const double *) {}
+  __device__ __forceinline__ void store16(double *Sout, int e, unsigned long long lo, unsigned long long hi) {
+    sd_store16<false>(Sout, 0, e, lo, hi);
+  }
 };
 
 // LDS bytes of the row body: Ψ by rank, the transform / output values, the U row, the scan list, and two
@@ -1029,13 +1096,19 @@ __device__ __forceinline__ void sd_perm_dma(const uint32_t *src, uint32_t *slot)
 // write LDS, and does not make every later LDS atomic wait (vmcnt(0)) for them -- and for the row loads queued
 // behind.  The driver orders them itself: they are issued before the next row's loads and complete under the
 // counted wait at that row's start, and every reader of the slot reads it after a later vmcnt(0) and a barrier.
+// The LDS destinations are byte addresses in the LDS (sd_lds_addr of the kernel's own shared array, a link-time
+// constant there): converted from a generic pointer each would carry that pointer's null test and its 64-bit value.
+__device__ __forceinline__ unsigned sd_lds_addr(const void *p) {
+  return (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)p);
+}
 template <int M>
-__device__ __forceinline__ void sd_perm_dma_asm(const uint32_t *src, uint32_t *slot) {
+__device__ __forceinline__ void sd_perm_dma_asm(const uint32_t *src, unsigned lds0) {
   constexpr int L = 1 << (3 * M), T = L / 8, NW = T / 64, NC = L * 4 / 1024;
+  static_assert(NC % NW == 0, "every wave copies the same number of chunks (no lane predicate)");
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)slot);
 #pragma unroll
-  for (int c = wave; c < NC; c += NW) {
+  for (int cc = 0; cc < NC / NW; ++cc) {
+    const int c = wave + NW * cc;
     const char *g = (const char *)src + c * 1024 + lane * 16;
     const unsigned m0 = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)c * 1024u);
     unsigned keep;  // M0 is reserved to the compiler: saved and restored around the copy
@@ -1049,15 +1122,25 @@ __device__ __forceinline__ void sd_perm_dma_asm(const uint32_t *src, uint32_t *s
 // df(:, s) and u_old(:, s) (M doubles each) into this wave's LDS words, and the flag same2[s - 1] (u_old(s-1) ==
 // u_old(s+1): the sphere order of step s-1 equals the one its slot holds, k_pyr_order) after them: lanes 0..4M move
 // one dword each (global_load_lds_dword, LDS-DMA, inline asm for the same reason as sd_perm_dma_asm)
+// The persistent driver keeps each lane's source of step 0 (sd_dfuo_src) and the lane's byte stride per step
+// (sd_dfuo_step) instead of the three arrays' addresses: go() then forms a lane's source with one multiply-add.
 template <int M>
-__device__ __forceinline__ void sd_dfuo_dma(const double *df, const double *uo, const int32_t *flag, unsigned char *sds) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane < 4 * M + (flag ? 1 : 0)) {
-    const char *g = lane < 2 * M   ? (const char *)df + 4 * lane
-                    : lane < 4 * M ? (const char *)uo + 4 * (lane - 2 * M)
-                                   : (const char *)flag;
-    const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)(sds + sd_dfuo_offset<M>())) +
-                          wave * (unsigned)sd_dfuo_stride<M>();
+__device__ __forceinline__ const char *sd_dfuo_src(const double *df, const double *uo, const int32_t *flag) {
+  const int lane = threadIdx.x & 63;
+  return lane < 2 * M   ? (const char *)df + 4 * lane
+         : lane < 4 * M ? (const char *)uo + 4 * (lane - 2 * M)
+                        : (const char *)flag;
+}
+template <int M>
+__device__ __forceinline__ unsigned sd_dfuo_step() {
+  return (threadIdx.x & 63) < 4 * M ? (unsigned)(M * sizeof(double)) : (unsigned)sizeof(int32_t);
+}
+// g: this lane's source (sd_dfuo_src of this step's df(:, s), u_old(:, s) and &same2[s - 1]); has_flag: s >= 1
+template <int M>
+__device__ __forceinline__ void sd_dfuo_dma(const char *g, bool has_flag, unsigned ldsb) {
+  const int wave = threadIdx.x >> 6, lane = sd_tid() & 63;  // (sd_tid: see SdPipe::early)
+  if (lane < 4 * M + (has_flag ? 1 : 0)) {
+    const unsigned lds0 = ldsb + (unsigned)sd_dfuo_offset<M>() + wave * (unsigned)sd_dfuo_stride<M>();
     const unsigned m0 = __builtin_amdgcn_readfirstlane(lds0);
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
@@ -1069,12 +1152,11 @@ __device__ __forceinline__ void sd_dfuo_dma(const double *df, const double *uo, 
 
 // (sd_strad) this wave's slab of a step's seam list (SD_STRAD_N uint16 = 64 bytes) into the slot's list in LDS:
 // lanes 0..15 move one dword each (LDS-DMA, inline asm as sd_perm_dma_asm); only this wave reads its slab's list
-__device__ __forceinline__ void sd_strad_dma(const uint16_t *src, uint16_t *slot) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+__device__ __forceinline__ void sd_strad_dma(const uint16_t *src, unsigned lds_slot) {
+  const int wave = threadIdx.x >> 6, lane = sd_tid() & 63;  // (sd_tid: see SdPipe::early)
   if (lane < SD_STRAD_N / 2) {
     const char *g = (const char *)(src + wave * SD_STRAD_N) + 4 * lane;
-    const unsigned m0 = __builtin_amdgcn_readfirstlane(
-        (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)(slot + wave * SD_STRAD_N)));
+    const unsigned m0 = __builtin_amdgcn_readfirstlane(lds_slot + (unsigned)(wave * SD_STRAD_N * sizeof(uint16_t)));
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep)
@@ -1269,7 +1351,7 @@ __device__ __forceinline__ void sd_read_next(SdNext &n, const uint32_t *pin, con
   n.sp = 0xFFFFu;
   n.se = 0;
   if constexpr (sd_strad<M>()) {
-    const int lane = tid & 63, wv = tid >> 6;
+    const int lane = sd_tid() & 63, wv = tid >> 6;
     n.sp = lane < SD_STRAD_N ? sl[wv * SD_STRAD_N + lane] : 0xFFFFu;
     n.se = pin[sd_seam_pos<M>(wv, (int)(n.sp & (L / NW - 1)))];
   }
@@ -1318,7 +1400,7 @@ __device__ __forceinline__ void sd_issue_pipe(SdRaw &w, __amdgpu_buffer_rsrc_t r
   }
   w.mask = mask;
 }
-// this lane's eight values; (sd_strad) the second element of a straddling pair is +Inf here -- its value comes with
+// this lane's eight values; (sd_strad) the second element of a straddling pair is a NaN here -- its value comes with
 // the lane that loaded it as a straddle element, which writes it after this lane (in-wave LDS order)
 template <int M>
 __device__ __forceinline__ void sd_take(double (&v)[8], const SdRaw &w) {
@@ -1329,7 +1411,8 @@ __device__ __forceinline__ void sd_take(double (&v)[8], const SdRaw &w) {
     const double a1 = __hiloint2double((int)w.a[q].w, (int)w.a[q].z);
     v[2 * q] = (m & 1) ? INFINITY : a0;
     if constexpr (sd_strad<M>()) {
-      v[2 * q + 1] = (m & 6) ? INFINITY : a1;
+      // (a straddling second element: a quiet NaN, which the statistics ignore -- sdt_stats)
+      v[2 * q + 1] = (m & 4) ? __longlong_as_double(0x7FF8000000000000ll) : (m & 2) ? INFINITY : a1;
     } else {
       const double b1 = __hiloint2double((int)w.b[q].y, (int)w.b[q].x);
       v[2 * q + 1] = (m & 2) ? INFINITY : (m & 4) ? b1 : a1;
@@ -1367,17 +1450,27 @@ struct SdPipe {
   int cp, i, ncp, ni;
   bool has_next;
   // constants of the launch
-  int lo, hi, B, NB, nt, k, g0;
+  int lo, hi, B, nt, k, g0;
+  int war;  // nt - i - NB = token(i + NB - 1): the token this step's write-after-read waits need (stepped with i)
   unsigned spin_limit, rowb, bufb, r0b;
   int32_t *dk, *lk, *err;
   const uint32_t *pk;
   uint32_t *slot;
   __amdgpu_buffer_rsrc_t rs;
-  const double *dfa, *uoa;
-  const int32_t *sm;  // same2 (k_pyr_order): u_old(s) == u_old(s + 2) per step s
+  // per lane: the source of its df / u_old / same2 word at step 0 (sd_dfuo_src: df(:, 0), u_old(:, 0), &same2[-1]) and
+  // its stride per step
+  const char *dfuo0;
+  unsigned dfuo_st;
   const uint16_t *sk;  // (sd_strad) this subproblem's seam lists, [nt][8][SD_STRAD_N]
   uint16_t *sslot;     // (sd_strad) the two slots' seam lists in LDS
   unsigned char *sds;
+  unsigned ldsb;  // sd_lds_addr(sds)
+  __device__ __forceinline__ unsigned lds_slot(int step) const {  // the sphere-order slot of `step`
+    return ldsb + (unsigned)sd_slot_offset<M>() + (unsigned)(step & 1) * (unsigned)(L * sizeof(uint32_t));
+  }
+  __device__ __forceinline__ unsigned lds_sslot(int step) const {  // its seam lists
+    return ldsb + (unsigned)sd_strad_offset<M>() + (unsigned)(step & 1) * (unsigned)(8 * SD_STRAD_N * sizeof(uint16_t));
+  }
   SdtShared<(1 << (3 * M - 3)) / 64> *sh;
   // carried from row to row: the previous row (its `done` is published at this row's publish()), this wave's polls,
   // the next row's loads in flight
@@ -1392,6 +1485,7 @@ struct SdPipe {
   unsigned valid_next;
   int whole;  // one row per workgroup (hi - lo == 1)
   unsigned nbo;     // byte offset of the next row's input buffer, (ni + 1) % NB (kept by the driver: no division)
+  unsigned sob;     // byte offset of this row's output row in the region (buffer i % NB, row cp)
   bool stop_seen;   // sh.stop as read after the row's barrier 3 (publish)
 
   // every wave polls its own dependency flags (lanes 0-31 RAW for the next row, 32-63 WAR for this row's stores; a
@@ -1399,7 +1493,9 @@ struct SdPipe {
   // this row's loads (early()); checked in go()
   __device__ __forceinline__ void early() {
     SD_TL_AT(g0, i, nt, 1);
-    const int tid = threadIdx.x, lane = tid & 63, s = lane < 32 ? lane + 1 : lane - 31;
+    // (sd_tid: the lane predicates below are recomputed per row -- kept live across the row loop as lane masks they cost
+    // two SGPRs each, and the loop has none to spare)
+    const int tid = sd_tid(), lane = tid & 63, s = lane < 32 ? lane + 1 : lane - 31;
     fp = lk + cp * SDT_FLAG_STRIDE;
     need = INT32_MIN;
     if (lane < 32) {
@@ -1410,21 +1506,21 @@ struct SdPipe {
       }
     } else {
       const int r = cp + s;
-      if (s <= 7 * M && r <= B && r >= hi && nt - i - NB > 0) {
+      if (s <= 7 * M && r <= B && r >= hi && war > 0) {
         fp = lk + r * SDT_FLAG_STRIDE;
-        need = nt - i - NB;  // token(i + NB - 1)
+        need = war;  // token(i + NB - 1)
       }
     }
     val = __hip_atomic_load(fp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // diagnostics [4]: this row reuses a staging buffer that a row above may still read (some WAR lane armed above)
-    if (tid == 0 && nt - i - NB > 0 && min(cp + 7 * M, B) >= max(cp + 1, hi)) ++sh->cnt[2];
+    if (tid == 0 && war > 0 && min(cp + 7 * M, B) >= max(cp + 1, hi)) ++sh->cnt[2];
   }
   // after the row's first barrier (every wave has consumed this row's loads): publish `loaded`; this wave waits until
   // its polls match (re-polling), then issues the next row's loads -- the measured-valid consumer form: the polling
   // wave loads only after its own poll matched
   __device__ __forceinline__ void go() {
     SD_TL_AT(g0, i, nt, 2);
-    const int tid = threadIdx.x;
+    const int tid = sd_tid();
     // evaluated before the flag store below: the compiler's wait for `val` would otherwise cover that store
     bool ready = __all(val >= need);
     if (tid == 0) __hip_atomic_store(lk + cp * SDT_FLAG_STRIDE, nt - 1 - i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1456,11 +1552,10 @@ struct SdPipe {
       sd_read_next<M>(nx, slot + ((ni + 1) & 1) * L, sslot + ((ni + 1) & 1) * 8 * SD_STRAD_N);
       sd_issue_pipe<M>(raw, rs, nx, ncp, nbo, r0b + (unsigned)(ni + 1) * rowb, rowb);
       if (ni != i && !same) {
-        sd_perm_dma_asm<M>(pk + (size_t)ni * L, slot + (ni & 1) * L);
-        if constexpr (sd_strad<M>()) sd_strad_dma(sk + (size_t)ni * 8 * SD_STRAD_N, sslot + (ni & 1) * 8 * SD_STRAD_N);
+        sd_perm_dma_asm<M>(pk + (size_t)ni * L, lds_slot(ni));
+        if constexpr (sd_strad<M>()) sd_strad_dma(sk + (size_t)ni * 8 * SD_STRAD_N, lds_sslot(ni));
       }
-      sd_dfuo_dma<M>(dfa + ((size_t)k * nt + ni) * M, uoa + ((size_t)k * nt + ni) * M,
-                     ni >= 1 ? sm + (size_t)k * nt + ni - 1 : nullptr, sds);
+      sd_dfuo_dma<M>(dfuo0 + (size_t)((unsigned)ni * dfuo_st), ni >= 1, ldsb);
     }
     SD_TL_AT(g0, i, nt, 4);
   }
@@ -1474,7 +1569,7 @@ struct SdPipe {
     SD_TL_AT(g0, i, nt, 5);
   }
   __device__ __forceinline__ void publish() {
-    if (threadIdx.x == 0 && pcp >= 0)
+    if (sd_tid() == 0 && pcp >= 0)
       __hip_atomic_store(dk + pcp * SDT_FLAG_STRIDE, nt - 1 - pi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // a timed-out wait of this row (go(), before this barrier) set sh.stop: read here, where every wave reads the same
     // value, so that the driver's exit test after the row needs no LDS round trip of its own
@@ -1482,6 +1577,13 @@ struct SdPipe {
     pcp = cp;
     pi = i;
   }
+  // the row's `sc1` stores, through a resource of the row's own, formed here from the row's byte offset (the row's
+  // 64-bit address is not kept live across the body).  Stored through the region's resource `rs` with the offset as
+  // the instruction's scalar offset, rows were read stale by the rows above: not kept.
+  __device__ __forceinline__ void store16(double *, int e, unsigned long long lo, unsigned long long hi) {
+    sd_store16<true>(reg + sob / 8, L * 8, e, lo, hi);
+  }
+  double *reg;  // the subproblem's region
   // the next row's statistics phase (its loads landed at this row's late drain): after this row's outputs are final,
   // before its stores.  A one-row workgroup's next row reads its own row of this step, whose stores are not issued yet:
   // the sphere-0 source at distance 0 (u_old(i) on the level grid: position 0 with b̃ = 0, lane 0 of wave 0) is this
@@ -1490,14 +1592,14 @@ struct SdPipe {
     if (!has_next) return;
     double v[8];
     sd_take<M>(v, raw);
-    if (whole && (threadIdx.x & 63) == 0 && (raw.e[0].x >> 16) == 0) v[0] = empty ? INFINITY : outv[raw.e[0].x & 0xFFFFu];
+    if (whole && (sd_tid() & 63) == 0 && (raw.e[0].x >> 16) == 0) v[0] = empty ? INFINITY : outv[raw.e[0].x & 0xFFFFu];
     const double xs = __hiloint2double((int)raw.sv.y, (int)raw.sv.x);
-    valid_next = sdt_stats<M, true>(*Pp, *Gp, k, ncp, ni, v, raw.e, *sh, sds, dfa, uoa, raw.srank, xs);
+    valid_next = sdt_stats<M, true>(*Pp, *Gp, k, ncp, ni, v, raw.e, *sh, sds, nullptr, nullptr, raw.srank, xs);
   }
 };
 
 template <int M>
-__global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P, LevelsDev Lv, PyrGeom G,
+__global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P_arg, LevelsDev Lv_arg, PyrGeom G,
                                                               const uint32_t *__restrict__ perm_all, double *S_all,
                                                               size_t kstride, int NB, uint16_t *__restrict__ UU_all,
                                                               size_t uu_stride_k, int32_t *__restrict__ counters,
@@ -1509,6 +1611,13 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P, L
   constexpr int L = 1 << (3 * M);
   extern __shared__ __attribute__((aligned(16))) unsigned char sds[];
   __shared__ SdtShared<(1 << (3 * M - 3)) / 64> sh;
+  // Δt, β and 1/β are read by double-precision VALU instructions only: held in vector registers across the row loop
+  // (the loop's scalar registers are all taken; as scalars these six were spilled to lanes and read back every row)
+  ProblemDev P = P_arg;
+  LevelsDev Lv = Lv_arg;
+  asm volatile("" : "+v"(P.dt), "+v"(Lv.beta), "+v"(Lv.inv_beta));
+  // likewise what only the timeout path and the epilogue read: the error word, the spin limit, the counters
+  asm volatile("" : "+v"(counters), "+v"(spin_limit));
   const int B = P.B, R = B + 1, nt = P.nt, tid = threadIdx.x;
   // (each flag SDT_FLAG_STRIDE words apart)
   const int FR = R * SDT_FLAG_STRIDE;
@@ -1518,20 +1627,27 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P, L
   if (k >= P.K) return;
   const int base = B / W, extra = B - base * W;  // rows 1..B, the longer chunks highest
   const int lo = 1 + wl * base + max(0, wl - (W - extra)), hi = lo + base + (wl >= W - extra ? 1 : 0);
+  __builtin_assume(lo < hi);  // W <= B: every chunk has a row
   uint32_t *slot = reinterpret_cast<uint32_t *>(sds + sd_slot_offset<M>());
   auto pslot = [&](int step) { return slot + (step & 1) * L; };  // sphere order of `step`
   // this subproblem's region: NB staging buffers of R rows, then row 0 of every step (k_sdt_row0); one buffer
   // resource over all of it (the host checks it is below 4 GiB)
   double *reg = S_all + (size_t)k * kstride;
   SdPipe<M> h;
-  h.lo = lo, h.hi = hi, h.B = B, h.NB = NB, h.nt = nt, h.k = k, h.g0 = k * R + lo;
+  h.lo = lo, h.hi = hi, h.B = B, h.war = 2 - NB, h.nt = nt, h.k = k, h.g0 = k * R + lo;
   h.spin_limit = spin_limit, h.rowb = (unsigned)L * 8u, h.bufb = (unsigned)R * h.rowb, h.r0b = (unsigned)NB * h.bufb;
+  asm volatile("" : "+v"(err));
   h.dk = done + (size_t)k * FR, h.lk = loaded + (size_t)k * FR, h.err = err;
   h.pk = perm_all + (size_t)k * nt * L, h.slot = slot;
   h.rs = __builtin_amdgcn_make_buffer_rsrc(reg, 0, (int)(h.r0b + (unsigned)nt * h.rowb), 0x00020000);
-  h.dfa = df_all, h.uoa = uo_all, h.sm = same2, h.sds = sds, h.sh = &sh;
+  h.dfuo0 = sd_dfuo_src<M>(df_all + (size_t)k * nt * M, uo_all + (size_t)k * nt * M, same2 + (size_t)k * nt - 1);
+  h.dfuo_st = sd_dfuo_step<M>();
+  h.sds = sds, h.ldsb = sd_lds_addr(sds), h.sh = &sh;
   h.sk = strad ? strad + (size_t)k * nt * 8 * SD_STRAD_N : nullptr;
   h.sslot = reinterpret_cast<uint16_t *>(sds + sd_strad_offset<M>());
+  // only ever added to per-lane offsets (the LDS-DMA sources; the flags a lane polls or stores)
+  asm volatile("" : "+v"(h.pk), "+v"(h.sk), "+v"(h.dk), "+v"(h.lk));
+  h.reg = reg;
   h.pcp = -1, h.pi = 0;
   if (tid == 0) {
     sh.stop = 0;
@@ -1540,14 +1656,13 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P, L
   }
   // prologue: both sphere orders of the first step, df / u_old, and the first row's loads (the terminal row was
   // written by an earlier launch)
-  sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 1) * L, pslot(nt - 1));
-  sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 2) * L, pslot(nt - 2));
+  sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 1) * L, h.lds_slot(nt - 1));
+  sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 2) * L, h.lds_slot(nt - 2));
   if constexpr (sd_strad<M>()) {
-    sd_strad_dma(h.sk + (size_t)(nt - 1) * 8 * SD_STRAD_N, h.sslot + ((nt - 1) & 1) * 8 * SD_STRAD_N);
-    sd_strad_dma(h.sk + (size_t)(nt - 2) * 8 * SD_STRAD_N, h.sslot + ((nt - 2) & 1) * 8 * SD_STRAD_N);
+    sd_strad_dma(h.sk + (size_t)(nt - 1) * 8 * SD_STRAD_N, h.lds_sslot(nt - 1));
+    sd_strad_dma(h.sk + (size_t)(nt - 2) * 8 * SD_STRAD_N, h.lds_sslot(nt - 2));
   }
-  sd_dfuo_dma<M>(df_all + ((size_t)k * nt + nt - 2) * M, uo_all + ((size_t)k * nt + nt - 2) * M,
-                 nt >= 3 ? same2 + (size_t)k * nt + nt - 3 : nullptr, sds);
+  sd_dfuo_dma<M>(h.dfuo0 + (size_t)((unsigned)(nt - 2) * h.dfuo_st), nt >= 3, h.ldsb);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   sd_bar();
   sd_read_next<M>(h.nx, pslot(nt - 1), h.sslot + ((nt - 1) & 1) * 8 * SD_STRAD_N);
@@ -1567,6 +1682,8 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P, L
   bool stop = false;
   // the staging buffers of steps i and i + 1 (i % NB, (i + 1) % NB), stepped down with i instead of divided per row
   int bi = (nt - 2) % NB, bi1 = (nt - 1) % NB;
+  // the U rows of step i (stepped down with i: R·L < 2^28 elements, the host bounds a staging buffer below 2^31 bytes)
+  uint16_t *uu_i = UU_all + (size_t)k * uu_stride_k + (size_t)(nt - 2) * ((size_t)R * L);
 #pragma nounroll
   for (int i = nt - 2; i >= 0 && !stop; --i) {
 #pragma nounroll
@@ -1576,6 +1693,7 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P, L
       h.ncp = last_row ? lo : cp + 1, h.ni = last_row ? i - 1 : i;  // the next row
       h.has_next = h.ni >= 0;
       h.nbo = (unsigned)(last_row ? bi : bi1) * h.bufb;  // buffer (ni + 1) % NB
+      h.sob = (unsigned)bi * h.bufb + (unsigned)cp * h.rowb;
       const int g = cp == lo ? h.g0 : 1 << 30;  // timeline stamps: the chunk's first row
       (void)g;
       SD_TL(0);
@@ -1589,18 +1707,20 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P, L
       uint2 ein[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) ein[q] = h.raw.e[q];
-      sdt_body<M, true>(P, Lv, G, k, cp, i, h.valid_next, ein, pslot(i + 1), pslot(i),
-                        reg + (size_t)bi * R * L + (size_t)cp * L,
-                        UU_all + (size_t)k * uu_stride_k + (size_t)i * ((size_t)R * L) + (size_t)cp * L, sh, sds, h,
-                        df_all, uo_all, par, h.raw.mask, h.raw.srank);
+      sdt_body<M, true>(P, Lv, G, k, cp, i, h.valid_next, ein, pslot(i + 1), pslot(i), nullptr,
+                        uu_i + (unsigned)cp * (unsigned)L, sh, sds, h, df_all, uo_all, par, h.raw.mask, h.raw.srank);
       par ^= 1;
       SD_TL(6);
       stop = h.stop_seen;  // read after the row's barrier 3 (every path has one)
     }
     bi1 = bi;
     bi = bi == 0 ? NB - 1 : bi - 1;
+    unsigned rows = (unsigned)R;
+    asm volatile("" : "+s"(rows));  // (the step's byte count is formed here, not kept across the row loop)
+    uu_i = reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(uu_i) - rows * (unsigned)(L * sizeof(uint16_t)));
+    ++h.war;
   }
-  if (tid == 0) {
+  if (sd_tid() == 0) {
     if (sh.cnt[0]) atomicAdd(&counters[0], sh.cnt[0]);
     if (sh.cnt[1]) atomicAdd(&counters[1], sh.cnt[1]);
     if (sh.cnt[2]) atomicAdd(&counters[4], sh.cnt[2]);

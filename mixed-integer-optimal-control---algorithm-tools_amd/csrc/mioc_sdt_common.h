@@ -36,6 +36,26 @@ __device__ __forceinline__ double sd_max(double a, double b) {
   return r;
 }
 
+// One pass's forward and backward sweep over a line of eight values (unit step 1.0) as ONE asm statement: per merge of
+// o[x] with its neighbour o[y] + 1, `t = o[y] + 1; d = o[x] - t; o[x] = min(o[x], t); dmin = min(dmin, |d|)` -- the
+// operations and operand order of sd_min(a, b) / sd_min_abs(dmin, a - b), 14 merges.  As separate asm statements every
+// v_min_f64 pair drew the compiler's boundary wait state (`s_nop 0`) before the next merge's v_add_f64, which no
+// hardware rule asks for between these instructions; inside one statement nothing is padded.  The fold into dmin sits
+// behind the value's own min, off the value chain; +Inf - +Inf is NaN, which v_min_f64 ignores.
+#define SD_MG(X, Y)                      \
+  "v_add_f64 %9, %" #Y ", 1.0\n\t"       \
+  "v_add_f64 %10, %" #X ", -%9\n\t"      \
+  "v_min_f64 %" #X ", %" #X ", %9\n\t"   \
+  "v_min_f64 %8, %8, |%10|\n\t"
+__device__ __forceinline__ void sd_sweeps(double (&o)[8], double &dmin) {
+  double t, d;
+  asm(SD_MG(1, 0) SD_MG(2, 1) SD_MG(3, 2) SD_MG(4, 3) SD_MG(5, 4) SD_MG(6, 5) SD_MG(7, 6)
+      SD_MG(6, 7) SD_MG(5, 6) SD_MG(4, 5) SD_MG(3, 4) SD_MG(2, 3) SD_MG(1, 2) SD_MG(0, 1)
+      : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]), "+v"(o[4]), "+v"(o[5]), "+v"(o[6]), "+v"(o[7]), "+v"(dmin),
+        "=&v"(t), "=&v"(d));
+}
+#undef SD_MG
+
 // The thread index as a value the compiler cannot hoist out of the persistent driver's row loop: everything the
 // row body derives from it (LDS addresses of the passes, swizzles, store offsets) is recomputed per row instead of
 // being kept live in VGPRs across the whole loop, which would leave the body no registers (spills to scratch join
@@ -73,15 +93,25 @@ __device__ __forceinline__ double sd_dpp_d(double x) {
 __device__ __forceinline__ double sd_rdl(double x, int l) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
 }
-// (min and max without llvm.minnum's canonicalisation: the operands are finite or ±Inf, never NaN)
+// (min and max without llvm.minnum's canonicalisation: the operands are finite, ±Inf or a quiet NaN, which v_min_f64 /
+// v_max_f64 ignore).  The result is valid in lanes 0..15 only (lane 0 stores it): after the four DPP steps each lane
+// holds its row's result, and row 0 folds in the other three rows' as scalar operands.  Each step's min and max share
+// one asm statement, so the compiler's wait state before the next DPP read comes once per step.
+__device__ __forceinline__ void sd_minmax(double &mn, double &mx, double a, double b) {
+  asm("v_min_f64 %0, %0, %2\n\tv_max_f64 %1, %1, %3" : "+v"(mn), "+v"(mx) : "v"(a), "v"(b));
+}
+__device__ __forceinline__ void sd_minmax_s(double &mn, double &mx, double a, double b) {  // a, b wave-uniform
+  asm("v_min_f64 %0, %2, %0\n\tv_max_f64 %1, %3, %1" : "+v"(mn), "+v"(mx) : "s"(a), "s"(b));
+}
 __device__ __forceinline__ void sd_wave_stats(double &mn, double &mx) {
-#define SD_STEP(C)                             \
-  mn = sd_min(mn, sd_dpp_d<C>(mn));            \
-  mx = sd_max(mx, sd_dpp_d<C>(mx));
+#define SD_STEP(C) sd_minmax(mn, mx, sd_dpp_d<C>(mn), sd_dpp_d<C>(mx));
   SD_STEP(0xB1) SD_STEP(0x4E) SD_STEP(0x141) SD_STEP(0x140)
 #undef SD_STEP
-  mn = sd_min(sd_min(sd_rdl(mn, 0), sd_rdl(mn, 16)), sd_min(sd_rdl(mn, 32), sd_rdl(mn, 48)));
-  mx = sd_max(sd_max(sd_rdl(mx, 0), sd_rdl(mx, 16)), sd_max(sd_rdl(mx, 32), sd_rdl(mx, 48)));
+  const double n1 = sd_rdl(mn, 16), n2 = sd_rdl(mn, 32), n3 = sd_rdl(mn, 48);
+  const double x1 = sd_rdl(mx, 16), x2 = sd_rdl(mx, 32), x3 = sd_rdl(mx, 48);
+  sd_minmax_s(mn, mx, n1, x1);
+  sd_minmax_s(mn, mx, n2, x2);
+  sd_minmax_s(mn, mx, n3, x3);
 }
 
 // LDS position of rank r (3 bits per dimension): XOR swizzle so that each 32-lane half of a pass reads
