@@ -37,6 +37,7 @@ extern "C" {
                                unwritten U cell at HelpFunctions.jl:116 */
 #define MIOC_ESTATE -6      /* call order violated (e.g. backtrack before bellman, B_use > B) */
 #define MIOC_ENONFINITE -7  /* non-finite gradient entry */
+#define MIOC_ECOMPILE -8    /* the hook source did not compile; the log says why */
 
 /* ---- switching-cost kinds: beta * (sum_m |nu_jm - nu_lm|^p)^(1/p), HelpFunctions.jl:63-67 ----- */
 #define MIOC_P_INF 0    /* p = Inf: the reference evaluates (sum |d|^Inf)^(1/Inf) == x^0.0 == 1.0, so
@@ -211,7 +212,7 @@ int32_t mioc_tv_device(mioc_ctx *ctx, int64_t K, const double *d_u, int64_t nx, 
  *     (offset 0: gate word, 4: any-active word, 8: copy word; then K doubles Δᵏ, K doubles TV_old, K int32 k,
  *     K int32 flags (1 inner, 2 halved, 4 stopped), K int32 outer iterations per restart).
  *   mioc_trm_attach(ctx, d_state): while the gate word is 0, the kernels of mioc_backtrack_batch*_device,
- *     mioc_pred_batch_device, mioc_ode_eval_device, mioc_heat_eval_device and mioc_conv_eval_device return at once;
+ *     mioc_pred_batch_device, mioc_ode_eval_device, mioc_ode_program_eval_device, mioc_heat_eval_device and mioc_conv_eval_device return at once;
  *     NULL detaches.
  *   mioc_trm_outer_begin_device: multi-trust.jl:99-107 (TV_old = TV_p(u), Δᵏ = Δ⁰, k = 1, budgets = B, every
  *     restart not stopped enters its inner loop; the gate opens if any did).
@@ -262,6 +263,69 @@ int32_t mioc_batch_multi(mioc_ctx *const *ctxs, int32_t nctx, int64_t K, const d
 #define MIOC_ODE_VANDERPOL 3
 int32_t mioc_ode_eval_device(mioc_ctx *ctx, int32_t problem, int64_t K, const double *d_x, int64_t nx, int64_t nt,
                              double T0, double T1, const double *params, int32_t nparams, double *d_J, double *d_df);
+
+/*
+ * User-defined ODE objectives: the reference's extension point (a subclass of AbstractODEObjective with the hooks
+ * F!, Fy!, Fu!, G, Gy!, Gu!, julia_opt/ODEObjective.jl:243-248) for problems other than the three above.  The caller
+ * hands the six hooks over as HIP source text; the library compiles them into its explicit-Euler / adjoint sweep for
+ * gfx950 at run time (hiprtc) and launches that kernel: min ∫ G(t, y, u) dt  s.t.  y' = F(t, y, u), y(T0) = state0,
+ * with ny states, nx controls (discrete controls only, the DP's) and nparams parameters.
+ *
+ * Hook contract.  The text is compiled as HIP C++ in front of the kernel; NY, NX and NP (= ny, nx, nparams) are
+ * defined as macros before it.  It may define helper __device__ functions, and it defines exactly these six:
+ *
+ *   __device__ void   F (const double *p, int i, double t, const double *y, const double *x, double *f);
+ *   __device__ void   Fy(const double *p, int i, double t, const double *y, const double *x, double (*fy)[NY]);
+ *   __device__ void   Fu(const double *p, int i, double t, const double *y, const double *x, double (*fu)[NX]);
+ *   __device__ double G (const double *p, int i, double t, const double *y, const double *x);
+ *   __device__ void   Gy(const double *p, int i, double t, const double *y, const double *x, double *gy);
+ *   __device__ void   Gu(const double *p, int i, double t, const double *y, const double *x, double *gu);
+ *
+ *   p: the NP parameters; y: the NY states; x: the NX controls of one time step; t = T0 + i*tau, tau = (T1 - T0)/nt.
+ *   F  writes the right-hand side f[r] = F_r(t, y, x), every entry (f is uninitialised);
+ *   Fy writes fy[r][c] = dF_r/dy_c;  Fu writes fu[r][m] = dF_r/dx_m;  G returns the running cost;
+ *   Gy writes gy[c] = dG/dy_c;  Gu writes gu[m] = dG/dx_m.
+ *   fy, fu, gy and gu are zeroed once per evaluation and not between calls (ODEObjective.jl:155-162): a hook may
+ *   write only the entries that are not structurally zero, but an entry it writes in one call it writes in all.
+ *   Hooks must not touch memory other than their arguments, and they must not write p, y or x.
+ *
+ * The step index i takes exactly the values the reference passes (0-based here; y_j = the state after j steps,
+ * y_0 = state0; x_j = column j of the control):
+ *   F   F(i, y_i, x_i) for i = 0..nt-1                                     (the Euler step y_{i+1} = y_i + tau*f)
+ *   G   G(0, y_0, x_0) with weight 1/2, then G(i+1, y_{i+1}, x_{i+1}) for i = 0..nt-2, then G(nt-1, y_nt, x_{nt-1})
+ *       with weight 1/2 -- the running cost may depend on the control        (ODEObjective.jl:130-146)
+ *   Gy  Gy(nt, y_nt, x_{nt-1}) at the terminal, then Gy(i, y_i, x_i) for i = nt-1..1
+ *   Fy  Fy(i, y_i, x_i) for i = nt-1..1
+ *   Fu, Gu  (i, y_i, x_i) for i = 0..nt-1
+ *
+ * Rounding order (compiled with -ffp-contract=off and without fast-math, like the library; every sum left to right):
+ *   forward    y_r = y_r + tau*f_r;  fval = 0.5*G(0, ..), then fval = fval + G or fval + 0.5*G (last);  J = fval*tau
+ *   terminal   lam_r = (-0.5*tau)*gy_r
+ *   adjoint    a_c = fy[0][c]*lam[0] + fy[1][c]*lam[1] + ...;  lam_c = lam_c + tau*(a_c - gy_c), all a before any lam
+ *   gradient   df[m, i] = (0.0 - (fu[0][m]*lam[0] + fu[1][m]*lam[1] + ...)) + gu[m]
+ * For ny = 2, nx = 3 and Gu = 0 this is the order of the built-in examples, so hooks that restate an example term for
+ * term reproduce the example's J and df bit for bit.
+ *
+ * mioc_ode_program_create needs no context and no GPU: it compiles for gfx950 and keeps the code object.  Limits:
+ *   1 <= ny <= 8, 1 <= nx <= 8, 0 <= nparams <= 32, source text of at most 1 MiB (else MIOC_EINVAL).  A compile
+ *   failure returns MIOC_ECOMPILE; the compiler's log (also the warnings of a successful compile) is copied into
+ *   `log`, NUL-terminated and truncated to log_cap bytes (log nullable).  Diagnostics of the caller's text carry
+ *   the file name "hooks" and the text's own line numbers ("hooks:3:...").  MIOC_EHIP: hiprtc could not be loaded.
+ * mioc_ode_program_eval_device evaluates K controls like the built-in entry above: d_x K x nx x nt (the DP's
+ *   input layout), d_J (K, nullable), d_df (K x nx x nt, nullable), state0 (ny) and params (nparams) host arrays
+ *   passed to the kernel by value, tau = (T1 - T0)/nt; nx must equal the levels' number of controls once levels
+ *   are set.  The code object is loaded on the context's device at first use and kept per device in the program; a
+ *   program may serve several contexts and devices.  Enqueued on the context's stream; gated by mioc_trm_attach.
+ * mioc_ode_program_destroy synchronises every device the program ran on, then unloads it; destroy a program before
+ *   the contexts' devices are reset, and not while another thread evaluates it.
+ */
+typedef struct mioc_ode_program mioc_ode_program;
+int32_t mioc_ode_program_create(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, mioc_ode_program **out,
+                                char *log, int64_t log_cap);
+int32_t mioc_ode_program_destroy(mioc_ode_program *prog);
+int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t K, const double *d_x, int64_t nt,
+                                     double T0, double T1, const double *state0, const double *params, double *d_J,
+                                     double *d_df);
 
 /*
  * Random admissible starts, rand_func_int (HelpFunctions.jl:204-225) on the device: K piecewise-constant controls

@@ -232,4 +232,45 @@ function conv_eval_device!(ctx::Context, K::Integer, d_x::Ptr{Float64}, d_J::Ptr
     nothing
 end
 
+# ---- user-defined ODE objectives: the six hooks of an AbstractODEObjective (ODEObjective.jl:243-248) as HIP source
+# text, compiled at run time for gfx950 (mioc_ode_program_*; the hook contract is in include/mioc.h) ----------------
+
+"""
+    ode_program_create(hooks, ny, nx, nparams) -> Ptr{Cvoid}
+
+Compile the hook text (needs no context and no GPU).  A compile failure raises an error carrying the compiler's log,
+whose diagnostics name the text's own lines (`hooks:3:…`).
+"""
+function ode_program_create(hooks::String, ny::Integer, nx::Integer, nparams::Integer)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    log = zeros(UInt8, 1 << 16)
+    rc = ccall((:mioc_ode_program_create, libmioc), Int32,
+               (Cstring, Int32, Int32, Int32, Ptr{Ptr{Cvoid}}, Ptr{UInt8}, Int64), hooks, ny, nx, nparams, r, log,
+               length(log))
+    rc == MIOC_OK || error("mioc_ode_program_create failed with $rc:\n" * unsafe_string(pointer(log)))
+    r[]
+end
+
+"""
+    ode_program_destroy(prog)
+
+Unload and free a program (after the work that uses it: every device it ran on is synchronised first).
+"""
+ode_program_destroy(prog::Ptr{Cvoid}) = (ccall((:mioc_ode_program_destroy, libmioc), Int32, (Ptr{Cvoid},), prog); nothing)
+
+"""
+    ode_program_eval_device!(ctx, prog, K, d_x, nt, T0, T1, state0, params, d_J, d_df)
+
+The batched device entry (mioc_ode_program_eval_device): K controls already in device memory (K × nx × nt), enqueued
+on the context's stream; state0 (ny) and params (nparams) are host vectors; d_J / d_df may be C_NULL.
+"""
+function ode_program_eval_device!(ctx::Context, prog::Ptr{Cvoid}, K::Integer, d_x::Ptr{Float64}, nt::Integer,
+                                  T0::Float64, T1::Float64, state0::Vector{Float64}, params::Vector{Float64},
+                                  d_J::Ptr{Float64}, d_df::Ptr{Float64})
+    check(ctx, ccall((:mioc_ode_program_eval_device, libmioc), Int32,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Float64, Float64, Ptr{Float64}, Ptr{Float64},
+                      Ptr{Float64}, Ptr{Float64}), ctx.ptr, prog, K, d_x, nt, T0, T1, state0, params, d_J, d_df))
+    nothing
+end
+
 end # module

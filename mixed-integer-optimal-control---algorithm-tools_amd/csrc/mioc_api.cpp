@@ -747,6 +747,11 @@ int mioc::join_bt(mioc_ctx *ctx) {
   return MIOC_OK;
 }
 
+// the forward-state scratch shared by mioc_ode_eval_device and mioc_ode_program_eval_device (mioc_ode_rtc.cpp)
+int mioc::grow_ode_state(mioc_ctx *ctx, size_t need_bytes) {
+  return grow(ctx, &ctx->d_ode_state, &ctx->ode_cap, need_bytes, "ODE states");
+}
+
 // ==================================================================================================
 // C ABI
 // ==================================================================================================

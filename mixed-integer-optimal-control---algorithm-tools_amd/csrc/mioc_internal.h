@@ -277,6 +277,8 @@ int join_bt(mioc_ctx *ctx);
     if (rcj_) return rcj_;                        \
   } while (0)
 
+int grow_ode_state(mioc_ctx *ctx, size_t need_bytes);  // mioc_api.cpp: grows mioc_ctx::d_ode_state
+
 struct HeatState;  // mioc_heat.hip: the PDE heat objective's device matrices (mioc_heat_setup)
 void heat_free(HeatState *h);
 struct ConvState;  // mioc_conv.hip: the convolution objective's device tables (mioc_conv_setup)
@@ -321,7 +323,7 @@ struct mioc_ctx {
   double *d_pred_own = nullptr;    // mioc_pred staging: 4 doubles, then the TV error flag (int32)
   bool trm_pending = false;
   const int32_t *Bvec = nullptr;   // per-subproblem B' of the running backtrack (mioc_backtrack_batch_budgets_device)
-  double *d_ode_state = nullptr;   // [K][nt][2] forward states of mioc_ode_eval_device
+  double *d_ode_state = nullptr;   // forward states: [K][nt][2] of mioc_ode_eval_device, [nt][ny][K] of an ODE program
   size_t ode_cap = 0;
   mioc::HeatState *heat = nullptr; // mioc_heat_setup / mioc_heat_eval_device
   mioc::ConvState *conv = nullptr; // mioc_conv_setup / mioc_conv_eval_device

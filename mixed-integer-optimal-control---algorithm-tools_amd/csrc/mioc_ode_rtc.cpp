@@ -1,0 +1,330 @@
+// mioc_ode_rtc.cpp -- user-defined ODE objectives (the reference's extension point, AbstractODEObjective with the
+// hooks F!, Fy!, Fu!, G, Gy!, Gu!: julia_opt/ODEObjective.jl:243-248) compiled at run time for gfx950.
+//
+// mioc_ode_program_create wraps the caller's six hooks (HIP source text, the contract is in include/mioc.h) in the
+// kernel skeleton below and compiles the result with hiprtc; mioc_ode_program_eval_device loads the code object on
+// the context's device at first use and launches it.  hiprtc is loaded lazily (dlopen at the first create), so
+// libmioc.so carries no link-time dependency on it and loads as before where it is absent.
+//
+// The kernel: eval_f_helper / eval_df_helper of ODEObjective.jl:125-184, one lane per restart in 64-lane blocks like
+// k_ode_eval (mioc_ode.hip), NY / NX / NP compile-time so that y, λ, fy, fu, gy, gu live in registers.  The forward
+// states go to a scratch laid out [step][r][k]: the 64 lanes of a wave store and load 64 contiguous doubles
+// (k_ode_eval's [k][step][r] gives every lane a cache line of its own per step).  Rounding order (no contraction, no
+// fast-math): see the skeleton; for NY = 2, NX = 3, Gu = 0 it is k_ode_eval's, operation for operation.
+#include <dlfcn.h>
+#include <hip/hip_runtime.h>
+#include <hip/hiprtc.h>
+
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "mioc_internal.h"
+
+namespace {
+
+constexpr int kMaxNY = 8, kMaxNX = 8, kMaxNP = 32;
+constexpr size_t kMaxSource = 1u << 20;
+const char *const kKernelName = "mioc_ode_program_kernel";
+
+// The skeleton follows the user text.  NY, NX, NP are #defined in front of both.
+const char *const kSkeleton = R"SKEL(
+namespace mioc_skeleton {
+struct Par {
+  double y0[NY];
+  double p[NP > 0 ? NP : 1];
+};
+}  // namespace mioc_skeleton
+
+extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
+    int K, int nt, double T0, double tau, mioc_skeleton::Par P, const double *X, double *J, double *DF, double *ST,
+    const int *gate) {
+  if (gate && *gate == 0) return;  // device TRM control: no restart is inside its inner loop
+  const unsigned ku = blockIdx.x * 64u + threadIdx.x;
+  if (ku >= (unsigned)K) return;
+  const size_t k = ku, KK = (size_t)K;
+  const double *p = P.p;
+  const double *x = X + k * (size_t)nt * NX;
+  // ---- forward: explicit Euler, trapezoid cost (ODEObjective.jl:125-150) ----
+  double y[NY], f[NY], xc[NX], xn[NX];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) y[r] = P.y0[r];
+#pragma unroll
+  for (int m = 0; m < NX; ++m) xc[m] = x[m];
+  double fval = 0.5 * G(p, 0, T0 + 0.0 * tau, y, xc);
+  for (int i = 0; i < nt; ++i) {
+    F(p, i, T0 + (double)i * tau, y, xc, f);
+#pragma unroll
+    for (int r = 0; r < NY; ++r) y[r] = y[r] + tau * f[r];
+    if (DF) {
+#pragma unroll
+      for (int r = 0; r < NY; ++r) ST[((size_t)i * NY + r) * KK + k] = y[r];
+    }
+    if (i < nt - 1) {  // G at step i + 1 sees the control column of step i + 1
+#pragma unroll
+      for (int m = 0; m < NX; ++m) xn[m] = x[(size_t)(i + 1) * NX + m];
+      fval = fval + G(p, i + 1, T0 + (double)(i + 1) * tau, y, xn);
+#pragma unroll
+      for (int m = 0; m < NX; ++m) xc[m] = xn[m];
+    } else {
+      fval = fval + 0.5 * G(p, nt - 1, T0 + (double)(nt - 1) * tau, y, xc);
+    }
+  }
+  if (J) J[k] = fval * tau;
+  if (!DF) return;
+  // ---- backward: adjoint and df = Gu - Fu' lambda (ODEObjective.jl:153-184) ----
+  // here y is the state after the last step and xc the last control column
+  double *df = DF + k * (size_t)nt * NX;
+  double gy[NY], gu[NX], fy[NY][NY], fu[NY][NX], lam[NY], a[NY], s[NY];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) {  // zeroed once per evaluation (ODEObjective.jl:155-162)
+    gy[r] = 0.0;
+#pragma unroll
+    for (int c = 0; c < NY; ++c) fy[r][c] = 0.0;
+#pragma unroll
+    for (int m = 0; m < NX; ++m) fu[r][m] = 0.0;
+  }
+#pragma unroll
+  for (int m = 0; m < NX; ++m) gu[m] = 0.0;
+  Gy(p, nt, T0 + (double)nt * tau, y, xc, gy);
+#pragma unroll
+  for (int r = 0; r < NY; ++r) lam[r] = (-0.5 * tau) * gy[r];
+  for (int i = nt - 1; i >= 0; --i) {
+    // df[:, i] needs lambda_i and the state before step i (state0 for i = 0); xc is the control column of step i
+    const double t = T0 + (double)i * tau;
+    if (i == 0) {
+#pragma unroll
+      for (int r = 0; r < NY; ++r) s[r] = P.y0[r];
+    } else {
+#pragma unroll
+      for (int r = 0; r < NY; ++r) s[r] = ST[((size_t)(i - 1) * NY + r) * KK + k];
+    }
+    Fu(p, i, t, s, xc, fu);
+    Gu(p, i, t, s, xc, gu);
+#pragma unroll
+    for (int m = 0; m < NX; ++m) {
+      double acc = fu[0][m] * lam[0];
+#pragma unroll
+      for (int r = 1; r < NY; ++r) acc = acc + fu[r][m] * lam[r];
+      df[(size_t)i * NX + m] = (0.0 - acc) + gu[m];
+    }
+    if (i == 0) break;
+    // lambda_{i-1} = lambda_i + tau (Fy' lambda_i - Gy), Fy and Gy at (state_{i-1}, x_i)
+    Gy(p, i, t, s, xc, gy);
+    Fy(p, i, t, s, xc, fy);
+#pragma unroll
+    for (int c = 0; c < NY; ++c) {
+      double acc = fy[0][c] * lam[0];
+#pragma unroll
+      for (int r = 1; r < NY; ++r) acc = acc + fy[r][c] * lam[r];
+      a[c] = acc;
+    }
+#pragma unroll
+    for (int c = 0; c < NY; ++c) lam[c] = lam[c] + tau * (a[c] - gy[c]);
+#pragma unroll
+    for (int m = 0; m < NX; ++m) xc[m] = x[(size_t)(i - 1) * NX + m];
+  }
+}
+)SKEL";
+
+// ---- hiprtc, loaded at the first mioc_ode_program_create -------------------------------------------------------
+struct Rtc {
+  bool ok = false;
+  std::string why;
+  decltype(&hiprtcCreateProgram) create = nullptr;
+  decltype(&hiprtcCompileProgram) compile = nullptr;
+  decltype(&hiprtcGetProgramLogSize) log_size = nullptr;
+  decltype(&hiprtcGetProgramLog) log = nullptr;
+  decltype(&hiprtcGetCodeSize) code_size = nullptr;
+  decltype(&hiprtcGetCode) code = nullptr;
+  decltype(&hiprtcDestroyProgram) destroy = nullptr;
+};
+
+const Rtc &rtc() {
+  static const Rtc r = [] {
+    Rtc q;
+    void *h = nullptr;
+    for (const char *name : {"libhiprtc.so.7", "libhiprtc.so", "/opt/rocm/lib/libhiprtc.so"}) {
+      h = dlopen(name, RTLD_NOW | RTLD_LOCAL);
+      if (h) break;
+    }
+    if (!h) {
+      q.why = "libhiprtc.so not found (it is part of the ROCm install)";
+      return q;
+    }
+    q.create = reinterpret_cast<decltype(q.create)>(dlsym(h, "hiprtcCreateProgram"));
+    q.compile = reinterpret_cast<decltype(q.compile)>(dlsym(h, "hiprtcCompileProgram"));
+    q.log_size = reinterpret_cast<decltype(q.log_size)>(dlsym(h, "hiprtcGetProgramLogSize"));
+    q.log = reinterpret_cast<decltype(q.log)>(dlsym(h, "hiprtcGetProgramLog"));
+    q.code_size = reinterpret_cast<decltype(q.code_size)>(dlsym(h, "hiprtcGetCodeSize"));
+    q.code = reinterpret_cast<decltype(q.code)>(dlsym(h, "hiprtcGetCode"));
+    q.destroy = reinterpret_cast<decltype(q.destroy)>(dlsym(h, "hiprtcDestroyProgram"));
+    q.ok = q.create && q.compile && q.log_size && q.log && q.code_size && q.code && q.destroy;
+    if (!q.ok) q.why = "libhiprtc.so lacks a hiprtc entry point";
+    return q;
+  }();
+  return r;
+}
+
+void put_log(char *log, int64_t cap, const char *text, size_t n) {
+  if (!log || cap < 1) return;
+  const size_t m = n < (size_t)(cap - 1) ? n : (size_t)(cap - 1);
+  std::memcpy(log, text, m);
+  log[m] = '\0';
+}
+
+int fail(mioc_ctx *ctx, int code, const std::string &msg) {
+  ctx->err = msg;
+  return code;
+}
+
+}  // namespace
+
+struct mioc_ode_program {
+  int ny = 0, nx = 0, np = 0;
+  std::vector<char> code;  // the gfx950 code object
+  struct Loaded {
+    int device;
+    hipModule_t mod;
+    hipFunction_t fn;
+  };
+  std::mutex mu;
+  std::vector<Loaded> loaded;  // one module per device the program ran on
+};
+
+extern "C" {
+
+int32_t mioc_ode_program_create(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, mioc_ode_program **out,
+                                char *log, int64_t log_cap) {
+  put_log(log, log_cap, "", 0);
+  if (!out) return MIOC_EINVAL;
+  *out = nullptr;
+  if (!hooks || ny < 1 || ny > kMaxNY || nx < 1 || nx > kMaxNX || nparams < 0 || nparams > kMaxNP) return MIOC_EINVAL;
+  const size_t len = strnlen(hooks, kMaxSource + 1);
+  if (len > kMaxSource) return MIOC_EINVAL;
+  const Rtc &R = rtc();
+  if (!R.ok) {
+    put_log(log, log_cap, R.why.c_str(), R.why.size());
+    return MIOC_EHIP;
+  }
+  std::string src;
+  try {
+    char head[128];
+    std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n#line 1 \"hooks\"\n", (int)ny, (int)nx,
+                  (int)nparams);
+    src.reserve(len + std::strlen(kSkeleton) + 256);
+    src = head;
+    src.append(hooks, len);
+    src += "\n#line 1 \"mioc_ode_program_skeleton\"";
+    src += kSkeleton;
+  } catch (const std::bad_alloc &) {
+    return MIOC_ENOMEM;
+  }
+  hiprtcProgram prog = nullptr;
+  if (R.create(&prog, src.c_str(), "mioc_ode_program.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
+    const char msg[] = "hiprtcCreateProgram failed";
+    put_log(log, log_cap, msg, sizeof msg - 1);
+    return MIOC_ECOMPILE;
+  }
+  // the flags of csrc/Makefile that bear on the arithmetic: no FMA contraction, no fast-math
+  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math"};
+  const hiprtcResult rc = R.compile(prog, (int)(sizeof opts / sizeof opts[0]), opts);
+  int ret = MIOC_OK;
+  try {
+    size_t ln = 0;
+    if (log && log_cap > 0 && R.log_size(prog, &ln) == HIPRTC_SUCCESS && ln > 1) {
+      std::vector<char> buf(ln + 1, '\0');
+      if (R.log(prog, buf.data()) == HIPRTC_SUCCESS) put_log(log, log_cap, buf.data(), strnlen(buf.data(), ln));
+    }
+    if (rc != HIPRTC_SUCCESS) {
+      ret = MIOC_ECOMPILE;
+    } else {
+      size_t cn = 0;
+      mioc_ode_program *p = new mioc_ode_program;
+      p->ny = ny, p->nx = nx, p->np = nparams;
+      if (R.code_size(prog, &cn) != HIPRTC_SUCCESS || cn == 0) {
+        ret = MIOC_ECOMPILE;
+      } else {
+        p->code.resize(cn);
+        if (R.code(prog, p->code.data()) != HIPRTC_SUCCESS) ret = MIOC_ECOMPILE;
+      }
+      if (ret == MIOC_OK)
+        *out = p;
+      else
+        delete p;
+    }
+  } catch (const std::bad_alloc &) {
+    ret = MIOC_ENOMEM;
+  }
+  R.destroy(&prog);
+  return ret;
+}
+
+int32_t mioc_ode_program_destroy(mioc_ode_program *prog) {
+  if (!prog) return MIOC_EINVAL;
+  int rc = MIOC_OK;
+  if (!prog->loaded.empty()) {
+    int prev = 0;
+    const bool have_prev = hipGetDevice(&prev) == hipSuccess;
+    for (const auto &l : prog->loaded) {  // a launch may still be in flight on this device
+      if (hipSetDevice(l.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+          hipModuleUnload(l.mod) != hipSuccess)
+        rc = MIOC_EHIP;
+    }
+    if (have_prev) (void)hipSetDevice(prev);
+  }
+  delete prog;
+  return rc;
+}
+
+int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t K, const double *d_x, int64_t nt,
+                                     double T0, double T1, const double *state0, const double *params, double *d_J,
+                                     double *d_df) {
+  if (!ctx) return MIOC_EINVAL;
+  MIOC_JOIN_BT(ctx);
+  if (!prog) return fail(ctx, MIOC_EINVAL, "no ODE program");
+  if (K < 1 || nt < 1 || K > INT32_MAX || nt > INT32_MAX || !d_x) return fail(ctx, MIOC_EINVAL, "bad K / nt / x");
+  if (!state0 || (prog->np > 0 && !params)) return fail(ctx, MIOC_EINVAL, "state0 / params missing");
+  if (!(T1 > T0)) return fail(ctx, MIOC_EINVAL, "need T1 > T0");
+  if (ctx->have_levels && ctx->M != prog->nx)
+    return fail(ctx, MIOC_EINVAL, "the program's nx differs from the levels' number of controls");
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, MIOC_EHIP, "hipSetDevice failed");
+  hipFunction_t fn = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(prog->mu);
+    for (const auto &l : prog->loaded)
+      if (l.device == ctx->device) fn = l.fn;
+    if (!fn) {
+      mioc_ode_program::Loaded l{ctx->device, nullptr, nullptr};
+      hipError_t e = hipModuleLoadData(&l.mod, prog->code.data());
+      if (e == hipSuccess) {
+        e = hipModuleGetFunction(&l.fn, l.mod, kKernelName);
+        if (e != hipSuccess) (void)hipModuleUnload(l.mod);
+      }
+      if (e != hipSuccess) return fail(ctx, MIOC_EHIP, std::string("loading the ODE program: ") + hipGetErrorString(e));
+      prog->loaded.push_back(l);
+      fn = l.fn;
+    }
+  }
+  {  // forward states [nt][ny][K]
+    const int rc = mioc::grow_ode_state(ctx, (size_t)K * (size_t)nt * (size_t)prog->ny * sizeof(double));
+    if (rc) return rc;
+  }
+  int Ki = (int)K, nti = (int)nt;
+  double t0 = T0, tau = (T1 - T0) / (double)nt;  // ODEObjective.jl: tau = (T1 - T0) / nt
+  double par[kMaxNY + kMaxNP] = {};              // the skeleton's Par: y0[NY], then p[max(NP, 1)]
+  for (int r = 0; r < prog->ny; ++r) par[r] = state0[r];
+  for (int q = 0; q < prog->np; ++q) par[prog->ny + q] = params[q];
+  const double *X = d_x;
+  double *ST = ctx->d_ode_state;
+  const int32_t *gate = ctx->gate;
+  void *args[] = {&Ki, &nti, &t0, &tau, par, &X, &d_J, &d_df, &ST, &gate};
+  const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)((K + 63) / 64), 1, 1, 64, 1, 1, 0, ctx->stream, args, nullptr);
+  if (e != hipSuccess) return fail(ctx, MIOC_EHIP, std::string("launching the ODE program: ") + hipGetErrorString(e));
+  return MIOC_OK;
+}
+
+}  // extern "C"

@@ -7,6 +7,7 @@ Host-side mirror of the reference's interface for that path; the DP itself runs 
 from .conv import ConvObj, ConvProblem
 from .iterators import LevelTable, bounded_sum_iterator, check_sum, product_iterator
 from .native import Context, InexactError, MiocNativeError, load_library
+from .ode_device import DeviceODEProblem, MiocCompileError, ODEProgram
 from .objective import (AbstractObjective, AbstractObjectiveAAO, AbstractObjectiveLazy, eval_df_, eval_f,
                         eval_f_, eval_fdf_)
 from .trm import (TRM, SubproblemSolver, TRM_parameters, TV_p, bellman_TRM_, eval_u_TRM_, rand_func,
@@ -17,4 +18,5 @@ __all__ = [
     "InexactError", "load_library", "AbstractObjective", "AbstractObjectiveAAO", "AbstractObjectiveLazy", "eval_f",
     "eval_f_", "eval_df_", "eval_fdf_", "TRM", "TRM_parameters", "TV_p", "SubproblemSolver", "bellman_TRM_",
     "eval_u_TRM_", "rand_func", "rand_func_int", "ConvProblem", "ConvObj",
+    "ODEProgram", "DeviceODEProblem", "MiocCompileError",
 ]

@@ -27,6 +27,7 @@ MIOC_EHIP = -4
 MIOC_EINFEASIBLE = -5
 MIOC_ESTATE = -6
 MIOC_ENONFINITE = -7
+MIOC_ECOMPILE = -8
 
 MIOC_P_INF, MIOC_P_ONE, MIOC_P_INTLUT, MIOC_P_TABLE = 0, 1, 2, 3
 MIOC_OPT_ALGO, MIOC_OPT_TIMING, MIOC_OPT_PERSIST, MIOC_OPT_PRED_FMA = 1, 2, 3, 4
@@ -46,6 +47,7 @@ EXPORTED = [
     "mioc_conv_setup", "mioc_conv_eval_device", "mioc_conv_eval",
     "mioc_trm_state_bytes", "mioc_trm_attach", "mioc_trm_outer_begin_device", "mioc_trm_inner_end_device",
     "mioc_trm_poll",
+    "mioc_ode_program_create", "mioc_ode_program_destroy", "mioc_ode_program_eval_device",
 ]
 
 
@@ -121,6 +123,9 @@ def load_library(path=None):
         "mioc_trm_inner_end_device": (i32, [vp, i64, vp, dbl, i64, dbl, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp,
                                             vp, vp]),
         "mioc_trm_poll": (i32, [vp, vp, vp]),
+        "mioc_ode_program_create": (i32, [ctypes.c_char_p, i32, i32, i32, ctypes.POINTER(vp), ctypes.c_char_p, i64]),
+        "mioc_ode_program_destroy": (i32, [vp]),
+        "mioc_ode_program_eval_device": (i32, [vp, vp, i64, vp, i64, dbl, dbl, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -425,6 +430,31 @@ class Context:
         self._check(self.lib.mioc_ode_eval_device(
             self.h, int(problem), K, ctypes.c_void_p(x.data_ptr()), nx, nt, float(T0), float(T1),
             None if par is None else _p(par), 0 if par is None else par.size,
+            ctypes.c_void_p(J.data_ptr()) if J is not None else None,
+            ctypes.c_void_p(df.data_ptr()) if df is not None else None))
+
+    def ode_program_eval_tensors(self, prog, x, T0, T1, state0, params, J=None, df=None):
+        """eval_f! / eval_df! of a user-defined ODE objective (mioc.ode_device.ODEProgram) for K controls x
+        (K, nt, nx) float64 CUDA tensor: J (K,) and df (K, nt, nx) float64 CUDA tensors (each optional); state0 (ny)
+        and params (nparams) host values; enqueued (mioc_ode_program_eval_device)."""
+        if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
+            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
+        K, nt, nx = x.shape
+        if nx != prog.nx:
+            raise ValueError(f"x has {nx} controls, the program {prog.nx}")
+        for name, t, n in (("J", J, K), ("df", df, x.numel())):
+            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or
+                                  t.numel() != n):
+                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries")
+        y0 = np.ascontiguousarray(state0, dtype=np.float64).reshape(-1)
+        par = np.ascontiguousarray(() if params is None else params, dtype=np.float64).reshape(-1)
+        if y0.size != prog.ny or par.size != prog.nparams:
+            raise ValueError(f"the program takes {prog.ny} initial states and {prog.nparams} parameters")
+        if not prog.h:
+            raise ValueError("the ODE program is closed")
+        self._check(self.lib.mioc_ode_program_eval_device(
+            self.h, prog.h, K, ctypes.c_void_p(x.data_ptr()), nt, float(T0), float(T1), _p(y0),
+            _p(par) if par.size else None,
             ctypes.c_void_p(J.data_ptr()) if J is not None else None,
             ctypes.c_void_p(df.data_ptr()) if df is not None else None))
 

@@ -1,0 +1,222 @@
+"""User-defined ODE objectives on the device: the six hooks of an AbstractODEObjective as HIP source text.
+
+The reference's extension point is the objective (julia_opt/ODEObjective.jl:243-248: F!, Fy!, Fu!, G, Gy!, Gu!).
+``ODEProgram`` hands the hooks to ``libmioc.so`` as text; the library compiles them into its explicit-Euler / adjoint
+sweep for gfx950 at run time (mioc_ode_program_create) and ``Context.ode_program_eval_tensors`` runs that kernel.  The
+hook contract (signatures, the step index each hook sees, zeroing, rounding order) is in ``include/mioc.h``.
+
+``EXAMPLE_SOURCES`` restates the three built-in problems as hook text, term for term as ``Hooks<...>`` of
+csrc/mioc_ode.hip has them, so each reproduces mioc_ode_eval_device bit for bit; they double as templates.  Parameter
+order as in mioc_ode_eval_device without the trailing y0, which is ``state0`` here (``EXAMPLE_PARAMS``,
+``EXAMPLE_STATE0``: the examples' constants).
+"""
+from __future__ import annotations
+
+import atexit
+import ctypes
+import sys
+import weakref
+
+from .native import MIOC_ECOMPILE, MIOC_OK, MiocNativeError, load_library
+
+
+class MiocCompileError(MiocNativeError):
+    """The hook source did not compile; ``log`` is the compiler's output (the hooks' own line numbers: hooks:N)."""
+
+    def __init__(self, code, log):
+        super().__init__(code, "the ODE hooks did not compile:\n" + log)
+        self.log = log
+
+
+_LIVE = weakref.WeakSet()  # programs not yet closed
+
+
+@atexit.register
+def _close_live_programs():
+    """Destroy the programs still open while the HIP runtime is alive (see native._close_live_contexts; this handler
+    is registered later, so it runs first: a program is unloaded before the contexts that ran it are destroyed)."""
+    for p in list(_LIVE):
+        try:
+            p.close()
+        except Exception:
+            pass
+
+
+class ODEProgram:
+    """Six hooks (HIP source text) compiled for gfx950: ny states, nx controls, nparams parameters.  Needs no GPU to
+    compile; one program serves any number of contexts.  ``close()`` destroys it (also ``with ODEProgram(...) as p``)."""
+
+    LOG_CAP = 1 << 16
+
+    def __init__(self, source, ny, nx, nparams):
+        self.h = None
+        self.lib = load_library()
+        self.ny, self.nx, self.nparams = int(ny), int(nx), int(nparams)
+        h = ctypes.c_void_p()
+        log = ctypes.create_string_buffer(self.LOG_CAP)
+        text = source.encode() if isinstance(source, str) else source
+        rc = self.lib.mioc_ode_program_create(text, self.ny, self.nx, self.nparams, ctypes.byref(h), log, self.LOG_CAP)
+        self.log = log.value.decode(errors="replace")
+        if rc == MIOC_ECOMPILE:
+            raise MiocCompileError(rc, self.log)
+        if rc != MIOC_OK:
+            raise MiocNativeError(rc, self.log or "mioc_ode_program_create: bad ny / nx / nparams / source "
+                                                  "(1 <= ny, nx <= 8, 0 <= nparams <= 32, at most 1 MiB of text)")
+        self.h = h
+        _LIVE.add(self)
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            _LIVE.discard(self)
+            self.lib.mioc_ode_program_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self, _finalizing=sys.is_finalizing):
+        if _finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceODEProblem:
+    """An ODE-constrained problem for TRM_batch: a compiled ``ODEProgram`` with the data the Julia objective holds --
+    the levels V and their iterator (None: the product grid), [T0, T1], the default number of steps nt, state0 and
+    the parameters."""
+
+    def __init__(self, program, V, iterator, T0, T1, nt, state0, params=()):
+        self.program = program
+        self.V = [list(v) for v in V]
+        self.iterator = iterator
+        self.T0, self.T1, self.nt = float(T0), float(T1), int(nt)
+        self.state0 = [float(v) for v in state0]
+        self.params = [float(v) for v in params]
+        if len(self.V) != program.nx or len(self.state0) != program.ny or len(self.params) != program.nparams:
+            raise ValueError("V, state0 and params must match the program's nx, ny and nparams")
+        if not self.T1 > self.T0 or self.nt < 1:
+            raise ValueError("need T1 > T0 and nt >= 1")
+
+    def eval_tensors(self, ctx, x, J=None, df=None):
+        ctx.ode_program_eval_tensors(self.program, x, self.T0, self.T1, self.state0, self.params, J, df)
+
+
+_SIG = "(const double *p, int i, double t, const double *y, const double *x"
+
+EXAMPLE_SOURCES = {
+    # Lotka-Volterra fishing (example_fishing.jl:14-92): p = alpha, beta, gamma, delta, c1, c2, v1[3], v2[3]
+    "fishing": """
+__device__ double fish_s1(const double *p, const double *x) { return ((0.0 + x[0] * p[6]) + x[1] * p[7]) + x[2] * p[8]; }
+__device__ double fish_s2(const double *p, const double *x) { return ((0.0 + x[0] * p[9]) + x[1] * p[10]) + x[2] * p[11]; }
+__device__ void F@SIG@, double *f) {
+  f[0] = y[0] * ((p[0] - p[1] * y[1]) - p[4] * fish_s1(p, x));
+  f[1] = y[1] * ((-p[2] + p[3] * y[0]) - p[5] * fish_s2(p, x));
+}
+__device__ void Fy@SIG@, double (*fy)[NY]) {
+  fy[0][0] = (p[0] - p[1] * y[1]) - p[4] * fish_s1(p, x);
+  fy[0][1] = y[0] * -p[1];
+  fy[1][0] = y[1] * p[3];
+  fy[1][1] = (-p[2] + p[3] * y[0]) - p[5] * fish_s2(p, x);
+}
+__device__ void Fu@SIG@, double (*fu)[NX]) {
+  for (int m = 0; m < 3; ++m) {
+    fu[0][m] = (y[0] * -p[4]) * p[6 + m];
+    fu[1][m] = (y[1] * -p[5]) * p[9 + m];
+  }
+}
+__device__ double G@SIG@) {
+  const double a = y[0] - 1.0, b = y[1] - 1.0;
+  return 0.5 * (a * a) + 0.5 * (b * b);
+}
+__device__ void Gy@SIG@, double *gy) {
+  gy[0] = y[0] - 1.0;
+  gy[1] = y[1] - 1.0;
+}
+__device__ void Gu@SIG@, double *gu) {}
+""",
+    # double tank multimode (example_doubletank.jl:14-82): p = k1, k2, c[3]
+    "doubletank": """
+__device__ double tank_cx(const double *p, const double *x) { return ((0.0 + p[2] * x[0]) + p[3] * x[1]) + p[4] * x[2]; }
+__device__ void F@SIG@, double *f) {
+  f[0] = tank_cx(p, x) - sqrt(y[0]);
+  f[1] = sqrt(y[0]) - sqrt(y[1]);
+}
+__device__ void Fy@SIG@, double (*fy)[NY]) {
+  fy[0][0] = -1.0 / (2.0 * sqrt(y[0]));
+  fy[0][1] = 0.0;
+  fy[1][0] = 1.0 / (2.0 * sqrt(y[0]));
+  fy[1][1] = -1.0 / (2.0 * sqrt(y[1]));
+}
+__device__ void Fu@SIG@, double (*fu)[NX]) {
+  for (int m = 0; m < 3; ++m) {
+    fu[0][m] = p[2 + m];
+    fu[1][m] = 0.0;
+  }
+}
+__device__ double G@SIG@) {
+  const double d = y[1] - p[1];
+  return p[0] * (d * d);
+}
+__device__ void Gy@SIG@, double *gy) {
+  gy[0] = 0.0;
+  gy[1] = (2.0 * p[0]) * (y[1] - p[1]);
+}
+__device__ void Gu@SIG@, double *gu) {}
+""",
+    # Van der Pol oscillator, binary variant (example_vanderpol.jl:14-81): p = c[3]
+    "vanderpol": """
+__device__ double vdp_cx(const double *p, const double *x) { return ((0.0 + p[0] * x[0]) + p[1] * x[1]) + p[2] * x[2]; }
+__device__ void F@SIG@, double *f) {
+  f[0] = y[1];
+  f[1] = ((1.0 - y[0] * y[0]) * y[1]) * vdp_cx(p, x) - y[0];
+}
+__device__ void Fy@SIG@, double (*fy)[NY]) {
+  const double s = vdp_cx(p, x);
+  fy[0][0] = 0.0;
+  fy[0][1] = 1.0;
+  fy[1][0] = ((-2.0 * y[0]) * y[1]) * s - 1.0;
+  fy[1][1] = (1.0 - y[0] * y[0]) * s;
+}
+__device__ void Fu@SIG@, double (*fu)[NX]) {
+  for (int m = 0; m < 3; ++m) {
+    fu[0][m] = 0.0;
+    fu[1][m] = (p[m] * (1.0 - y[0] * y[0])) * y[1];
+  }
+}
+__device__ double G@SIG@) { return y[0] * y[0] + y[1] * y[1]; }
+__device__ void Gy@SIG@, double *gy) {
+  gy[0] = 2.0 * y[0];
+  gy[1] = 2.0 * y[1];
+}
+__device__ void Gu@SIG@, double *gu) {}
+""",
+}
+EXAMPLE_SOURCES = {k: v.replace("@SIG@", _SIG) for k, v in EXAMPLE_SOURCES.items()}
+
+# the examples' constants (example_fishing.jl, example_doubletank.jl, example_vanderpol.jl) and shapes
+EXAMPLE_PARAMS = {"fishing": [1, 1, 1, 1, 1, 1, 0.2, 0.4, 0.01, 0.1, 0.2, 0.1], "doubletank": [2, 3, 1, 0.5, 2],
+                  "vanderpol": [-1, 0.75, -2]}
+EXAMPLE_STATE0 = {"fishing": [0.5, 0.7], "doubletank": [2, 2], "vanderpol": [1, 0]}
+EXAMPLE_SHAPES = {k: (2, 3, len(v)) for k, v in EXAMPLE_PARAMS.items()}  # (ny, nx, nparams)
+
+
+def example_program(name):
+    """ODEProgram of a built-in example's hook text."""
+    return ODEProgram(EXAMPLE_SOURCES[name], *EXAMPLE_SHAPES[name])
+
+
+def example_problem(name, program=None):
+    """DeviceODEProblem of a built-in example (SOS1 over three binary controls, the example's horizon and nt)."""
+    from .iterators import bounded_sum_iterator
+    from .trm_batch import PROBLEMS
+    _, nt, T0, T1 = PROBLEMS[name]
+    V = [[0, 1], [0, 1], [0, 1]]
+    return DeviceODEProblem(program or example_program(name), V, bounded_sum_iterator(V, 1, 1), T0, T1, nt,
+                            EXAMPLE_STATE0[name], EXAMPLE_PARAMS[name])

@@ -9,7 +9,8 @@ The control flow is multi-trust.jl:53-170 per restart, run for K restarts in loc
   return            J + β·TV_p(u)                                            :169
 
 Device kernels do all O(nt) work: the random starts (mioc_rand_start_device, HelpFunctions.jl:204-225), the ODE
-objective and adjoint gradient (mioc_ode_eval_device, ODEObjective.jl:125-184) or the PDE heat objective's
+objective and adjoint gradient (mioc_ode_eval_device, ODEObjective.jl:125-184; for a user-defined ODE objective the
+kernel compiled from its hooks, mioc_ode_program_eval_device) or the PDE heat objective's
 (mioc_heat_eval_device, PDEObjective.jl:129-199) or the convolution objective's (mioc_conv_eval_device,
 example_convolution.jl:128-141), the DP and backtrack with one budget per restart after halving
 (mioc_backtrack_batch_budgets_device), pred and TV_p -- and the control itself: Δᵏ, k, the inner / halved / stopped
@@ -50,7 +51,8 @@ def TRM_batch(problem, par, K=None, x0=None, seed=0, nt=None, device=0, log=None
     problem: "fishing" / "doubletank" / "vanderpol", or a mioc.heat.HeatProblem (example_heat.jl: 6 x 6 product
     levels, gradient from mioc_heat_eval_device; its nt is the problem's), or a mioc.conv.ConvProblem / the string
     "convolution" = ConvProblem(nt = nt or 2048) (example_convolution.jl: one control, levels -2..2, gradient from
-    mioc_conv_eval_device).
+    mioc_conv_eval_device), or a mioc.ode_device.DeviceODEProblem (a user-defined ODE objective: levels from its V and
+    iterator, gradient from its compiled hooks, mioc_ode_program_eval_device).
     x0: a (K, nt, nx) float64 CUDA tensor of starts, or None for K device random starts (rand_func_int with `seed`).
     log: a list to receive (inner iteration, decisions (K,)) after every inner iteration (debugging: one stream
     synchronisation each).  inner_chunk: inner iterations enqueued between two read-backs of the control flags.
@@ -61,6 +63,7 @@ def TRM_batch(problem, par, K=None, x0=None, seed=0, nt=None, device=0, log=None
     import torch
 
     from .conv import ConvProblem
+    from .ode_device import DeviceODEProblem
     if isinstance(problem, str) and problem == "convolution":
         problem = ConvProblem(nt=nt or 2048)
     ctx = Context(device)
@@ -74,6 +77,13 @@ def TRM_batch(problem, par, K=None, x0=None, seed=0, nt=None, device=0, log=None
 
         def evalf(x, J, df):
             ctx.conv_eval_tensors(x, J, df)
+    elif isinstance(problem, DeviceODEProblem):  # a user-defined ODE objective (mioc_ode_program_eval_device)
+        dp = problem
+        nt_def, T0, T1 = dp.nt, dp.T0, dp.T1
+        lt = LevelTable(dp.V, dp.iterator)
+
+        def evalf(x, J, df):
+            dp.eval_tensors(ctx, x, J, df)
     elif isinstance(problem, str):
         prob, nt_def, T0, T1 = PROBLEMS[problem]
         lt = sos1_levels()
