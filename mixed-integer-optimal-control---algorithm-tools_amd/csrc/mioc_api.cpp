@@ -440,7 +440,10 @@ int run_bellman(mioc_ctx *ctx) {
         int ncu = 0;
         HIP_TRY(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
         S = 1;
-        while (S < 8 && (size_t)K * (size_t)(2 * S) <= (size_t)ncu && fsep2_plan(ctx->pyr, ctx->B, 2 * S, nullptr))
+        // (only segments of whole waves of rows: the even split with idle lane groups is for forced counts)
+        FsepPlan t;
+        while (S < 8 && (size_t)K * (size_t)(2 * S) <= (size_t)ncu && fsep2_plan(ctx->pyr, ctx->B, 2 * S, &t) &&
+               t.RS == t.W * (64 / t.lanes))
           S *= 2;
       }
       // a u_old off the level grid can send a target further than SMAX rows up, past a segment's outbox rows

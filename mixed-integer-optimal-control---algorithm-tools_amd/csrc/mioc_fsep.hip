@@ -129,7 +129,7 @@ struct FsepArgs {
   int32_t *counters;
   double *ring;    // [K][S][NB][SMAX][L]: segment q's outbox (rows hi_q .. hi_q + SMAX - 1), read by q + 1
   int32_t *flags;  // [K][S][2] {outbox token, consumed token}, then the error flag at [2·K·S]
-  int S, RS, NB;   // segments, rows per segment (a multiple of 32), ring depth
+  int S, RS, NB;   // segments, rows per segment (at most the workgroup's lane groups), ring depth
   int koff;        // K table offset in the LDS (doubles)
   int stg;         // S > 1: the inbox staging rows in the LDS (doubles)
   int slot_bytes;  // S > 1: bytes per ring slot (SMAX·L doubles, rounded up to 1 KiB: whole LDS-DMA chunks)
@@ -681,6 +681,9 @@ bool fsep2_plan(const PyrGeom &G, int B, int S, FsepPlan *out) {
     const int rpw = 64 / p.lanes;
     p.RS = rpw * std::max(1, (R - 1 + rpw * S - 1) / (rpw * S));
     p.W = p.RS / rpw;
+    // whole waves of rows per segment can leave the last segment empty (8x8 at B = 140, S = 4: 3·48 > 140): then the
+    // even split, whose last wave keeps idle lane groups (a row at or above the segment's end is inactive anyway)
+    if ((S - 1) * p.RS >= R) p.RS = std::max(1, (R - 1 + S - 1) / S);
     if ((S - 1) * p.RS >= R || p.RS < SMAX + 1) return false;  // an empty last segment / a halo past the next one
     p.rows = std::min(R, p.RS + 1 + SMAX);
   }

@@ -184,7 +184,7 @@ hipError_t launch_fsep_run(hipStream_t s, const ProblemDev &P, const LevelsDev &
 // ... round-3 layout (mioc_fsep.hip): two lanes per row, the front updated in place, optionally S row segments per
 // subproblem on S workgroups chained by an outbox ring (strong scaling)
 struct FsepPlan {
-  int S = 1, RS = 0, W = 0;  // segments, rows per segment (multiple of 32), waves per workgroup
+  int S = 1, RS = 0, W = 0;  // segments, rows per segment (at most W waves of rows), waves per workgroup
   int rows = 0, koff = 0;    // LDS front rows, K table offset (doubles)
   int stg = 0, slot_bytes = 0;  // S > 1: inbox staging offset (doubles), ring slot bytes
   int threads = 0;
