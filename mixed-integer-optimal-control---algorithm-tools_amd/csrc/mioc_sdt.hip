@@ -655,7 +655,9 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
 #pragma unroll
     for (int x = 0; x < 8; ++x) {
       const int r = tid | (x << (3 * (M - 1))), j = jx[x];
-      const bool fin = (valid >> x & 1) && o[x] < INFINITY;
+      // the winners run only in a row that is not `empty`: it has a finite source, which reaches every target at a
+      // finite distance, so every o[x] is finite here -- only the trust region decides
+      const bool fin = (valid >> x & 1) != 0;
       const bool flg = FLAG && (__double2loint(o[x]) & SD_CNT) != 0;
       // d(l, j*) exactly: an unflagged finite o[x] is V_j* + d with V_j* = the stamp of Ψ_j* (the same expression
       // as the stamping above, payload j*), every term exact in the binade (garbage, unused, otherwise)
@@ -812,6 +814,30 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
       }
     }
     list_targets(listed);
+    // the listed targets' exact scans (the caller's next barrier publishes their results)
+    auto scans = [&]() {
+      const int nl = sh.nlist[par];
+      if (nl) {  // uniform
+        if (nl <= SD_COOP)
+          sd_scan<M, true>(list, nl, psi, a, lb, beta, uu, outv, sh.redv, sh.redj);
+        else if (nl <= SD_LCAP)
+          sd_scan<M, false>(list, nl, psi, a, lb, beta, uu, outv, sh.redv, sh.redj);
+        else
+          sd_scan<M, false>(nullptr, L, psi, a, lb, beta, uu, outv, sh.redv, sh.redj);  // every NaN-marked rank
+        if (tid == 0) sh.cnt[direct ? 1 : 0] += nl;
+      }
+      return nl;
+    };
+    // (persistent driver) a direct row -- row B of every step, with its one target -- has no passes between go() and the
+    // drain: it would sit out the whole latency of the next row's loads in the drain and only then scan, which made
+    // row B the slowest item of the DP, the one every other row waits for.  Its scans need nothing the drain brings (Ψ
+    // by rank and the list are in the LDS), so they run first, under that latency; the drain's barrier then publishes
+    // their results together with the previous row's `done`.
+    const bool scan_first = PERSIST && direct;  // uniform
+    if (scan_first) {
+      sd_bar();  // the list is complete, every lane's placeholder outputs are written
+      scans();
+    }
     h.late_drain();  // this wave's stores of the previous row have landed (late: they have had the whole row)
     sd_bar();
     h.publish();     // ... so have every wave's: the previous row is done
@@ -822,17 +848,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
       sd_bar();
       if (tid == 0) ++sh.cnt[3];
     }
-    const int nl = sh.nlist[par];
-    if (nl) {
-      if (nl <= SD_COOP)
-        sd_scan<M, true>(list, nl, psi, a, lb, beta, uu, outv, sh.redv, sh.redj);
-      else if (nl <= SD_LCAP)
-        sd_scan<M, false>(list, nl, psi, a, lb, beta, uu, outv, sh.redv, sh.redj);
-      else
-        sd_scan<M, false>(nullptr, L, psi, a, lb, beta, uu, outv, sh.redv, sh.redj);  // every NaN-marked rank
-      sd_bar();
-      if (tid == 0) sh.cnt[direct ? 1 : 0] += nl;
-    }
+    if (!scan_first && scans()) sd_bar();
   }
   if (empty) {  // uniform: the row is +Inf, U unwritten -- through LDS, so that the stores below take one path
 #pragma unroll
@@ -1442,6 +1458,17 @@ __device__ __forceinline__ void sd_take(double (&v)[8], const SdRaw &w) {
 // Every wait points at an item of an earlier step, or of the same step and a lower row, so with every workgroup
 // resident nothing deadlocks; a wait beyond spin_limit polls sets *err and every workgroup leaves (the host then
 // redoes the DP with per-step launches: check_run).
+
+// A poll of a hand-off flag.  The flags live in global memory, but the driver keeps their addresses as generic pointers
+// (held in vector registers, SdPipe), through which the compiler emits flat_load: that counts in lgkmcnt as well as
+// vmcnt, so every LDS wait after a poll -- the first of them a dozen instructions after early() -- waited for the poll's
+// whole round trip.  As a global-address-space access it is the same relaxed agent-scope `sc1` load, counted in vmcnt
+// only: the statistics' reduction and scale() run while the polls are in flight.
+__device__ __forceinline__ int sd_flag_poll(const int32_t *p) {
+  return __hip_atomic_load((const __attribute__((address_space(1))) int32_t *)p, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // The pipeline hooks of the persistent driver (the row body calls them, see sdt_body).
 template <int M>
 struct SdPipe {
@@ -1511,7 +1538,7 @@ struct SdPipe {
         need = war;  // token(i + NB - 1)
       }
     }
-    val = __hip_atomic_load(fp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    val = sd_flag_poll(fp);
     // diagnostics [4]: this row reuses a staging buffer that a row above may still read (some WAR lane armed above)
     if (tid == 0 && war > 0 && min(cp + 7 * M, B) >= max(cp + 1, hi)) ++sh->cnt[2];
   }
@@ -1526,7 +1553,7 @@ struct SdPipe {
     if (tid == 0) __hip_atomic_store(lk + cp * SDT_FLAG_STRIDE, nt - 1 - i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     unsigned spins = 0;
     while (!ready) {
-      if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || ++spins > spin_limit) {
+      if (sd_flag_poll(err) || ++spins > spin_limit) {
         if ((tid & 63) == 0) {
           __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           sh->stop = 1;  // read by the driver after the row's next barrier: the launch is abandoned
@@ -1534,7 +1561,7 @@ struct SdPipe {
         break;
       }
       __builtin_amdgcn_s_sleep(1);
-      val = __hip_atomic_load(fp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      val = sd_flag_poll(fp);
       ready = __all(val >= need);
     }
     SD_TL_AT(g0, i, nt, 3);

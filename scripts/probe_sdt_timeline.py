@@ -77,6 +77,18 @@ print(f"stores issued -> next row start: median {np.median(rest):.3f} us")
 skew = T[1:, :, 0] - T[:-1, :, 0]  # row c starts step i this long after row c-1
 print(f"skew row c vs row c-1 (same step start): median {np.median(skew):.3f}  p10 {np.percentile(skew, 10):.3f}  "
       f"p90 {np.percentile(skew, 90):.3f} us; total over rows 1..{R - 1}: {np.median(T[-1, :, 0] - T[0, :, 0]):.1f} us")
+# by row class (M = 4: 7·M = 28): rows c' <= 28 hold geometric +Inf sources (source rows below 0), rows c' > B - 28
+# have targets outside the trust region (`valid` from u_old), the rows between take the common path throughout
+Sm = 28
+print(f"by row class (medians, us): rows 1-{Sm} | {Sm + 1}-{R - 1 - Sm} | {R - Sm}-{R - 1}")
+cls = [rows <= Sm, (rows > Sm) & (rows < R - Sm), rows >= R - Sm]
+cols = [(nm, q, q + 1) for q, nm in enumerate(names)] + [("  of it: waiting for the loads (0->7)", 0, 7)]
+for nm, a, b in cols:
+    d = T[:, :, b] - T[:, :, a]
+    print(f"{nm:38s} " + " | ".join(f"{np.median(d[c][ok[c]]):6.3f}" for c in cls))
+print(f"{'polls matched at go (share of items)':38s} " +
+      " | ".join(f"{np.mean((T[:, :, 3] - T[:, :, 2])[c][ok[c]] < 0.05):6.3f}" for c in cls))
+print(f"{'step period':38s} " + " | ".join(f"{np.median(per[c]):6.3f}" for c in cls))
 by_row = np.median(T[:, :, 3] - T[:, :, 2], axis=1)
 print("poll wait by row (median, every 16th row):", [round(float(x), 3) for x in by_row[::16]])
 ld = np.median(T[:, :, 7] - T[:, :, 0], axis=1)
