@@ -306,6 +306,38 @@ int32_t mioc_ode_eval_device(mioc_ctx *ctx, int32_t problem, int64_t K, const do
  * For ny = 2, nx = 3 and Gu = 0 this is the order of the built-in examples, so hooks that restate an example term for
  * term reproduce the example's J and df bit for bit.
  *
+ * Integrators.  All of the above is the reference's scheme, MIOC_ODE_INT_EULER, which mioc_ode_program_create
+ * compiles.  mioc_ode_program_create_ex also offers MIOC_ODE_INT_HEUN (c = (0, 1), a21 = 1, b = (1/2, 1/2)) and
+ * MIOC_ODE_INT_RK4 (c = (0, 1/2, 1/2, 1), a21 = a32 = 1/2, a43 = 1, b = (1/6, 1/3, 1/3, 1/6)), each with
+ * m = `substeps` steps of h = tau/m inside every control interval.  The reference has no such scheme; it is defined
+ * here.  Substep n = i*m + j (i = 0..nt-1 the control interval, j = 0..m-1) starts at t_n = T0 + n*h with the state
+ * y_n, y_0 = state0; the control x_i is held over the whole interval i.  With S stages:
+ *   forward    Y_1 = y_n,  Y_s = y_n + (h*a_{s,s-1})*k_{s-1};  k_s = F(i, t_n + c_s*h, Y_s, x_i),
+ *              g_s = G(i, t_n + c_s*h, Y_s, x_i);  y_{n+1} = y_n + sum_s (h*b_s)*k_s.  The running cost is a
+ *              quadrature state: q_0 = 0, q_{n+1} = q_n + sum_s (h*b_s)*g_s, and J = q_{nt*m} -- not the
+ *              reference's trapezoid: G sees the control of its own interval.
+ *   gradient   the exact derivative of that J by the scheme's discrete adjoint.  w = 0 after the last substep; per
+ *              substep n = nt*m-1..0, with the stage states Y_s recomputed from the stored y_n, for s = S..1:
+ *                kbar_s = (h*b_s)*w + (h*a_{s+1,s})*Ybar_{s+1}              (s = S: kbar_S = (h*b_S)*w)
+ *                Ybar_s = Fy(Y_s)' kbar_s + (h*b_s)*Gy(Y_s),   xbar_i += Fu(Y_s)' kbar_s + (h*b_s)*Gu(Y_s)
+ *              then w = w + sum_s Ybar_s.  df[m, i] = xbar_i[m] / tau: the function-space scaling of the reference's
+ *              df (the directional derivative of J along d is tau * sum df.*d), so df feeds the DP unchanged.
+ *   hooks      every hook sees i = the control interval, t = the stage time t_n + c_s*h, y = the stage state Y_s and
+ *              x = x_i.  F and G: every stage of every substep, forward; F again for the stages 1..S-1 in the
+ *              backward sweep; Fy, Gy, Fu, Gu (in this order): every stage, s = S..1, of every substep backwards.
+ *              fy, fu, gy, gu are zeroed once per evaluation, as above.
+ *   rounding   tau = (T1 - T0)/nt, h = tau/m, t_n = T0 + (double)n*h, stage time t_n + (c_s*h); the products c_s*h,
+ *              a_{s,s-1}*h, b_s*h are rounded once (b: the doubles 1.0/6.0, 1.0/3.0, 0.5); every sum left to right:
+ *                Y_s[r] = y[r] + (a_s h)*k_{s-1}[r];  y[r] = y[r] + (((b_1 h)*k_1[r] + (b_2 h)*k_2[r]) + ...)
+ *                q = q + (((b_1 h)*g_1 + (b_2 h)*g_2) + ...);  J = q
+ *                kbar_s[r] = (b_s h)*w[r] + (a_{s+1} h)*Ybar_{s+1}[r]
+ *                Ybar_s[c] = ((fy[0][c]*kbar_s[0] + fy[1][c]*kbar_s[1]) + ...) + (b_s h)*gy[c]
+ *                xbar[m] = xbar[m] + (((fu[0][m]*kbar_s[0] + fu[1][m]*kbar_s[1]) + ...) + (b_s h)*gu[m]), xbar = 0.0
+ *                at the start of an interval's backward sweep;  w[c] = w[c] + ((Ybar_S[c] + Ybar_{S-1}[c]) + ...)
+ *                df[m, i] = xbar[m] / tau
+ *   scratch    with d_df the state at every substep start is stored: K * nt * m * ny doubles of the context's ODE
+ *              scratch, grown on demand (MIOC_ENOMEM if that fails); a value-only call (d_df NULL) stores nothing.
+ *
  * mioc_ode_program_create needs no context and no GPU: it compiles for gfx950 and keeps the code object.  Limits:
  *   1 <= ny <= 8, 1 <= nx <= 8, 0 <= nparams <= 32, source text of at most 1 MiB (else MIOC_EINVAL).  A compile
  *   failure returns MIOC_ECOMPILE; the compiler's log (also the warnings of a successful compile) is copied into
@@ -322,6 +354,15 @@ int32_t mioc_ode_eval_device(mioc_ctx *ctx, int32_t problem, int64_t K, const do
 typedef struct mioc_ode_program mioc_ode_program;
 int32_t mioc_ode_program_create(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, mioc_ode_program **out,
                                 char *log, int64_t log_cap);
+/* The same with an integrator and its substeps per control interval (see "Integrators" above).  MIOC_EINVAL also for
+ * an unknown integrator, substeps outside 1..64, and MIOC_ODE_INT_EULER with substeps != 1 (the reference scheme
+ * defines no substeps).  mioc_ode_program_create(...) is _ex(..., MIOC_ODE_INT_EULER, 1, ...).  The program carries
+ * its integrator and substeps: mioc_ode_program_eval_device takes them from it. */
+#define MIOC_ODE_INT_EULER 0
+#define MIOC_ODE_INT_HEUN 1
+#define MIOC_ODE_INT_RK4 2
+int32_t mioc_ode_program_create_ex(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t integrator,
+                                   int32_t substeps, mioc_ode_program **out, char *log, int64_t log_cap);
 int32_t mioc_ode_program_destroy(mioc_ode_program *prog);
 int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t K, const double *d_x, int64_t nt,
                                      double T0, double T1, const double *state0, const double *params, double *d_J,

@@ -11,6 +11,10 @@
 // states go to a scratch laid out [step][r][k]: the 64 lanes of a wave store and load 64 contiguous doubles
 // (k_ode_eval's [k][step][r] gives every lane a cache line of its own per step).  Rounding order (no contraction, no
 // fast-math): see the skeleton; for NY = 2, NX = 3, Gu = 0 it is k_ode_eval's, operation for operation.
+//
+// mioc_ode_program_create_ex also takes an integrator: Heun or classical RK4 with substeps inside each control
+// interval, a quadrature cost and the scheme's discrete adjoint (kSkeletonRK; the scheme is defined in include/mioc.h).
+// The program carries integrator and substeps; the Euler skeleton and what it compiles to are untouched.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -26,7 +30,7 @@
 
 namespace {
 
-constexpr int kMaxNY = 8, kMaxNX = 8, kMaxNP = 32;
+constexpr int kMaxNY = 8, kMaxNX = 8, kMaxNP = 32, kMaxSubsteps = 64;
 constexpr size_t kMaxSource = 1u << 20;
 const char *const kKernelName = "mioc_ode_program_kernel";
 
@@ -130,6 +134,142 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
 }
 )SKEL";
 
+// The Heun / classical RK4 skeleton (mioc_ode_program_create_ex; the scheme and its rounding order are written out in
+// include/mioc.h).  NS, the stage count, is #defined in front with NY / NX / NP; the tableau follows from it.  Every
+// stage loop is fully unrolled, so ch / ha / hb and the stage arrays are indexed by constants and stay in registers.
+// ST holds y_n for every substep n = 0 .. nt*ms - 1, [n][r][k].
+const char *const kSkeletonRK = R"SKEL(
+namespace mioc_skeleton {
+struct Par {
+  double y0[NY];
+  double p[NP > 0 ? NP : 1];
+};
+}  // namespace mioc_skeleton
+
+extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
+    int K, int nt, int ms, double T0, double tau, double h, mioc_skeleton::Par P, const double *X, double *J,
+    double *DF, double *ST, const int *gate) {
+  if (gate && *gate == 0) return;  // device TRM control: no restart is inside its inner loop
+  const unsigned ku = blockIdx.x * 64u + threadIdx.x;
+  if (ku >= (unsigned)K) return;
+  const size_t k = ku, KK = (size_t)K;
+  const double *p = P.p;
+  const double *x = X + k * (size_t)nt * NX;
+  // stage time offsets c_s h, stage weights h a_{s,s-1} (ha[0] unused) and h b_s
+  double ch[NS], ha[NS], hb[NS];
+#if NS == 2  // Heun: c = (0, 1), a21 = 1, b = (1/2, 1/2)
+  ch[0] = 0.0 * h, ch[1] = 1.0 * h;
+  ha[0] = 0.0 * h, ha[1] = 1.0 * h;
+  hb[0] = 0.5 * h, hb[1] = 0.5 * h;
+#else  // classical RK4: c = (0, 1/2, 1/2, 1), a21 = a32 = 1/2, a43 = 1, b = (1/6, 1/3, 1/3, 1/6)
+  ch[0] = 0.0 * h, ch[1] = 0.5 * h, ch[2] = 0.5 * h, ch[3] = 1.0 * h;
+  ha[0] = 0.0 * h, ha[1] = 0.5 * h, ha[2] = 0.5 * h, ha[3] = 1.0 * h;
+  hb[0] = (1.0 / 6.0) * h, hb[1] = (1.0 / 3.0) * h, hb[2] = (1.0 / 3.0) * h, hb[3] = (1.0 / 6.0) * h;
+#endif
+  // ---- forward: y_{n+1} = y_n + sum_s hb_s k_s, the running cost as the quadrature state q ----
+  double y[NY], Y[NY], kk[NS][NY], g[NS], xc[NX];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) y[r] = P.y0[r];
+  double q = 0.0;
+  for (int i = 0; i < nt; ++i) {
+#pragma unroll
+    for (int m = 0; m < NX; ++m) xc[m] = x[(size_t)i * NX + m];
+    for (int j = 0; j < ms; ++j) {
+      const long long n = (long long)i * ms + j;
+      const double tn = T0 + (double)n * h;
+      if (DF) {
+#pragma unroll
+        for (int r = 0; r < NY; ++r) ST[((size_t)n * NY + r) * KK + k] = y[r];
+      }
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+#pragma unroll
+        for (int r = 0; r < NY; ++r) Y[r] = s == 0 ? y[r] : y[r] + ha[s] * kk[s > 0 ? s - 1 : 0][r];
+        F(p, i, tn + ch[s], Y, xc, kk[s]);
+        g[s] = G(p, i, tn + ch[s], Y, xc);
+      }
+#pragma unroll
+      for (int r = 0; r < NY; ++r) {
+        double inc = hb[0] * kk[0][r];
+#pragma unroll
+        for (int s = 1; s < NS; ++s) inc = inc + hb[s] * kk[s][r];
+        y[r] = y[r] + inc;
+      }
+      double inc = hb[0] * g[0];
+#pragma unroll
+      for (int s = 1; s < NS; ++s) inc = inc + hb[s] * g[s];
+      q = q + inc;
+    }
+  }
+  if (J) J[k] = q;
+  if (!DF) return;
+  // ---- backward: the scheme's discrete adjoint; df[:, i] = xbar_i / tau ----
+  double *df = DF + k * (size_t)nt * NX;
+  double gy[NY], gu[NX], fy[NY][NY], fu[NY][NX], w[NY], YS[NS][NY], kb[NY], Yb[NY], acc[NY], xbar[NX];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) {  // zeroed once per evaluation, as in the Euler skeleton
+    gy[r] = 0.0;
+    w[r] = 0.0;
+    Yb[r] = 0.0;
+#pragma unroll
+    for (int c = 0; c < NY; ++c) fy[r][c] = 0.0;
+#pragma unroll
+    for (int m = 0; m < NX; ++m) fu[r][m] = 0.0;
+  }
+#pragma unroll
+  for (int m = 0; m < NX; ++m) gu[m] = 0.0;
+  for (int i = nt - 1; i >= 0; --i) {
+#pragma unroll
+    for (int m = 0; m < NX; ++m) {
+      xc[m] = x[(size_t)i * NX + m];
+      xbar[m] = 0.0;
+    }
+    for (int j = ms - 1; j >= 0; --j) {
+      const long long n = (long long)i * ms + j;
+      const double tn = T0 + (double)n * h;
+#pragma unroll
+      for (int r = 0; r < NY; ++r) YS[0][r] = ST[((size_t)n * NY + r) * KK + k];
+#pragma unroll
+      for (int s = 1; s < NS; ++s) {  // the stage states again, from the stored y_n
+        F(p, i, tn + ch[s - 1], YS[s - 1], xc, kk[s - 1]);
+#pragma unroll
+        for (int r = 0; r < NY; ++r) YS[s][r] = YS[0][r] + ha[s] * kk[s - 1][r];
+      }
+#pragma unroll
+      for (int s = NS - 1; s >= 0; --s) {
+#pragma unroll
+        for (int r = 0; r < NY; ++r)
+          kb[r] = s == NS - 1 ? hb[s] * w[r] : hb[s] * w[r] + ha[s < NS - 1 ? s + 1 : s] * Yb[r];
+        Fy(p, i, tn + ch[s], YS[s], xc, fy);
+        Gy(p, i, tn + ch[s], YS[s], xc, gy);
+        Fu(p, i, tn + ch[s], YS[s], xc, fu);
+        Gu(p, i, tn + ch[s], YS[s], xc, gu);
+#pragma unroll
+        for (int c = 0; c < NY; ++c) {
+          double t = fy[0][c] * kb[0];
+#pragma unroll
+          for (int r = 1; r < NY; ++r) t = t + fy[r][c] * kb[r];
+          Yb[c] = t + hb[s] * gy[c];
+        }
+#pragma unroll
+        for (int m = 0; m < NX; ++m) {
+          double t = fu[0][m] * kb[0];
+#pragma unroll
+          for (int r = 1; r < NY; ++r) t = t + fu[r][m] * kb[r];
+          xbar[m] = xbar[m] + (t + hb[s] * gu[m]);
+        }
+#pragma unroll
+        for (int c = 0; c < NY; ++c) acc[c] = s == NS - 1 ? Yb[c] : acc[c] + Yb[c];
+      }
+#pragma unroll
+      for (int c = 0; c < NY; ++c) w[c] = w[c] + acc[c];
+    }
+#pragma unroll
+    for (int m = 0; m < NX; ++m) df[(size_t)i * NX + m] = xbar[m] / tau;
+  }
+}
+)SKEL";
+
 // ---- hiprtc, loaded at the first mioc_ode_program_create -------------------------------------------------------
 struct Rtc {
   bool ok = false;
@@ -185,6 +325,7 @@ int fail(mioc_ctx *ctx, int code, const std::string &msg) {
 
 struct mioc_ode_program {
   int ny = 0, nx = 0, np = 0;
+  int integrator = MIOC_ODE_INT_EULER, substeps = 1;
   std::vector<char> code;  // the gfx950 code object
   struct Loaded {
     int device;
@@ -199,10 +340,20 @@ extern "C" {
 
 int32_t mioc_ode_program_create(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, mioc_ode_program **out,
                                 char *log, int64_t log_cap) {
+  return mioc_ode_program_create_ex(hooks, ny, nx, nparams, MIOC_ODE_INT_EULER, 1, out, log, log_cap);
+}
+
+int32_t mioc_ode_program_create_ex(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t integrator,
+                                   int32_t substeps, mioc_ode_program **out, char *log, int64_t log_cap) {
   put_log(log, log_cap, "", 0);
   if (!out) return MIOC_EINVAL;
   *out = nullptr;
   if (!hooks || ny < 1 || ny > kMaxNY || nx < 1 || nx > kMaxNX || nparams < 0 || nparams > kMaxNP) return MIOC_EINVAL;
+  if (integrator != MIOC_ODE_INT_EULER && integrator != MIOC_ODE_INT_HEUN && integrator != MIOC_ODE_INT_RK4)
+    return MIOC_EINVAL;
+  if (substeps < 1 || substeps > kMaxSubsteps || (integrator == MIOC_ODE_INT_EULER && substeps != 1)) return MIOC_EINVAL;
+  // the reference scheme keeps its own skeleton and its head, so its source text is what it was
+  const char *const skeleton = integrator == MIOC_ODE_INT_EULER ? kSkeleton : kSkeletonRK;
   const size_t len = strnlen(hooks, kMaxSource + 1);
   if (len > kMaxSource) return MIOC_EINVAL;
   const Rtc &R = rtc();
@@ -213,13 +364,17 @@ int32_t mioc_ode_program_create(const char *hooks, int32_t ny, int32_t nx, int32
   std::string src;
   try {
     char head[128];
-    std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n#line 1 \"hooks\"\n", (int)ny, (int)nx,
-                  (int)nparams);
-    src.reserve(len + std::strlen(kSkeleton) + 256);
+    if (integrator == MIOC_ODE_INT_EULER)
+      std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n#line 1 \"hooks\"\n", (int)ny,
+                    (int)nx, (int)nparams);
+    else  // NS: the stage count, which selects the tableau
+      std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n#define NS %d\n#line 1 \"hooks\"\n",
+                    (int)ny, (int)nx, (int)nparams, integrator == MIOC_ODE_INT_HEUN ? 2 : 4);
+    src.reserve(len + std::strlen(skeleton) + 256);
     src = head;
     src.append(hooks, len);
     src += "\n#line 1 \"mioc_ode_program_skeleton\"";
-    src += kSkeleton;
+    src += skeleton;
   } catch (const std::bad_alloc &) {
     return MIOC_ENOMEM;
   }
@@ -245,6 +400,7 @@ int32_t mioc_ode_program_create(const char *hooks, int32_t ny, int32_t nx, int32
       size_t cn = 0;
       mioc_ode_program *p = new mioc_ode_program;
       p->ny = ny, p->nx = nx, p->np = nparams;
+      p->integrator = integrator, p->substeps = substeps;
       if (R.code_size(prog, &cn) != HIPRTC_SUCCESS || cn == 0) {
         ret = MIOC_ECOMPILE;
       } else {
@@ -309,19 +465,29 @@ int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int6
       fn = l.fn;
     }
   }
-  {  // forward states [nt][ny][K]
+  const bool euler = prog->integrator == MIOC_ODE_INT_EULER;
+  if (euler) {  // forward states [nt][ny][K]
     const int rc = mioc::grow_ode_state(ctx, (size_t)K * (size_t)nt * (size_t)prog->ny * sizeof(double));
     if (rc) return rc;
+  } else if (d_df) {  // the state at every substep start [nt * substeps][ny][K]; a value-only call stores nothing
+    // K * nt < 2^62 and per <= 64 * 8 * 8: the product is taken only once it is known to stay below 2^46
+    const uint64_t cells = (uint64_t)K * (uint64_t)nt, per = (uint64_t)(prog->substeps * prog->ny) * sizeof(double);
+    if (cells > ((uint64_t)1 << 46) / per) return fail(ctx, MIOC_ENOMEM, "the ODE states of all substeps exceed 64 TiB");
+    const int rc = mioc::grow_ode_state(ctx, (size_t)(cells * per));
+    if (rc) return rc;
   }
-  int Ki = (int)K, nti = (int)nt;
+  int Ki = (int)K, nti = (int)nt, ms = prog->substeps;
   double t0 = T0, tau = (T1 - T0) / (double)nt;  // ODEObjective.jl: tau = (T1 - T0) / nt
+  double h = tau / (double)ms;                   // the substep of the Heun / RK4 schemes
   double par[kMaxNY + kMaxNP] = {};              // the skeleton's Par: y0[NY], then p[max(NP, 1)]
   for (int r = 0; r < prog->ny; ++r) par[r] = state0[r];
   for (int q = 0; q < prog->np; ++q) par[prog->ny + q] = params[q];
   const double *X = d_x;
   double *ST = ctx->d_ode_state;
   const int32_t *gate = ctx->gate;
-  void *args[] = {&Ki, &nti, &t0, &tau, par, &X, &d_J, &d_df, &ST, &gate};
+  void *args_euler[] = {&Ki, &nti, &t0, &tau, par, &X, &d_J, &d_df, &ST, &gate};
+  void *args_rk[] = {&Ki, &nti, &ms, &t0, &tau, &h, par, &X, &d_J, &d_df, &ST, &gate};
+  void **args = euler ? args_euler : args_rk;
   const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)((K + 63) / 64), 1, 1, 64, 1, 1, 0, ctx->stream, args, nullptr);
   if (e != hipSuccess) return fail(ctx, MIOC_EHIP, std::string("launching the ODE program: ") + hipGetErrorString(e));
   return MIOC_OK;

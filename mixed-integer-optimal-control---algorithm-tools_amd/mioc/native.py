@@ -35,6 +35,7 @@ MIOC_OPT_SPIN_LIMIT, MIOC_OPT_SDT_BUFFERS, MIOC_OPT_FSEP_SEGMENTS, MIOC_OPT_PINF
 MIOC_ALGO_AUTO, MIOC_ALGO_GENERIC, MIOC_ALGO_PINF, MIOC_ALGO_PYRAMID, MIOC_ALGO_SEPARABLE = 0, 1, 2, 3, 4
 MIOC_ALGO_FUSED, MIOC_ALGO_FUSED_SEPARABLE = 5, 6
 MIOC_ODE_FISHING, MIOC_ODE_DOUBLETANK, MIOC_ODE_VANDERPOL = 1, 2, 3
+MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_RK4 = 0, 1, 2
 
 EXPORTED = [
     "mioc_version", "mioc_create", "mioc_destroy", "mioc_last_error", "mioc_set_option", "mioc_set_levels",
@@ -48,6 +49,7 @@ EXPORTED = [
     "mioc_trm_state_bytes", "mioc_trm_attach", "mioc_trm_outer_begin_device", "mioc_trm_inner_end_device",
     "mioc_trm_poll",
     "mioc_ode_program_create", "mioc_ode_program_destroy", "mioc_ode_program_eval_device",
+    "mioc_ode_program_create_ex",
 ]
 
 
@@ -124,6 +126,8 @@ def load_library(path=None):
                                             vp, vp]),
         "mioc_trm_poll": (i32, [vp, vp, vp]),
         "mioc_ode_program_create": (i32, [ctypes.c_char_p, i32, i32, i32, ctypes.POINTER(vp), ctypes.c_char_p, i64]),
+        "mioc_ode_program_create_ex": (i32, [ctypes.c_char_p, i32, i32, i32, i32, i32, ctypes.POINTER(vp),
+                                             ctypes.c_char_p, i64]),
         "mioc_ode_program_destroy": (i32, [vp]),
         "mioc_ode_program_eval_device": (i32, [vp, vp, i64, vp, i64, dbl, dbl, vp, vp, vp, vp]),
     }

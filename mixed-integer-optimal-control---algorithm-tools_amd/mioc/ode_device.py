@@ -4,6 +4,9 @@ The reference's extension point is the objective (julia_opt/ODEObjective.jl:243-
 ``ODEProgram`` hands the hooks to ``libmioc.so`` as text; the library compiles them into its explicit-Euler / adjoint
 sweep for gfx950 at run time (mioc_ode_program_create) and ``Context.ode_program_eval_tensors`` runs that kernel.  The
 hook contract (signatures, the step index each hook sees, zeroing, rounding order) is in ``include/mioc.h``.
+``ODEProgram(..., integrator="heun" | "rk4", substeps=m)`` compiles the hooks into a Heun / classical RK4 sweep with m
+substeps per control interval instead (mioc_ode_program_create_ex): the states are integrated as accurately as needed
+while nt, and with it the DP, follows how finely the control should switch.
 
 ``EXAMPLE_SOURCES`` restates the three built-in problems as hook text, term for term as ``Hooks<...>`` of
 csrc/mioc_ode.hip has them, so each reproduces mioc_ode_eval_device bit for bit; they double as templates.  Parameter
@@ -17,7 +20,8 @@ import ctypes
 import sys
 import weakref
 
-from .native import MIOC_ECOMPILE, MIOC_OK, MiocNativeError, load_library
+from .native import (MIOC_ECOMPILE, MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_RK4, MIOC_OK, MiocNativeError,
+                     load_library)
 
 
 class MiocCompileError(MiocNativeError):
@@ -42,20 +46,40 @@ def _close_live_programs():
             pass
 
 
+INTEGRATORS = {"euler": MIOC_ODE_INT_EULER, "heun": MIOC_ODE_INT_HEUN, "rk4": MIOC_ODE_INT_RK4}
+MAX_SUBSTEPS = 64
+
+
 class ODEProgram:
     """Six hooks (HIP source text) compiled for gfx950: ny states, nx controls, nparams parameters.  Needs no GPU to
-    compile; one program serves any number of contexts.  ``close()`` destroys it (also ``with ODEProgram(...) as p``)."""
+    compile; one program serves any number of contexts.  ``close()`` destroys it (also ``with ODEProgram(...) as p``).
+
+    ``integrator``: "euler" (the reference's explicit Euler / trapezoid scheme, the default), "heun" or "rk4", the
+    latter two with ``substeps`` steps inside every control interval and the exact gradient of their discrete J
+    (include/mioc.h, "Integrators"); the program carries both, every evaluation uses them."""
 
     LOG_CAP = 1 << 16
 
-    def __init__(self, source, ny, nx, nparams):
+    def __init__(self, source, ny, nx, nparams, integrator="euler", substeps=1):
         self.h = None
+        if integrator not in INTEGRATORS:
+            raise ValueError(f"integrator must be one of {sorted(INTEGRATORS)}, not {integrator!r}")
+        if int(substeps) != substeps or not 1 <= substeps <= MAX_SUBSTEPS:
+            raise ValueError(f"substeps must be an integer in 1..{MAX_SUBSTEPS}, not {substeps!r}")
+        if integrator == "euler" and substeps != 1:
+            raise ValueError("the reference's Euler scheme defines no substeps: use heun or rk4")
+        self.integrator, self.substeps = integrator, int(substeps)
         self.lib = load_library()
         self.ny, self.nx, self.nparams = int(ny), int(nx), int(nparams)
         h = ctypes.c_void_p()
         log = ctypes.create_string_buffer(self.LOG_CAP)
         text = source.encode() if isinstance(source, str) else source
-        rc = self.lib.mioc_ode_program_create(text, self.ny, self.nx, self.nparams, ctypes.byref(h), log, self.LOG_CAP)
+        if integrator == "euler":
+            rc = self.lib.mioc_ode_program_create(text, self.ny, self.nx, self.nparams, ctypes.byref(h), log,
+                                                  self.LOG_CAP)
+        else:
+            rc = self.lib.mioc_ode_program_create_ex(text, self.ny, self.nx, self.nparams, INTEGRATORS[integrator],
+                                                     self.substeps, ctypes.byref(h), log, self.LOG_CAP)
         self.log = log.value.decode(errors="replace")
         if rc == MIOC_ECOMPILE:
             raise MiocCompileError(rc, self.log)
@@ -207,16 +231,18 @@ EXAMPLE_STATE0 = {"fishing": [0.5, 0.7], "doubletank": [2, 2], "vanderpol": [1, 
 EXAMPLE_SHAPES = {k: (2, 3, len(v)) for k, v in EXAMPLE_PARAMS.items()}  # (ny, nx, nparams)
 
 
-def example_program(name):
+def example_program(name, integrator="euler", substeps=1):
     """ODEProgram of a built-in example's hook text."""
-    return ODEProgram(EXAMPLE_SOURCES[name], *EXAMPLE_SHAPES[name])
+    return ODEProgram(EXAMPLE_SOURCES[name], *EXAMPLE_SHAPES[name], integrator=integrator, substeps=substeps)
 
 
-def example_problem(name, program=None):
-    """DeviceODEProblem of a built-in example (SOS1 over three binary controls, the example's horizon and nt)."""
+def example_problem(name, program=None, nt=None, integrator="euler", substeps=1):
+    """DeviceODEProblem of a built-in example (SOS1 over three binary controls, the example's horizon; nt: the
+    example's unless given -- with heun / rk4 and substeps the control grid can be much coarser than the example's).
+    Without ``program``, one is compiled with ``integrator`` and ``substeps``."""
     from .iterators import bounded_sum_iterator
     from .trm_batch import PROBLEMS
-    _, nt, T0, T1 = PROBLEMS[name]
+    _, nt_def, T0, T1 = PROBLEMS[name]
     V = [[0, 1], [0, 1], [0, 1]]
-    return DeviceODEProblem(program or example_program(name), V, bounded_sum_iterator(V, 1, 1), T0, T1, nt,
-                            EXAMPLE_STATE0[name], EXAMPLE_PARAMS[name])
+    return DeviceODEProblem(program or example_program(name, integrator, substeps), V, bounded_sum_iterator(V, 1, 1),
+                            T0, T1, nt_def if nt is None else nt, EXAMPLE_STATE0[name], EXAMPLE_PARAMS[name])
