@@ -166,14 +166,20 @@ __device__ __forceinline__ void sd_scan(const uint16_t *list, int nl, const doub
     }
     return t1;
   };
+  // the whole-workgroup scans reduce through DPP (sd_wave_argmin: no LDS round trips); the one-wave-per-target scans
+  // of long lists keep the ds_bpermute butterfly, as they were
   auto wave_min = [&](double &bv, int &bj) {
+    if constexpr (COOP) {
+      sd_wave_argmin(bv, bj);
+    } else {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const double ov = __shfl_xor(bv, off);
-      const int oj = __shfl_xor(bj, off);
-      if (oj >= 0 && (bj < 0 || ov < bv || (ov == bv && oj < bj))) {
-        bv = ov;
-        bj = oj;
+      for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(bv, off);
+        const int oj = __shfl_xor(bj, off);
+        if (oj >= 0 && (bj < 0 || ov < bv || (ov == bv && oj < bj))) {
+          bv = ov;
+          bj = oj;
+        }
       }
     }
   };
@@ -688,6 +694,12 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
   };
   int nf, nv;
   bool empty;
+  // (persistent driver) the row has exactly one target inside the trust region, the level at position 0 of the sphere
+  // order of step i (e0h: its entry) -- row B of every step: the one-target item below
+  // (held in a vector register and read back as a scalar at each use: the row loop has no scalar register to spare)
+  int onev = 0;
+  auto is_one = [&]() { return PERSIST && __builtin_amdgcn_readfirstlane(onev) != 0; };  // uniform
+  [[maybe_unused]] uint32_t e0h = 0;
   {
     double pmn, pmx;
     sd_bar();  // every wave's row statistics (sdt_stats) are in sh, its Ψ in the LDS: the loads of S_{i+1} are consumed
@@ -707,10 +719,11 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
       // (persistent driver) the row's targets inside the trust region, as far as the row body asks (none, at most
       // SD_FEW, more): the sphere order of step i ascends in b̃, so at most q levels have b̃ <= B - c' iff entry q has
       // b̃ > B - c' -- two broadcast reads in the same batch instead of eight ballots per wave (sdt_stats)
-      [[maybe_unused]] uint32_t e0 = 0, ef = 0;
+      [[maybe_unused]] uint32_t e0 = 0, e1 = 0, ef = 0;
       if constexpr (PERSIST) {
         static_assert(SD_FEW < L, "entry SD_FEW of the sphere order");
         e0 = pout[0];
+        e1 = pout[1];  // exactly one target iff entry 0 is inside and entry 1 is not
         ef = pout[SD_FEW];
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -726,12 +739,24 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
       pmx = mx[0];
       nf = cn[0] >> 16;
       nv = cn[0] & 0xFFFF;
-      if constexpr (PERSIST) nv = (int)(e0 >> 16) > P.B - cp ? 0 : (int)(ef >> 16) > P.B - cp ? SD_FEW : SD_FEW + 1;
+      if constexpr (PERSIST) {
+        nv = (int)(e0 >> 16) > P.B - cp ? 0 : (int)(ef >> 16) > P.B - cp ? SD_FEW : SD_FEW + 1;
+        // (a row with at most SD_SPARSE finite sources stays with the sparse path, as before)
+        onev = nv != 0 && (int)(e1 >> 16) > P.B - cp && pmn < INFINITY && nf > SD_SPARSE;
+        asm volatile("" : "+v"(onev));
+        e0h = e0;
+      }
     }
     SD_STAMP(1);
     // no target in the trust region, or nothing reachable: the row is +Inf and U unwritten (0xFFFF)
     empty = __builtin_amdgcn_readfirstlane((int)(nv == 0 || !(pmn < INFINITY))) != 0;  // uniform
-    scale(pmn, pmx);
+    // a one-target row is direct whatever the range of its sources: it uses nothing of the binade
+    if (is_one()) {
+      ref = base = g = tol = 0.0;
+      scale_ok = true;
+    } else {
+      scale(pmn, pmx);
+    }
   }
   // few finite sources (rows near c' = 0): every target's minimum over them, directly
   const bool sparse = !empty && nf <= SD_SPARSE;
@@ -777,7 +802,36 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
     // ---- targets: R(l, j*) for a certified winner (no merge of the row's transform came within tol: every winner beats
     // every other source by more than tol); a row that met a near tie anywhere is redone below, counting them
     unsigned listed = 0;
-    if (!direct && !sparse) {
+    if (is_one()) {
+      // ---- the one-target item: the reference loop for target l0 over every source, Ψ by rank from the LDS (thread t:
+      // sources t + T·s, ascending, so a strict `<` keeps the lower rank; a +Inf source never wins), the wave's
+      // (value, rank) minimum through DPP, one partial per wave.  No outputs through the LDS, no list, no barrier of
+      // its own: the drain's barrier below publishes the partials, and the lanes fold them in registers past it.
+      const int l0 = (int)(e0h & 0xFFFFu);
+      double t1 = 0.0;
+#pragma unroll
+      for (int m = 0; m < M; ++m) t1 = t1 + a[m] * (double)(lb[m] + ((l0 >> (3 * m)) & 7));  // as sd_scan's target()
+      const int xt = (l0 >> (3 * (M - 1))) & 7;
+      const unsigned dpre = sd_l1(sd_bytes(tid), sd_bytes(l0 & ((1 << (3 * (M - 1))) - 1)));
+      double ps[8];
+#pragma unroll
+      for (int s = 0; s < 8; ++s) ps[s] = psi[tid + T * s];
+      double bv = INFINITY;
+      int bj = -1;
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const double val = (t1 + beta * (double)(dpre + (unsigned)abs(s - xt))) + ps[s];
+        if (val < bv) {
+          bv = val;
+          bj = tid + T * s;
+        }
+      }
+      sd_wave_argmin(bv, bj);
+      if (lane == 0) {
+        sh.redv[tid >> 6] = bv;
+        sh.redj[tid >> 6] = bj;
+      }
+    } else if (!direct && !sparse) {
       winners(std::false_type{});
       if (__any(dmin <= tol) && lane == 0) sh.redo[par] = 1;
     } else {
@@ -828,12 +882,12 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
       }
       return nl;
     };
-    // (persistent driver) a direct row -- row B of every step, with its one target -- has no passes between go() and the
-    // drain: it would sit out the whole latency of the next row's loads in the drain and only then scan, which made
-    // row B the slowest item of the DP, the one every other row waits for.  Its scans need nothing the drain brings (Ψ
-    // by rank and the list are in the LDS), so they run first, under that latency; the drain's barrier then publishes
-    // their results together with the previous row's `done`.
-    const bool scan_first = PERSIST && direct;  // uniform
+    // (persistent driver) a direct row has no passes between go() and the drain: it would sit out the whole latency of
+    // the next row's loads in the drain and only then scan.  Its scans need nothing the drain brings (Ψ by rank and the
+    // list are in the LDS), so they run first, under that latency; the drain's barrier then publishes their results
+    // together with the previous row's `done`.  (Row B of every step, with its one target, has scanned above without a
+    // list: the one-target item.  This is for direct rows with two to SD_FEW targets, or whose scale does not fit.)
+    const bool scan_first = PERSIST && direct && !is_one();  // uniform (the one-target item has scanned already)
     if (scan_first) {
       sd_bar();  // the list is complete, every lane's placeholder outputs are written
       scans();
@@ -848,7 +902,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
       sd_bar();
       if (tid == 0) ++sh.cnt[3];
     }
-    if (!scan_first && scans()) sd_bar();
+    if (!scan_first && !is_one() && scans()) sd_bar();
   }
   if (empty) {  // uniform: the row is +Inf, U unwritten -- through LDS, so that the stores below take one path
 #pragma unroll
@@ -861,16 +915,51 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
   SD_STAMP(8);
   // ---- Φ_i row c' in the sphere order of u_old(i), and the U row, both 16 bytes per lane: gathered from the LDS
   // before the tail, so that the two dependent LDS round trips (order entries, then values) run under its VALU work
-  uint2 eo[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) eo[q] = *reinterpret_cast<const uint2 *>(pout + sd_p2<M>(tid, q));
   double go[8];
+  ulonglong2 ut;
+  if (is_one()) {
+    // the one-target item's outputs, formed in registers: the waves' partials in one batch of broadcast reads (the
+    // barrier above published them), folded with ties to the lower rank; the row is +Inf and its U cells 0xFFFF but
+    // for the target's: position 0 of the output order (thread 0) and rank l0 of the U row (thread l0 / 8)
+    double pv[NW];
+    int pj[NW];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    go[2 * q] = outv[eo[q].x & 0xFFFFu];
-    go[2 * q + 1] = outv[eo[q].y & 0xFFFFu];
+    for (int q = 0; q < NW; ++q) {
+      pv[q] = sh.redv[q];
+      pj[q] = sh.redj[q];
+    }
+    double bv = pv[0];
+    int bj = pj[0];
+#pragma unroll
+    for (int q = 1; q < NW; ++q)
+      if (pv[q] < bv || (pv[q] == bv && (unsigned)pj[q] < (unsigned)bj)) {
+        bv = pv[q];
+        bj = pj[q];
+      }
+    const int l0 = (int)(e0h & 0xFFFFu);
+    const bool fin = bj >= 0;  // a finite minimum: the reference writes U[l0] (else the cell stays unwritten, Φ = +Inf)
+#pragma unroll
+    for (int x = 0; x < 8; ++x) go[x] = INFINITY;
+    if (tid == 0) {
+      if (fin) go[0] = bv;
+      outv[l0] = go[0];  // a one-row workgroup's next item takes its distance-0 source from here (SdPipe::tail)
+      sh.cnt[1] += 1;
+    }
+    const bool mine = fin && tid == (l0 >> 3);
+    const int sft = 16 * (l0 & 3);
+    const unsigned long long cell = ~(0xFFFFull << sft) | ((unsigned long long)bj << sft);
+    ut = make_ulonglong2(mine && !(l0 & 4) ? cell : ~0ull, mine && (l0 & 4) ? cell : ~0ull);
+  } else {
+    uint2 eo[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) eo[q] = *reinterpret_cast<const uint2 *>(pout + sd_p2<M>(tid, q));
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      go[2 * q] = outv[eo[q].x & 0xFFFFu];
+      go[2 * q + 1] = outv[eo[q].y & 0xFFFFu];
+    }
+    ut = reinterpret_cast<const ulonglong2 *>(uu)[tid];
   }
-  const ulonglong2 ut = reinterpret_cast<const ulonglong2 *>(uu)[tid];
   // the persistent driver's next row: its statistics phase (LDS writes and VALU only), with this row's outputs final
   h.tail(empty, outv);
 #pragma unroll
@@ -1674,6 +1763,9 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P_ar
   h.sslot = reinterpret_cast<uint16_t *>(sds + sd_strad_offset<M>());
   // only ever added to per-lane offsets (the LDS-DMA sources; the flags a lane polls or stores)
   asm volatile("" : "+v"(h.pk), "+v"(h.sk), "+v"(h.dk), "+v"(h.lk));
+  // likewise two values that only ever meet per-lane operands (the row-0 array's offset in the load addressing, the
+  // write-after-read token in the poll predicates)
+  asm volatile("" : "+v"(h.r0b), "+v"(h.war));
   h.reg = reg;
   h.pcp = -1, h.pi = 0;
   if (tid == 0) {
@@ -1711,6 +1803,7 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P_ar
   int bi = (nt - 2) % NB, bi1 = (nt - 1) % NB;
   // the U rows of step i (stepped down with i: R·L < 2^28 elements, the host bounds a staging buffer below 2^31 bytes)
   uint16_t *uu_i = UU_all + (size_t)k * uu_stride_k + (size_t)(nt - 2) * ((size_t)R * L);
+  asm volatile("" : "+v"(uu_i));  // (only ever added to a lane's offset: a vector register pair, as h.pk above)
 #pragma nounroll
   for (int i = nt - 2; i >= 0 && !stop; --i) {
 #pragma nounroll

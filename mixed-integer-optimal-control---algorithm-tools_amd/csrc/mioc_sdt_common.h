@@ -114,6 +114,40 @@ __device__ __forceinline__ void sd_wave_stats(double &mn, double &mx) {
   sd_minmax_s(mn, mx, n3, x3);
 }
 
+// The wave's (value, rank) minimum, ties to the lower rank, wave-uniform in every lane.  bj < 0: the lane has no
+// candidate (its bv is +Inf and never the only holder of a finite minimum); compared as unsigned, such a lane loses to
+// every rank, and a wave without a candidate returns bj = -1.  Every lane active.
+// The value by DPP as in sd_wave_stats (min and max in one statement per step: no wait state after the v_min_f64; the
+// max is not used), then the smallest rank among the lanes that hold the minimum, by the same steps on integers.  The
+// 16-lane rows are folded with row_bcast:15 (rows 1 and 3 take lane 15 of the row below) and row_bcast:31 (rows 2 and 3
+// take lane 31), which leaves the wave's result in lane 63: three scalar registers in all, where reading the four row
+// results as scalars takes twelve -- the persistent driver's row loop has none to spare.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ int sd_dpp_rows_i(int x) {  // lanes of the rows outside ROWS keep x
+  return __builtin_amdgcn_update_dpp(x, x, CTRL, ROWS, 0xF, false);
+}
+template <int CTRL, int ROWS>
+__device__ __forceinline__ double sd_dpp_rows_d(double x) {
+  return __hiloint2double(sd_dpp_rows_i<CTRL, ROWS>(__double2hiint(x)), sd_dpp_rows_i<CTRL, ROWS>(__double2loint(x)));
+}
+__device__ __forceinline__ void sd_wave_argmin(double &bv, int &bj) {
+  double mn = bv, mx = bv;
+#define SD_STEP(C) sd_minmax(mn, mx, sd_dpp_d<C>(mn), sd_dpp_d<C>(mx));
+  SD_STEP(0xB1) SD_STEP(0x4E) SD_STEP(0x141) SD_STEP(0x140)
+#undef SD_STEP
+  sd_minmax(mn, mx, sd_dpp_rows_d<0x142, 0xA>(mn), sd_dpp_rows_d<0x142, 0xA>(mx));
+  sd_minmax(mn, mx, sd_dpp_rows_d<0x143, 0xC>(mn), sd_dpp_rows_d<0x143, 0xC>(mx));
+  const double wm = sd_rdl(mn, 63);
+  unsigned c = bv == wm ? (unsigned)bj : ~0u;
+#define SD_STEP(C) c = min(c, (unsigned)sd_dpp_i<C>((int)c));
+  SD_STEP(0xB1) SD_STEP(0x4E) SD_STEP(0x141) SD_STEP(0x140)
+#undef SD_STEP
+  c = min(c, (unsigned)sd_dpp_rows_i<0x142, 0xA>((int)c));
+  c = min(c, (unsigned)sd_dpp_rows_i<0x143, 0xC>((int)c));
+  bv = wm;
+  bj = __builtin_amdgcn_readlane((int)c, 63);
+}
+
 // LDS position of rank r (3 bits per dimension): XOR swizzle so that each 32-lane half of a pass reads
 // 32 distinct 8-byte bank slots in every pass: slot = (x0 ^ x1) + 8·((x1 ^ x2) & 3)
 __device__ __forceinline__ int sd_swz(int r) { return r ^ ((r >> 3) & 7) ^ (((r >> 6) & 3) << 3); }
