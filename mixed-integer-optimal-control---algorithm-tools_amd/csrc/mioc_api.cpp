@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "mioc_internal.h"
+#include "mioc_sdt_plan.h"
 
 using namespace mioc;
 
@@ -34,44 +35,22 @@ int hip_fail(mioc_ctx *ctx, hipError_t e, const char *where) {
     if (_e != hipSuccess) return hip_fail((ctx), _e, #expr);    \
   } while (0)
 
-template <typename T>
-int grow(mioc_ctx *ctx, T **p, size_t *cap_bytes, size_t need_bytes, const char *what) {
-  if (*p && *cap_bytes >= need_bytes) return MIOC_OK;
-  if (*p) {
-    (void)hipDeviceSynchronize();  // the old buffer may still be read by a backtrack in flight on the other stream
-    hipFree(*p);
-    *p = nullptr;
-    *cap_bytes = 0;
-  }
-  if (need_bytes == 0) need_bytes = 16;
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(p), need_bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    char buf[160];
-    std::snprintf(buf, sizeof buf, "cannot allocate %.3f GB for %s", need_bytes / 1e9, what);
-    return fail(ctx, MIOC_ENOMEM, buf);
-  }
-  *cap_bytes = need_bytes;
-  return MIOC_OK;
-}
-
 LevelsDev levels_dev(const mioc_ctx *ctx) {
   LevelsDev Lv;
   Lv.M = (int)ctx->M;
   Lv.L = (int)ctx->L;
-  Lv.nuval = ctx->d_nuval;
-  Lv.nuint = ctx->d_nuint;
-  Lv.gidx = ctx->d_gidx;
-  Lv.vals = ctx->d_vals;
-  Lv.voff = ctx->d_voff;
-  Lv.g2r = ctx->d_g2r;
+  Lv.nuval = ctx->d_nuval.get();
+  Lv.nuint = ctx->d_nuint.get();
+  Lv.gidx = ctx->d_gidx.get();
+  Lv.vals = ctx->d_vals.get();
+  Lv.voff = ctx->d_voff.get();
+  Lv.g2r = ctx->d_g2r.get();
   Lv.p_kind = ctx->p_kind;
   Lv.p_int = (int)ctx->p_int;
   Lv.beta = ctx->beta;
   Lv.inv_beta = ctx->beta > 0.0 ? 1.0 / ctx->beta : 0.0;
-  Lv.costlut = ctx->d_costlut;
-  Lv.costtab = ctx->d_costtab;
+  Lv.costlut = ctx->d_costlut.get();
+  Lv.costtab = ctx->d_costtab.get();
   return Lv;
 }
 
@@ -83,75 +62,31 @@ ProblemDev problem_dev(const mioc_ctx *ctx) {
   P.B = ctx->B;
   P.RP = ctx->RP;
   P.dt = ctx->dt;
-  P.df = ctx->d_df;
-  P.uold = ctx->d_uold;
+  P.df = ctx->cur().df.get();
+  P.uold = ctx->cur().uold.get();
   P.Bvec = ctx->Bvec;
   P.gate = ctx->gate;
   return P;
 }
 
-void ev_collect(mioc_ctx *ctx);
+// the current slot's p = Inf tables, the context's segmented-walk tables and the last DP's class and walk geometry
+PinfDev pinf_dev(const mioc_ctx *ctx) {
+  const mioc_ctx::Slot &q = ctx->cur();
+  PinfDev D;
+  D.BW = ctx->pinf_BW, D.BWP = ctx->pinf_BWP, D.CH = ctx->pinf_CH, D.W = ctx->pinf_W;
+  D.kmin = q.kmin.get(), D.k2 = q.k2.get(), D.kfirst = q.kfirst.get(), D.R = q.R.get(), D.kabs = q.kabs.get();
+  D.ftab = ctx->d_ftab.get(), D.fseg = ctx->d_fseg.get(), D.fneed = ctx->d_fneed.get();
+  return D;
+}
 
-// the context's current inputs and p = Inf tables <-> its DP slots
-void slot_save(mioc_ctx *ctx) {
-  mioc_ctx::Slot &q = ctx->slots[ctx->slot];
-  q.df = ctx->d_df, q.uold = ctx->d_uold, q.in_cap = ctx->in_cap;
-  q.kmin = ctx->pinf.kmin, q.k2 = ctx->pinf.k2, q.kfirst = ctx->pinf.kfirst, q.R = ctx->pinf.R, q.kabs = ctx->pinf.kabs;
-  q.cap_k = ctx->pinf_cap_k, q.cap_R = ctx->pinf_cap_R, q.cap_kabs = ctx->pinf_cap_kabs;
-}
-void slot_load(mioc_ctx *ctx) {
-  const mioc_ctx::Slot &q = ctx->slots[ctx->slot];
-  ctx->d_df = q.df, ctx->d_uold = q.uold, ctx->in_cap = q.in_cap;
-  ctx->pinf.kmin = q.kmin, ctx->pinf.k2 = q.k2, ctx->pinf.kfirst = q.kfirst, ctx->pinf.R = q.R, ctx->pinf.kabs = q.kabs;
-  ctx->pinf_cap_k = q.cap_k, ctx->pinf_cap_R = q.cap_R, ctx->pinf_cap_kabs = q.cap_kabs;
-}
 // a new DP: the other slot, once the backtracks that read it are done (on the device: the stream waits).
 // Called only with arguments that check_problem accepted, and the wait (the one step that can fail) comes before the
-// swap: a call that returns an error from here or earlier leaves the context's slot, inputs and tables as they were.
+// flip: a call that returns an error from here or earlier leaves the context's slot, inputs and tables as they were.
 int begin_dp(mioc_ctx *ctx) {
   const int other = ctx->slot ^ 1;
   if (ctx->bt_rec[other]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_bt[other], 0));
-  slot_save(ctx);
   ctx->slot = other;
-  slot_load(ctx);
   return MIOC_OK;
-}
-
-void free_all(mioc_ctx *ctx) {
-  if (ctx->d_runflags) hipFree(ctx->d_runflags);
-  if (ctx->d_chain) hipFree(ctx->d_chain);
-  if (ctx->d_ring) hipFree(ctx->d_ring);
-  if (ctx->d_segflags) hipFree(ctx->d_segflags);
-  if (ctx->h_run_err) hipHostFree(ctx->h_run_err);
-  if (ctx->h_trm_poll) hipHostFree(ctx->h_trm_poll);
-  if (ctx->bstream) hipStreamSynchronize(ctx->bstream);
-  if (ctx->stream) hipStreamSynchronize(ctx->stream);
-  slot_save(ctx);  // the current inputs and p = Inf tables are one of the slots
-  for (auto &q : ctx->slots) {
-    void *sp[] = {q.df, q.uold, q.kmin, q.k2, q.kfirst, q.R, q.kabs};
-    for (void *p : sp)
-      if (p) hipFree(p);
-  }
-  void *ptrs[] = {ctx->d_nuval, ctx->d_nuint,  ctx->d_gidx,      ctx->d_numin,       ctx->d_numax,
-                  ctx->d_costlut, ctx->d_costtab, ctx->d_front,
-                  ctx->d_U,     ctx->pinf.ftab, ctx->pinf.fseg, ctx->pinf.fneed,
-                  ctx->d_start, ctx->d_ranks,   ctx->d_flags,      ctx->d_uout_own,    ctx->d_phistar_own,
-                  ctx->d_status_own, ctx->d_stage,    ctx->d_counters, ctx->d_perm, ctx->d_same2, ctx->d_strad,
-                  ctx->d_vals,  ctx->d_voff,    ctx->d_g2r,   ctx->d_tvw,        ctx->d_pred_own, ctx->d_ode_state};
-  for (void *p : ptrs)
-    if (p) hipFree(p);
-  if (ctx->h_flags) hipHostFree(ctx->h_flags);
-  heat_free(ctx->heat);
-  ctx->heat = nullptr;
-  conv_free(ctx->conv);
-  ctx->conv = nullptr;
-  ev_collect(ctx);
-  for (auto &pr : ctx->ev_pool) hipEventDestroy(pr.begin), hipEventDestroy(pr.end);
-  if (ctx->ev_dp) hipEventDestroy(ctx->ev_dp);
-  for (hipEvent_t e : ctx->ev_bt)
-    if (e) hipEventDestroy(e);
-  if (ctx->bstream) hipStreamDestroy(ctx->bstream);
-  if (ctx->stream) hipStreamDestroy(ctx->stream);
 }
 
 // (re)build the device cost tables for the current levels + cost
@@ -190,28 +125,23 @@ int build_cost_tables(mioc_ctx *ctx) {
       return fail(ctx, MIOC_EINVAL, "MIOC_P_TABLE needs table_len == L*L for the current levels");
     std::vector<double> tab(L * L);
     for (int64_t q = 0; q < L * L; ++q) tab[q] = ctx->beta * ctx->table[q];
-    size_t cap = 0;
-    if (ctx->d_costtab) hipFree(ctx->d_costtab), ctx->d_costtab = nullptr;
-    int rc = grow(ctx, &ctx->d_costtab, &cap, tab.size() * sizeof(double), "pair cost table");
+    int rc = ctx->d_costtab.grow(ctx, tab.size() * sizeof(double), "pair cost table");
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(ctx->d_costtab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_costtab.get(), tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     lut.assign(1, 0.0);
   }
   // TV_p's summand uses the unscaled weights (HelpFunctions.jl:262): keep the host table on the device as is
-  if (ctx->d_tvw) hipFree(ctx->d_tvw), ctx->d_tvw = nullptr;
+  ctx->d_tvw.reset();  // (no table: a null pointer and tvw_len == 0)
   ctx->tvw_len = 0;
   if ((ctx->p_kind == MIOC_P_INTLUT || ctx->p_kind == MIOC_P_TABLE) && !ctx->table.empty()) {
-    size_t wcap = 0;
-    int rc = grow(ctx, &ctx->d_tvw, &wcap, ctx->table.size() * sizeof(double), "TV weight table");
+    int rc = ctx->d_tvw.grow(ctx, ctx->table.size() * sizeof(double), "TV weight table");
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(ctx->d_tvw, ctx->table.data(), ctx->table.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_tvw.get(), ctx->table.data(), ctx->table.size() * sizeof(double), hipMemcpyHostToDevice));
     ctx->tvw_len = (int64_t)ctx->table.size();
   }
-  size_t cap = 0;
-  if (ctx->d_costlut) hipFree(ctx->d_costlut), ctx->d_costlut = nullptr;
-  int rc = grow(ctx, &ctx->d_costlut, &cap, lut.size() * sizeof(double), "cost lut");
+  int rc = ctx->d_costlut.grow(ctx, lut.size() * sizeof(double), "cost lut");
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy(ctx->d_costlut, lut.data(), lut.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->d_costlut.get(), lut.data(), lut.size() * sizeof(double), hipMemcpyHostToDevice));
   ctx->costlut_len = (int64_t)lut.size();
   return MIOC_OK;
 }
@@ -256,40 +186,63 @@ void ev_end(mioc_ctx *ctx, int which, int64_t launches, hipStream_t st = nullptr
   ctx->ev_pending[which].push_back(pr);
 }
 
+// before the context is deleted (its buffers free themselves): drain and destroy the streams and events
+void free_all(mioc_ctx *ctx) {
+  if (ctx->bstream) hipStreamSynchronize(ctx->bstream);
+  if (ctx->stream) hipStreamSynchronize(ctx->stream);
+  heat_free(ctx->heat);
+  ctx->heat = nullptr;
+  conv_free(ctx->conv);
+  ctx->conv = nullptr;
+  ev_collect(ctx);
+  for (auto &pr : ctx->ev_pool) hipEventDestroy(pr.begin), hipEventDestroy(pr.end);
+  if (ctx->ev_dp) hipEventDestroy(ctx->ev_dp);
+  for (hipEvent_t e : ctx->ev_bt)
+    if (e) hipEventDestroy(e);
+  if (ctx->bstream) hipStreamDestroy(ctx->bstream);
+  if (ctx->stream) hipStreamDestroy(ctx->stream);
+}
+
 // --------------------------------------------------------------------------------------------------
 // the DP
 // --------------------------------------------------------------------------------------------------
-int run_bellman(mioc_ctx *ctx) {
-  ProblemDev P = problem_dev(ctx);
-  LevelsDev Lv = levels_dev(ctx);
-  // fills queued before the validation's host sync below, so that they overlap the previous call's device work: the
-  // DP counters, and (p = Inf, the likely algorithm) the segmented recursion's flags
-  if (!ctx->d_counters) {
-    size_t cc = 0;
-    int rc0 = grow(ctx, &ctx->d_counters, &cc, 8 * sizeof(int32_t), "counters");
-    if (rc0) return rc0;
-  }
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, 8 * sizeof(int32_t), ctx->stream));
-  bool pinf_flags_zeroed = false;
-  if (ctx->p_kind == MIOC_P_INF && !ctx->force_steps) {
-    const size_t fbytes = ((size_t)ctx->K * pinf_recur_segments(P) * PINF_WS_FLAG_STRIDE + 1) * sizeof(int32_t);
-    int rcf = grow(ctx, &ctx->d_runflags, &ctx->runflag_cap, fbytes, "p=Inf segment flags");
-    if (rcf) return rcf;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_runflags, 0, fbytes, ctx->stream));
-    pinf_flags_zeroed = true;
-  }
-  // validation pass: finite df, integral u_old, max budget class
+// the segmented p = Inf recursion's flags: K · segments records, then the error word
+size_t pinf_err_off(const mioc_ctx *ctx) {
+  return (size_t)ctx->K * pinf_recur_segments(problem_dev(ctx)) * PINF_WS_FLAG_STRIDE;
+}
+// ... sized and cleared.  validate_inputs queues this before its host sync, so that the fill overlaps the previous
+// call's device work; run_pinf has nothing left to clear (algorithm MIOC_ALGO_PINF implies cost MIOC_P_INF)
+int pinf_prepare_flags(mioc_ctx *ctx) {
+  const size_t fbytes = (pinf_err_off(ctx) + 1) * sizeof(int32_t);
+  const int rc = ctx->d_runflags.grow(ctx, fbytes, "p=Inf segment flags");
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_runflags.get(), 0, fbytes, ctx->stream));
+  return MIOC_OK;
+}
+
+// validation pass: finite df, integral u_old, max budget class
+int validate_inputs(mioc_ctx *ctx, int *bmax) {
+  // fills queued before the host sync below, so that they overlap the previous call's device work: the DP counters,
+  // and (p = Inf, the likely algorithm) the segmented recursion's flags
+  int rc = ctx->d_counters.grow(ctx, 8 * sizeof(int32_t), "counters");
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters.get(), 0, 8 * sizeof(int32_t), ctx->stream));
+  if (ctx->p_kind == MIOC_P_INF && !ctx->force_steps && (rc = pinf_prepare_flags(ctx))) return rc;
   // (words 0, 1 only: 2, 3 are a backtrack's, which may still run on the other stream)
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_flags, 0, 2 * sizeof(int32_t), ctx->stream));
-  HIP_TRY(ctx, launch_validate(ctx->stream, P, ctx->d_numin, ctx->d_numax, ctx->d_flags));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_flags.get(), 0, 2 * sizeof(int32_t), ctx->stream));
+  HIP_TRY(ctx, launch_validate(ctx->stream, problem_dev(ctx), ctx->d_numin.get(), ctx->d_numax.get(), ctx->d_flags.get()));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_flags.get(), ctx->d_flags.get(), 2 * sizeof(int32_t), hipMemcpyDeviceToHost,
+                              ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (ctx->h_flags[0] & 2)
     return fail(ctx, MIOC_EINEXACT, "u_old has a non-integral entry: convert(Int64, abs(nu - u_old)) "
                                     "would throw InexactError (HelpFunctions.jl:37,57)");
   if (ctx->h_flags[0] & 1) return fail(ctx, MIOC_ENONFINITE, "df has a non-finite entry");
-  const int bmax = ctx->h_flags[1];
+  *bmax = ctx->h_flags[1];
+  return MIOC_OK;
+}
 
+int choose_algo(mioc_ctx *ctx, int bmax, int *algo_out) {
   int algo = (int)ctx->opt_algo;
   // the p=Inf recursion keeps two budget rows and the staged class rows in LDS
   const bool pinf_ok = ctx->p_kind == MIOC_P_INF && bmax + 1 <= 64 && ctx->RP <= 7936;
@@ -321,265 +274,279 @@ int run_bellman(mioc_ctx *ctx) {
   if (algo == MIOC_ALGO_SEPARABLE && !sdt_ok)
     return fail(ctx, MIOC_EINVAL, "the separable L1 transform needs p = 1, beta > 0 and an 8^3 or 8^4 product grid "
                                   "of consecutive integer levels");
-  ctx->algo = algo;
-  const size_t K = (size_t)ctx->K, nt = (size_t)ctx->nt, L = (size_t)ctx->L, RP = (size_t)ctx->RP;
+  *algo_out = algo;
+  return MIOC_OK;
+}
 
-  if (algo == MIOC_ALGO_PYRAMID || algo == MIOC_ALGO_SEPARABLE) {
-    const size_t s_stride = (size_t)(ctx->B + 1) * L;
-    // persistent separable transform: rows 1..B of every subproblem in contiguous chunks over resident workgroups
-    // (one per CU: the row body needs 2 waves per SIMD of registers and ~106 KB of LDS), row 0 of every step
-    // precomputed (k_sdt_chain, k_sdt_row0), NB staging buffers
-    const size_t run_lds = sdt_lds_bytes(ctx->pyr);
-    int nwg = 0;
-    bool persist = false;
-    // (B + 1)·L·8 < 2^31: the persistent kernel addresses a staging block with 32-bit buffer offsets
-    // ... and every b̃ within the kernel's dependency window (7 per dimension: u_old on the level grid); a u_old
-    // off the grid reaches rows further back than the window waits for, so those problems take per-step launches
-    if (algo == MIOC_ALGO_SEPARABLE && ctx->opt_persist && nt >= 2 && ctx->B >= 1 &&
-        s_stride * sizeof(double) < (1ull << 31) && bmax <= 7 * ctx->pyr.M && !ctx->force_steps) {
-      int ncu = 0;
-      HIP_TRY(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-      // one workgroup per CU over contiguous row chunks (k_sdt_run)
-      const int bpc = std::min(sdt_run_blocks_per_cu(ctx->pyr, run_lds), 1);  // one row workgroup per CU
-      const size_t slots = (size_t)ncu * (size_t)std::max(bpc, 0);
-      const size_t per_k = std::min<size_t>((size_t)ctx->B, K ? slots / K : 0);  // workgroups per subproblem
-      nwg = (int)(per_k * K);
-      persist = per_k >= 1;
-    }
-    // persistent layout: per subproblem NB staging buffers of (B+1)·L, then row 0 of every step (nt·L), one region
-    // addressed by one buffer resource (< 4 GiB); per-step layout: two buffers of K blocks of (B+1)·L
-    // at least 7·M + 1 buffers: item (c', i) waits (write-after-read) for the rows up to 7·M above it to have loaded
-    // S_{i+NB}, and (one item ahead) for the rows below it to have finished step i; with NB <= 7·M those waits close a
-    // cycle -- (c', i) <- (c'-1, i-1) <- ... <- (c'-NB, i-NB), whose WAR wait needs row c' to have loaded S_i, i.e.
-    // item (c', i-1) -- and the DP deadlocks until the spin limit (tests/test_gpu_c4.py runs 29, 32 and 37)
-    const int nb_min = 7 * ctx->pyr.M + 1;
-    int nbuf = persist ? std::max(ctx->opt_nb, nb_min) : 2;
-    // one buffer resource addresses a subproblem's whole region (32-bit offsets): as many buffers as fit under 4 GiB
-    if (persist) {
-      const size_t cap = (1ull << 32) / sizeof(double);
-      const size_t fit = cap > nt * L ? (cap - nt * L - 1) / s_stride : 0;
-      if ((size_t)nbuf > fit) nbuf = (int)fit;
-      if (nbuf < nb_min) persist = false, nbuf = 2;  // too few fit to be deadlock-free: per-step launches
-    }
-    const size_t kstride = persist ? (size_t)nbuf * s_stride + nt * L : s_stride;
-    if (persist && kstride * sizeof(double) >= (1ull << 32)) persist = false;  // (then also kstride = s_stride)
-    const size_t ks = persist ? kstride : s_stride;
-    // flags: done and loaded per row, then the error word
-    const size_t nflag = 2 * K * (size_t)(ctx->B + 1) * SDT_FLAG_STRIDE;
-    const size_t runflag_bytes = ((nflag + 1) * sizeof(int32_t) + 15) / 16 * 16;
-    if (persist) {
-      int rcf = grow(ctx, &ctx->d_runflags, &ctx->runflag_cap, runflag_bytes, "persistent row flags");
-      if (!rcf) rcf = grow(ctx, &ctx->d_chain, &ctx->chain_cap, K * nt * sizeof(double), "row 0 chain");
-      if (rcf) return rcf;
-      if (!ctx->h_run_err) HIP_TRY(ctx, hipHostMalloc(&ctx->h_run_err, 16, 0));
-      *ctx->h_run_err = 0;
-    }
-    const size_t stage_doubles = persist ? K * ks : 2 * K * s_stride;
-    int rc = grow(ctx, &ctx->d_stage, &ctx->stage_cap, stage_doubles * sizeof(double), "staging fronts");
+// where the tables of a DP of the context's problem lie (run_staged sets the staging blocks' distance)
+DpLayout dp_layout(const mioc_ctx *ctx, int algo) {
+  const size_t L = (size_t)ctx->L, steps = ctx->nt > 1 ? (size_t)ctx->nt - 1 : 1;
+  const bool staged = algo == MIOC_ALGO_PYRAMID || algo == MIOC_ALGO_SEPARABLE;
+  DpLayout y;
+  y.algo = algo;
+  y.ubytes = staged || (algo == MIOC_ALGO_GENERIC && L > 256) ? 2 : 1;
+  y.s_stride = (size_t)(ctx->B + 1) * L;
+  y.stage_kstride = y.s_stride;
+  y.uu_stride_k = y.u_stride_k = steps * y.s_stride;
+  y.front_stride = L * (size_t)ctx->RP;
+  return y;
+}
+
+// the DP just queued hands rows between its workgroups: its timeout word (lay.err_buf, lay.err_off) follows it to
+// the host, where check_run reads it after the next synchronisation
+int queue_timeout_read(mioc_ctx *ctx) {
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_run_err.get(), ctx->lay.err_buf->get() + ctx->lay.err_off, sizeof(int32_t),
+                              hipMemcpyDeviceToHost, ctx->stream));
+  ctx->run_pending = true;
+  return MIOC_OK;
+}
+
+int run_bellman(mioc_ctx *ctx);
+
+// The DP again from its validation, without in-launch hand-offs between workgroups (force_steps: per-step launches,
+// one workgroup per subproblem), which needs no co-residency: after a dependency wait timed out (check_run), or
+// instead of a segmented launch whose workgroups would not all be resident (run_fused).
+int redo_unsegmented(mioc_ctx *ctx) {
+  ctx->n_persist_fallbacks += 1;
+  ctx->force_steps = true;
+  const int rc = run_bellman(ctx);
+  ctx->force_steps = false;
+  return rc;
+}
+
+// the L1-ball pyramid and the separable transform: fronts in the staging layout, each row in sphere order
+int run_staged(mioc_ctx *ctx, int bmax) {
+  const ProblemDev P = problem_dev(ctx);
+  const LevelsDev Lv = levels_dev(ctx);
+  DpLayout &Y = ctx->lay;
+  const bool sdt = Y.algo == MIOC_ALGO_SEPARABLE;
+  const size_t K = (size_t)ctx->K, nt = (size_t)ctx->nt, L = (size_t)ctx->L, s_stride = Y.s_stride;
+  const size_t run_lds = sdt_lds_bytes(ctx->pyr);
+  const bool want_persist = sdt && ctx->opt_persist;
+  const SdtPlan plan = sdt_stage_plan(K, nt, ctx->B, L, ctx->pyr.M, bmax, ctx->opt_nb, want_persist, ctx->force_steps,
+                                      ctx->ncu, want_persist ? sdt_run_blocks_per_cu(ctx->pyr, run_lds) : 0);
+  const bool persist = plan.persist;
+  const size_t ks = Y.stage_kstride = plan.kstride;
+  // flags: done and loaded per row, then the error word
+  const size_t nflag = 2 * K * (size_t)(ctx->B + 1) * SDT_FLAG_STRIDE;
+  const size_t runflag_bytes = ((nflag + 1) * sizeof(int32_t) + 15) / 16 * 16;
+  int rc = MIOC_OK;
+  if (persist) {
+    rc = ctx->d_runflags.grow(ctx, runflag_bytes, "persistent row flags");
+    if (!rc) rc = ctx->d_chain.grow(ctx, K * nt * sizeof(double), "row 0 chain");
     if (rc) return rc;
-    ctx->stage_kstride = ks;
-    const size_t uu_stride_k = (nt > 1 ? nt - 1 : 1) * s_stride;
-    rc = grow(ctx, &ctx->d_U, &ctx->U_cap, K * uu_stride_k * sizeof(uint16_t), "argmin table U");
-    if (rc) return rc;
-    rc = grow(ctx, &ctx->d_perm, &ctx->perm_cap, K * nt * L * sizeof(uint32_t), "sphere orders");
-    if (!rc) rc = grow(ctx, &ctx->d_same2, &ctx->same2_cap, K * nt * sizeof(int32_t), "sphere-order reuse flags");
-    const bool seams = persist && sdt_seam_lists(ctx->pyr);
-    if (!rc && seams) rc = grow(ctx, &ctx->d_strad, &ctx->strad_cap, K * nt * 8 * 32 * sizeof(uint16_t), "seam lists");
-    if (rc) return rc;
-    double *st[2] = {ctx->d_stage, ctx->d_stage + K * s_stride};
-    double *term = persist ? ctx->d_stage + ((nt - 1) % nbuf) * s_stride : st[(nt - 1) & 1];
-    HIP_TRY(ctx, launch_pyr_order(ctx->stream, P, ctx->pyr, ctx->d_perm, ctx->d_same2, seams ? ctx->d_strad : nullptr,
-                                  ctx->d_counters));
-    HIP_TRY(ctx, launch_pyr_terminal(ctx->stream, P, Lv, ctx->d_perm, term, ks));
-    if (algo == MIOC_ALGO_SEPARABLE && persist) {
-      // the whole DP as one persistent launch: rows handed between resident workgroups by flags
-      HIP_TRY(ctx, launch_sdt_prep(ctx->stream, P, Lv, ctx->pyr, ctx->d_perm, ctx->d_chain, ctx->d_stage, ks,
-                                   (size_t)nbuf * s_stride, (uint16_t *)ctx->d_U, uu_stride_k));
-      HIP_TRY(ctx, hipMemsetAsync(ctx->d_runflags, 0, runflag_bytes, ctx->stream));
-      ev_begin(ctx, 0, "k_sdt_run");
-      // (the grid is nwg <= CUs x resident workgroups per CU by construction above; a wait that never ends anyway --
-      // another process holding CUs -- is caught by the spin limit and redone per step by check_run)
-      HIP_TRY(ctx, launch_sdt_run(ctx->stream, P, Lv, ctx->pyr, ctx->d_perm, ctx->d_same2, ctx->d_strad, ctx->d_stage,
-                                  ks, nbuf, (uint16_t *)ctx->d_U, uu_stride_k, ctx->d_counters, ctx->d_runflags, nwg,
-                                  ctx->spin_limit, run_lds));
-      ev_end(ctx, 0, 1);
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_run_err, ctx->d_runflags + nflag, sizeof(int32_t),
-                                  hipMemcpyDeviceToHost, ctx->stream));
-      ctx->run_pending = true;
-    } else if (algo == MIOC_ALGO_SEPARABLE) {
-      ev_begin(ctx, 0, "k_sdt_step");
-      for (int i = ctx->nt - 2; i >= 0; --i)
-        HIP_TRY(ctx, launch_sdt_step(ctx->stream, P, Lv, ctx->pyr, i, ctx->d_perm, st[(i + 1) & 1], st[i & 1],
-                                     (uint16_t *)ctx->d_U, s_stride, uu_stride_k, ctx->d_counters));
-      ev_end(ctx, 0, ctx->nt - 1);
-    } else {
-      ev_begin(ctx, 0, "k_pyr_step");
-      for (int i = ctx->nt - 2; i >= 0; --i)
-        HIP_TRY(ctx, launch_pyr_step(ctx->stream, P, Lv, ctx->pyr, i, ctx->d_perm, st[(i + 1) & 1], st[i & 1],
-                                     (uint16_t *)ctx->d_U, s_stride, uu_stride_k, ctx->d_counters));
-      ev_end(ctx, 0, ctx->nt - 1);
-    }
-  } else if (algo == MIOC_ALGO_FUSED || algo == MIOC_ALGO_FUSED_SEPARABLE) {
-    ctx->ubytes = 1;
-    const size_t front_stride = L * RP;
-    int rc = grow(ctx, &ctx->d_front, &ctx->front_cap, K * front_stride * sizeof(double), "value fronts");
-    if (rc) return rc;
-    const size_t u_stride_k = (nt > 1 ? nt - 1 : 1) * L * (size_t)(ctx->B + 1);
-    rc = grow(ctx, &ctx->d_U, &ctx->U_cap, K * u_stride_k, "argmin table U");
-    if (rc) return rc;
-    ctx->occupancy = fused_blocks_per_cu(algo == MIOC_ALGO_FUSED_SEPARABLE, ctx->pyr, (int)ctx->L, ctx->B);
-    if (algo == MIOC_ALGO_FUSED) {
-      ev_begin(ctx, 0, "k_fused_run");
-      HIP_TRY(ctx, launch_fused_run(ctx->stream, P, Lv, ctx->d_front, front_stride, (uint8_t *)ctx->d_U, u_stride_k));
-    } else {
-      // two lanes per row, the front in place (mioc_fsep.hip); S row segments per subproblem when the batch alone
-      // would leave CUs idle (two resident subproblems per CU when the front is half the LDS)
-      FsepPlan plan;
-      int S = ctx->force_steps ? 1 : ctx->opt_fsep_seg;
-      if (S == 0) {
-        int ncu = 0;
-        HIP_TRY(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-        S = 1;
-        // (only segments of whole waves of rows: the even split with idle lane groups is for forced counts)
-        FsepPlan t;
-        while (S < 8 && (size_t)K * (size_t)(2 * S) <= (size_t)ncu && fsep2_plan(ctx->pyr, ctx->B, 2 * S, &t) &&
-               t.RS == t.W * (64 / t.lanes))
-          S *= 2;
-      }
-      // a u_old off the level grid can send a target further than SMAX rows up, past a segment's outbox rows
-      if (S > 1 && bmax > ctx->pyr.n[0] + ctx->pyr.n[1] - 2) S = 1;
-      const bool v2 = S >= 1 && fsep2_plan(ctx->pyr, ctx->B, S, &plan);
-      ctx->last_fsep_seg = v2 ? S : 0;
-      if (v2 && S > 1) {
-        // segments with at most one workgroup per CU to go round: reserve more than half a CU's LDS, so that the
-        // dispatcher cannot put two segments on one CU while another CU idles (the segments run as one pipeline,
-        // and a shared CU slows all of them: the 128-restart shard ran 17 - 28 ms from run to run)
-        int ncu = 0, cu_lds = 0, wg_lds = 0;
-        HIP_TRY(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-        HIP_TRY(ctx, hipDeviceGetAttribute(&cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, ctx->device));
-        HIP_TRY(ctx, hipDeviceGetAttribute(&wg_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
-        // half a CU's LDS plus one 2 KiB allocation granule (gfx950: 82 KiB of 160), capped at a workgroup's maximum
-        const size_t half = std::min<size_t>((size_t)cu_lds / 2 + 2048, (size_t)wg_lds);
-        if ((size_t)K * (size_t)S <= (size_t)ncu) plan.lds = std::max<size_t>(plan.lds, half);
-      }
-      if (v2) ctx->occupancy = fsep2_blocks_per_cu(ctx->pyr, plan);
-      if (v2 && S > 1) {
-        const int NB = 8, SM = ctx->pyr.n[0] + ctx->pyr.n[1] - 2;
-        (void)SM;
-        rc = grow(ctx, &ctx->d_ring, &ctx->ring_cap, K * (size_t)S * NB * (size_t)plan.slot_bytes, "segment rings");
-        if (!rc) rc = grow(ctx, &ctx->d_segflags, &ctx->segflag_cap, (FSEP_FLAG_STRIDE * K * (size_t)S + 1) * sizeof(int32_t),
-                           "segment flags");
-        if (rc) return rc;
-        if (!ctx->h_run_err) HIP_TRY(ctx, hipHostMalloc(&ctx->h_run_err, 16, 0));
-        *ctx->h_run_err = 0;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_segflags, 0, (FSEP_FLAG_STRIDE * K * (size_t)S + 1) * sizeof(int32_t), ctx->stream));
-        ev_begin(ctx, 0, "k_fsep2");
-        int ncu = 0;
-        HIP_TRY(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-        // every segment must be resident at once (they wait for each other): else the unsegmented kernel below
-        const hipError_t le =
-            (size_t)K * (size_t)S > (size_t)ncu * (size_t)std::max<int64_t>(ctx->occupancy, 0)
-                ? hipErrorCooperativeLaunchTooLarge
-                : launch_fsep2(ctx->stream, P, Lv, ctx->pyr, plan, ctx->d_front, front_stride, (uint8_t *)ctx->d_U,
-                               u_stride_k, ctx->d_counters, ctx->d_ring, NB, ctx->d_segflags, ctx->spin_limit);
-        if (le == hipErrorCooperativeLaunchTooLarge) {  // not every segment resident: one workgroup per subproblem
-          ev_end(ctx, 0, 0);
-          ctx->n_persist_fallbacks += 1;
-          ctx->force_steps = true;
-          const int rcs = run_bellman(ctx);
-          ctx->force_steps = false;
-          return rcs;
-        }
-        HIP_TRY(ctx, le);
-        ev_end(ctx, 0, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_run_err, ctx->d_segflags + FSEP_FLAG_STRIDE * K * (size_t)S, sizeof(int32_t),
-                                    hipMemcpyDeviceToHost, ctx->stream));
-        ctx->run_pending = true;
-        ctx->have_dp = true;
-        return MIOC_OK;
-      }
-      if (v2) {
-        ev_begin(ctx, 0, "k_fsep2");
-        HIP_TRY(ctx, launch_fsep2(ctx->stream, P, Lv, ctx->pyr, plan, ctx->d_front, front_stride, (uint8_t *)ctx->d_U,
-                                  u_stride_k, ctx->d_counters, nullptr, 1, nullptr, ctx->spin_limit));
-      } else {
-        ev_begin(ctx, 0, "k_fsep_run");
-        HIP_TRY(ctx, launch_fsep_run(ctx->stream, P, Lv, ctx->pyr, ctx->d_front, front_stride, (uint8_t *)ctx->d_U,
-                                     u_stride_k, ctx->d_counters));
-      }
-    }
-    ev_end(ctx, 0, 1);
-  } else if (algo == MIOC_ALGO_GENERIC) {
-    ctx->ubytes = L <= 256 ? 1 : 2;
-    const size_t front_stride = L * RP;
-    int rc = grow(ctx, &ctx->d_front, &ctx->front_cap, 2 * K * front_stride * sizeof(double), "value fronts");
-    if (rc) return rc;
-    const size_t u_stride_k = (nt > 1 ? nt - 1 : 1) * L * (size_t)(ctx->B + 1);
-    rc = grow(ctx, &ctx->d_U, &ctx->U_cap, K * u_stride_k * ctx->ubytes, "argmin table U");
-    if (rc) return rc;
-    double *fr[2] = {ctx->d_front, ctx->d_front + K * front_stride};
-    HIP_TRY(ctx, launch_generic_terminal(ctx->stream, P, Lv, fr[(nt - 1) & 1], front_stride));
-    ev_begin(ctx, 0, "k_generic_step");
-    for (int i = ctx->nt - 2; i >= 0; --i)
-      HIP_TRY(ctx, launch_generic_step(ctx->stream, P, Lv, i, fr[(i + 1) & 1], fr[i & 1], ctx->d_U, ctx->ubytes,
-                                       front_stride, u_stride_k));
-    ev_end(ctx, 0, ctx->nt - 1);
-  } else {
-    PinfDev &D = ctx->pinf;
-    D.BW = bmax + 1;
-    D.BWP = 8;
-    while (D.BWP < D.BW) D.BWP *= 2;
-    const size_t kcells = K * nt * (size_t)D.BWP;
-    size_t cap_km = ctx->pinf_cap_k, cap_k2 = ctx->pinf_cap_k, cap_kf = ctx->pinf_cap_k;
-    int rc = grow(ctx, &D.kmin, &cap_km, kcells * sizeof(double), "class minima");
-    if (!rc) rc = grow(ctx, &D.k2, &cap_k2, kcells * sizeof(double), "class second minima");
-    if (!rc) rc = grow(ctx, &D.kfirst, &cap_kf, kcells * sizeof(double), "class first ranks");
-    if (rc) return rc;
-    ctx->pinf_cap_k = std::min(cap_km, std::min(cap_k2, cap_kf));
-    pinf_plan((int)RP, (int)nt, D);
-    rc = grow(ctx, &D.R, &ctx->pinf_cap_R, K * nt * RP * sizeof(double), "row minima R");
-    if (!rc) rc = grow(ctx, &D.kabs, &ctx->pinf_cap_kabs, K * nt * sizeof(double), "level value bounds");
-    if (rc) return rc;
-    ev_begin(ctx, 2, "k_pinf_prep");
-    HIP_TRY(ctx, launch_pinf_prep(ctx->stream, P, Lv, D));
-    ev_end(ctx, 2, 1);
-    ev_begin(ctx, 0, "k_pinf_recur");
-    if (!ctx->ncu) HIP_TRY(ctx, hipDeviceGetAttribute(&ctx->ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    // row segments on several CUs need their hand-off flags (and a timed-out wait redoes the DP in one workgroup)
-    int32_t *pflags = nullptr;
-    if (!ctx->force_steps) {
-      if (!pinf_flags_zeroed) {
-        const size_t fbytes = ((size_t)K * pinf_recur_segments(P) * PINF_WS_FLAG_STRIDE + 1) * sizeof(int32_t);
-        rc = grow(ctx, &ctx->d_runflags, &ctx->runflag_cap, fbytes, "p=Inf segment flags");
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_runflags, 0, fbytes, ctx->stream));
-      }
-      if (!ctx->h_run_err) HIP_TRY(ctx, hipHostMalloc(&ctx->h_run_err, 16, 0));
-      *ctx->h_run_err = 0;
-      pflags = ctx->d_runflags;
-    }
-    bool segmented = false;
-    const char *variant = "k_pinf_recur";
-    HIP_TRY(ctx, launch_pinf_recur(ctx->stream, P, D, ctx->ncu, pflags, ctx->spin_limit, &segmented, &variant));
-    ev_end(ctx, 0, 1);
-    ctx->stat_name[0] = variant;  // the timing window is named after the recursion kernel that ran
-    if (segmented) {
-      const int nseg = pinf_recur_segments(P);
-      if (!P.gate) {
-        // a wait past the spin limit: the one-workgroup recursion redoes the DP on the device, gated by the error word
-        // (no host round trip between the DP and the backtrack); diagnostics [6] reads its count (d_counters[6])
-        ProblemDev Pr = P;
-        Pr.redo_gate = ctx->d_runflags + (size_t)K * nseg * PINF_WS_FLAG_STRIDE;
-        Pr.redo_count = ctx->d_counters + 6;
-        HIP_TRY(ctx, launch_pinf_recur(ctx->stream, Pr, D, ctx->ncu, nullptr, ctx->spin_limit, nullptr, nullptr));
-      } else {
-        // under the device TRM control the backtrack kernels are gated already: the host checks and redoes (check_run)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_run_err, ctx->d_runflags + (size_t)K * nseg * PINF_WS_FLAG_STRIDE, sizeof(int32_t),
-                                    hipMemcpyDeviceToHost, ctx->stream));
-        ctx->run_pending = true;
-      }
-    }
+    ctx->h_run_err[0] = 0;
   }
+  const size_t stage_doubles = persist ? K * ks : 2 * K * s_stride;
+  rc = ctx->d_stage.grow(ctx, stage_doubles * sizeof(double), "staging fronts");
+  if (!rc) rc = ctx->d_U.grow(ctx, K * Y.uu_stride_k * sizeof(uint16_t), "argmin table U");
+  if (rc) return rc;
+  rc = ctx->d_perm.grow(ctx, K * nt * L * sizeof(uint32_t), "sphere orders");
+  if (!rc) rc = ctx->d_same2.grow(ctx, K * nt * sizeof(int32_t), "sphere-order reuse flags");
+  const bool seams = persist && sdt_seam_lists(ctx->pyr);
+  if (!rc && seams) rc = ctx->d_strad.grow(ctx, K * nt * 8 * 32 * sizeof(uint16_t), "seam lists");
+  if (rc) return rc;
+  double *const stage = ctx->d_stage.get();
+  uint16_t *const UU = (uint16_t *)ctx->d_U.get();
+  uint32_t *const perm = ctx->d_perm.get();
+  int32_t *const counters = ctx->d_counters.get();
+  double *st[2] = {stage, stage + K * s_stride};
+  double *term = persist ? stage + ((nt - 1) % plan.nbuf) * s_stride : st[(nt - 1) & 1];
+  HIP_TRY(ctx, launch_pyr_order(ctx->stream, P, ctx->pyr, perm, ctx->d_same2.get(),
+                                seams ? ctx->d_strad.get() : nullptr, counters));
+  HIP_TRY(ctx, launch_pyr_terminal(ctx->stream, P, Lv, perm, term, ks));
+  if (persist) {
+    // the whole DP as one persistent launch: rows handed between resident workgroups by flags
+    HIP_TRY(ctx, launch_sdt_prep(ctx->stream, P, Lv, ctx->pyr, perm, ctx->d_chain.get(), stage, ks,
+                                 (size_t)plan.nbuf * s_stride, UU, Y.uu_stride_k));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_runflags.get(), 0, runflag_bytes, ctx->stream));
+    ev_begin(ctx, 0, "k_sdt_run");
+    // (the grid is nwg <= CUs x resident workgroups per CU by construction of the plan; a wait that never ends
+    // anyway -- another process holding CUs -- is caught by the spin limit and redone per step by check_run)
+    HIP_TRY(ctx, launch_sdt_run(ctx->stream, P, Lv, ctx->pyr, perm, ctx->d_same2.get(), ctx->d_strad.get(), stage, ks,
+                                plan.nbuf, UU, Y.uu_stride_k, counters, ctx->d_runflags.get(), plan.nwg,
+                                ctx->spin_limit, run_lds));
+    ev_end(ctx, 0, 1);
+    Y.err_buf = &ctx->d_runflags, Y.err_off = nflag;
+    return queue_timeout_read(ctx);
+  }
+  ev_begin(ctx, 0, sdt ? "k_sdt_step" : "k_pyr_step");
+  for (int i = ctx->nt - 2; i >= 0; --i)
+    HIP_TRY(ctx, (sdt ? launch_sdt_step : launch_pyr_step)(ctx->stream, P, Lv, ctx->pyr, i, perm, st[(i + 1) & 1],
+                                                           st[i & 1], UU, s_stride, Y.uu_stride_k, counters));
+  ev_end(ctx, 0, ctx->nt - 1);
+  return MIOC_OK;
+}
+
+// The row segments of a fused separable DP and their plan: `want` as MIOC_OPT_FSEP_SEGMENTS (0: chosen here, S row
+// segments per subproblem when the batch alone would leave CUs idle).  Returns S >= 1, or 0 for the one-lane-per-row
+// kernel of mioc_fused.hip.
+int fsep_segment_plan(const PyrGeom &G, size_t K, int B, int bmax, int want, int ncu, int cu_lds, int wg_lds,
+                      FsepPlan *plan) {
+  int S = want;
+  if (S == 0) {
+    S = 1;
+    // (only segments of whole waves of rows: the even split with idle lane groups is for forced counts)
+    FsepPlan t;
+    while (S < 8 && K * (size_t)(2 * S) <= (size_t)ncu && fsep2_plan(G, B, 2 * S, &t) && t.RS == t.W * (64 / t.lanes))
+      S *= 2;
+  }
+  // a u_old off the level grid can send a target further than SMAX rows up, past a segment's outbox rows
+  if (S > 1 && bmax > G.n[0] + G.n[1] - 2) S = 1;
+  if (S < 1 || !fsep2_plan(G, B, S, plan)) return 0;
+  if (S > 1 && K * (size_t)S <= (size_t)ncu) {
+    // segments with at most one workgroup per CU to go round: reserve more than half a CU's LDS, so that the
+    // dispatcher cannot put two segments on one CU while another CU idles (the segments run as one pipeline,
+    // and a shared CU slows all of them: the 128-restart shard ran 17 - 28 ms from run to run)
+    // half a CU's LDS plus one 2 KiB allocation granule (gfx950: 82 KiB of 160), capped at a workgroup's maximum
+    const size_t half = std::min<size_t>((size_t)cu_lds / 2 + 2048, (size_t)wg_lds);
+    plan->lds = std::max<size_t>(plan->lds, half);
+  }
+  return S;
+}
+
+// the fused small-state DPs: a subproblem's whole front in one CU's LDS, one launch
+int run_fused(mioc_ctx *ctx, int bmax) {
+  const ProblemDev P = problem_dev(ctx);
+  const LevelsDev Lv = levels_dev(ctx);
+  DpLayout &Y = ctx->lay;
+  const bool sep = Y.algo == MIOC_ALGO_FUSED_SEPARABLE;
+  const size_t K = (size_t)ctx->K;
+  int rc = ctx->d_front.grow(ctx, K * Y.front_stride * sizeof(double), "value fronts");
+  if (!rc) rc = ctx->d_U.grow(ctx, K * Y.u_stride_k, "argmin table U");
+  if (rc) return rc;
+  double *const front = ctx->d_front.get();
+  uint8_t *const U = ctx->d_U.get();
+  ctx->occupancy = fused_blocks_per_cu(sep, ctx->pyr, (int)ctx->L, ctx->B);
+  if (!sep) {
+    ev_begin(ctx, 0, "k_fused_run");
+    HIP_TRY(ctx, launch_fused_run(ctx->stream, P, Lv, front, Y.front_stride, U, Y.u_stride_k));
+    ev_end(ctx, 0, 1);
+    return MIOC_OK;
+  }
+  // two lanes per row, the front in place (mioc_fsep.hip), in S row segments (two resident subproblems per CU when
+  // the front is half the LDS)
+  FsepPlan plan;
+  const int S = fsep_segment_plan(ctx->pyr, K, ctx->B, bmax, ctx->force_steps ? 1 : ctx->opt_fsep_seg, ctx->ncu,
+                                  ctx->cu_lds, ctx->wg_lds, &plan);
+  ctx->last_fsep_seg = S;
+  if (S >= 1) ctx->occupancy = fsep2_blocks_per_cu(ctx->pyr, plan);
+  if (S > 1) {
+    const int NB = 8;
+    const size_t nflag = FSEP_FLAG_STRIDE * K * (size_t)S;  // the segments' records, then the error word
+    rc = ctx->d_ring.grow(ctx, K * (size_t)S * NB * (size_t)plan.slot_bytes, "segment rings");
+    if (!rc) rc = ctx->d_segflags.grow(ctx, (nflag + 1) * sizeof(int32_t), "segment flags");
+    if (rc) return rc;
+    ctx->h_run_err[0] = 0;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_segflags.get(), 0, (nflag + 1) * sizeof(int32_t), ctx->stream));
+    ev_begin(ctx, 0, "k_fsep2");
+    // every segment must be resident at once (they wait for each other): else one workgroup per subproblem
+    const bool resident = K * (size_t)S <= (size_t)ctx->ncu * (size_t)std::max<int64_t>(ctx->occupancy, 0);
+    if (!resident) {
+      ev_end(ctx, 0, 0);
+      return redo_unsegmented(ctx);
+    }
+    HIP_TRY(ctx, launch_fsep2(ctx->stream, P, Lv, ctx->pyr, plan, front, Y.front_stride, U, Y.u_stride_k,
+                              ctx->d_counters.get(), ctx->d_ring.get(), NB, ctx->d_segflags.get(), ctx->spin_limit));
+    ev_end(ctx, 0, 1);
+    Y.err_buf = &ctx->d_segflags, Y.err_off = nflag;
+    return queue_timeout_read(ctx);
+  }
+  if (S == 1) {
+    ev_begin(ctx, 0, "k_fsep2");
+    HIP_TRY(ctx, launch_fsep2(ctx->stream, P, Lv, ctx->pyr, plan, front, Y.front_stride, U, Y.u_stride_k,
+                              ctx->d_counters.get(), nullptr, 1, nullptr, ctx->spin_limit));
+  } else {
+    ev_begin(ctx, 0, "k_fsep_run");
+    HIP_TRY(ctx, launch_fsep_run(ctx->stream, P, Lv, ctx->pyr, front, Y.front_stride, U, Y.u_stride_k,
+                                 ctx->d_counters.get()));
+  }
+  ev_end(ctx, 0, 1);
+  return MIOC_OK;
+}
+
+// the generic min-plus sweep: one launch per step over two fronts
+int run_generic(mioc_ctx *ctx) {
+  const ProblemDev P = problem_dev(ctx);
+  const LevelsDev Lv = levels_dev(ctx);
+  const DpLayout &Y = ctx->lay;
+  const size_t K = (size_t)ctx->K, nt = (size_t)ctx->nt;
+  int rc = ctx->d_front.grow(ctx, 2 * K * Y.front_stride * sizeof(double), "value fronts");
+  if (!rc) rc = ctx->d_U.grow(ctx, K * Y.u_stride_k * Y.ubytes, "argmin table U");
+  if (rc) return rc;
+  double *fr[2] = {ctx->d_front.get(), ctx->d_front.get() + K * Y.front_stride};
+  HIP_TRY(ctx, launch_generic_terminal(ctx->stream, P, Lv, fr[(nt - 1) & 1], Y.front_stride));
+  ev_begin(ctx, 0, "k_generic_step");
+  for (int i = ctx->nt - 2; i >= 0; --i)
+    HIP_TRY(ctx, launch_generic_step(ctx->stream, P, Lv, i, fr[(i + 1) & 1], fr[i & 1], ctx->d_U.get(), Y.ubytes,
+                                     Y.front_stride, Y.u_stride_k));
+  ev_end(ctx, 0, ctx->nt - 1);
+  return MIOC_OK;
+}
+
+// the p = Inf collapse: per-budget class tables instead of U
+int run_pinf(mioc_ctx *ctx, int bmax) {
+  const ProblemDev P = problem_dev(ctx);
+  const LevelsDev Lv = levels_dev(ctx);
+  const size_t K = (size_t)ctx->K, nt = (size_t)ctx->nt, RP = (size_t)ctx->RP;
+  ctx->pinf_BW = bmax + 1;
+  ctx->pinf_BWP = 8;
+  while (ctx->pinf_BWP < ctx->pinf_BW) ctx->pinf_BWP *= 2;
+  const size_t kcells = K * nt * (size_t)ctx->pinf_BWP;
+  mioc_ctx::Slot &q = ctx->cur();
+  int rc = q.kmin.grow(ctx, kcells * sizeof(double), "class minima");
+  if (!rc) rc = q.k2.grow(ctx, kcells * sizeof(double), "class second minima");
+  if (!rc) rc = q.kfirst.grow(ctx, kcells * sizeof(double), "class first ranks");
+  if (!rc) rc = q.R.grow(ctx, K * nt * RP * sizeof(double), "row minima R");
+  if (!rc) rc = q.kabs.grow(ctx, K * nt * sizeof(double), "level value bounds");
+  if (rc) return rc;
+  PinfDev D = pinf_dev(ctx);
+  pinf_plan((int)RP, (int)nt, D);
+  ctx->pinf_CH = D.CH, ctx->pinf_W = D.W;
+  ev_begin(ctx, 2, "k_pinf_prep");
+  HIP_TRY(ctx, launch_pinf_prep(ctx->stream, P, Lv, D));
+  ev_end(ctx, 2, 1);
+  ev_begin(ctx, 0, "k_pinf_recur");
+  // row segments on several CUs need their hand-off flags, cleared by validate_inputs (and a timed-out wait redoes
+  // the DP in one workgroup)
+  int32_t *pflags = nullptr;
+  if (!ctx->force_steps) {
+    ctx->h_run_err[0] = 0;
+    pflags = ctx->d_runflags.get();
+  }
+  bool segmented = false;
+  const char *variant = "k_pinf_recur";
+  HIP_TRY(ctx, launch_pinf_recur(ctx->stream, P, D, ctx->ncu, pflags, ctx->spin_limit, &segmented, &variant));
+  ev_end(ctx, 0, 1);
+  ctx->stat_name[0] = variant;  // the timing window is named after the recursion kernel that ran
+  if (!segmented) return MIOC_OK;
+  ctx->lay.err_buf = &ctx->d_runflags, ctx->lay.err_off = pinf_err_off(ctx);
+  // under the device TRM control the backtrack kernels are gated already: the host checks and redoes (check_run)
+  if (P.gate) return queue_timeout_read(ctx);
+  // a wait past the spin limit: the one-workgroup recursion redoes the DP on the device, gated by the error word
+  // (no host round trip between the DP and the backtrack); diagnostics [6] reads its count (d_counters[6])
+  ProblemDev Pr = P;
+  Pr.redo_gate = ctx->d_runflags.get() + ctx->lay.err_off;
+  Pr.redo_count = ctx->d_counters.get() + 6;
+  HIP_TRY(ctx, launch_pinf_recur(ctx->stream, Pr, D, ctx->ncu, nullptr, ctx->spin_limit, nullptr, nullptr));
+  return MIOC_OK;
+}
+
+int run_bellman(mioc_ctx *ctx) {
+  int bmax = 0, algo = MIOC_ALGO_AUTO;
+  int rc = validate_inputs(ctx, &bmax);
+  if (!rc) rc = choose_algo(ctx, bmax, &algo);
+  if (rc) return rc;
+  ctx->lay = dp_layout(ctx, algo);
+  switch (algo) {
+    case MIOC_ALGO_PYRAMID:
+    case MIOC_ALGO_SEPARABLE: rc = run_staged(ctx, bmax); break;
+    case MIOC_ALGO_FUSED:
+    case MIOC_ALGO_FUSED_SEPARABLE: rc = run_fused(ctx, bmax); break;
+    case MIOC_ALGO_GENERIC: rc = run_generic(ctx); break;
+    default: rc = run_pinf(ctx, bmax);
+  }
+  if (rc) return rc;
   ctx->have_dp = true;
   return MIOC_OK;
 }
@@ -597,9 +564,10 @@ int run_backtrack(mioc_ctx *ctx, int64_t B_use, double *d_u_out, double *d_phi_s
   if (!ctx->have_dp) return fail(ctx, MIOC_ESTATE, "backtrack called before bellman");
   if (B_use < 0 || B_use > ctx->B)
     return fail(ctx, MIOC_ESTATE, "B_use must satisfy 0 <= B_use <= B of the last bellman call");
+  const DpLayout &Y = ctx->lay;
   // p = Inf (outside the device TRM control): on the second stream, after this DP, so that the next bellman's kernels
   // overlap it; the other algorithms run on the context's stream after any such backtrack in flight
-  const bool async_bt = ctx->algo == MIOC_ALGO_PINF && !ctx->gate;
+  const bool async_bt = Y.algo == MIOC_ALGO_PINF && !ctx->gate;
   if (!async_bt) {
     const int rcj = join_bt(ctx);
     if (rcj) return rcj;
@@ -612,66 +580,58 @@ int run_backtrack(mioc_ctx *ctx, int64_t B_use, double *d_u_out, double *d_phi_s
   ProblemDev P = problem_dev(ctx);
   LevelsDev Lv = levels_dev(ctx);
   const size_t K = (size_t)ctx->K, nt = (size_t)ctx->nt;
-  size_t cap = 0;
-  if (!ctx->d_start) {
-    int rc = grow(ctx, &ctx->d_start, &cap, 4096 * sizeof(Start), "start cells");
-    if (rc) return rc;
-  }
-  if (K > 4096) return fail(ctx, MIOC_EINVAL, "batch larger than 4096 subproblems");
-  int rc = grow(ctx, &ctx->d_ranks, &ctx->ranks_cap, 2 * K * nt * sizeof(int32_t), "rank path");
+  int rc = ctx->d_start.grow(ctx, 4096 * sizeof(Start), "start cells");
   if (rc) return rc;
-  int32_t *d_urank = ctx->d_ranks + K * nt;
-  if (ctx->algo != MIOC_ALGO_PINF) HIP_TRY(ctx, launch_uold_rank(ctx->stream, P, Lv, d_urank));
+  if (K > 4096) return fail(ctx, MIOC_EINVAL, "batch larger than 4096 subproblems");
+  rc = ctx->d_ranks.grow(ctx, 2 * K * nt * sizeof(int32_t), "rank path");
+  if (rc) return rc;
+  Start *const start = ctx->d_start.get();
+  int32_t *const ranks = ctx->d_ranks.get(), *const d_urank = ranks + K * nt, *const walk_flags = ctx->d_flags.get() + 2;
+  if (Y.algo != MIOC_ALGO_PINF) HIP_TRY(ctx, launch_uold_rank(ctx->stream, P, Lv, d_urank));
   // (p = Inf: k_pinf_start zeroes them, one fill fewer on the stream)
-  if (ctx->algo != MIOC_ALGO_PINF) HIP_TRY(ctx, hipMemsetAsync(ctx->d_flags + 2, 0, 2 * sizeof(int32_t), ctx->stream));
-  if (ctx->algo == MIOC_ALGO_PYRAMID || ctx->algo == MIOC_ALGO_SEPARABLE) {
-    const size_t s_stride = (size_t)(ctx->B + 1) * ctx->L;
-    const size_t uu_stride_k = (nt > 1 ? nt - 1 : 1) * s_stride;
-    HIP_TRY(ctx, launch_stage_argmin0(ctx->stream, P, Lv, ctx->d_perm, ctx->d_stage, ctx->stage_kstride, (int)B_use,
-                                      ctx->d_start));
+  if (Y.algo != MIOC_ALGO_PINF) HIP_TRY(ctx, hipMemsetAsync(walk_flags, 0, 2 * sizeof(int32_t), ctx->stream));
+  if (Y.algo == MIOC_ALGO_PYRAMID || Y.algo == MIOC_ALGO_SEPARABLE) {
+    HIP_TRY(ctx, launch_stage_argmin0(ctx->stream, P, Lv, ctx->d_perm.get(), ctx->d_stage.get(), Y.stage_kstride,
+                                      (int)B_use, start));
     ev_begin(ctx, 1, "k_stage_walk");
-    HIP_TRY(ctx, launch_stage_walk(ctx->stream, P, Lv, (const uint16_t *)ctx->d_U, uu_stride_k, ctx->d_start,
-                                   d_urank, ctx->d_ranks, ctx->d_flags + 2));
+    HIP_TRY(ctx, launch_stage_walk(ctx->stream, P, Lv, (const uint16_t *)ctx->d_U.get(), Y.uu_stride_k, start, d_urank,
+                                   ranks, walk_flags));
     ev_end(ctx, 1, 1);
-  } else if (ctx->algo == MIOC_ALGO_GENERIC || ctx->algo == MIOC_ALGO_FUSED ||
-             ctx->algo == MIOC_ALGO_FUSED_SEPARABLE) {
-    const size_t front_stride = (size_t)ctx->L * ctx->RP;
-    const size_t u_stride_k = (nt > 1 ? nt - 1 : 1) * (size_t)ctx->L * (size_t)(ctx->B + 1);
-    HIP_TRY(ctx, launch_generic_argmin0(ctx->stream, P, Lv, ctx->d_front, front_stride, (int)B_use, ctx->d_start));
+  } else if (Y.algo != MIOC_ALGO_PINF) {  // generic, fused, fused separable
+    HIP_TRY(ctx, launch_generic_argmin0(ctx->stream, P, Lv, ctx->d_front.get(), Y.front_stride, (int)B_use, start));
     ev_begin(ctx, 1, "k_generic_walk");
-    HIP_TRY(ctx, launch_generic_walk(ctx->stream, P, Lv, ctx->d_U, ctx->ubytes, u_stride_k, ctx->d_start,
-                                     d_urank, ctx->d_ranks, ctx->d_flags + 2));
+    HIP_TRY(ctx, launch_generic_walk(ctx->stream, P, Lv, ctx->d_U.get(), Y.ubytes, Y.u_stride_k, start, d_urank, ranks,
+                                     walk_flags));
     ev_end(ctx, 1, 1);
   } else {
     // the segmented walk spreads one subproblem's path over many workgroups: for batches too small to fill the GPU
     // with one serial walk each (auto: K <= 64 and at least 512 steps)
     const bool fwalk = ctx->opt_pinf_walk > 0 || (ctx->opt_pinf_walk == 0 && K <= 64 && nt >= 512);
     ctx->last_pinf_fwalk = fwalk;
-    PinfDev &D = ctx->pinf;
     if (fwalk) {
       int G, nseg;
       pinf_fplan((int)nt, &G, &nseg);
-      rc = grow(ctx, &D.ftab, &ctx->pinf_cap_ftab, K * nt * (size_t)ctx->RP, "segmented walk class table");
-      if (!rc) rc = grow(ctx, &D.fseg, &ctx->pinf_cap_fseg, K * (size_t)nseg * ctx->RP * sizeof(int32_t),
-                         "segmented walk segment maps");
-      if (!rc) rc = grow(ctx, &D.fneed, &ctx->pinf_cap_fneed, (K + 1) * sizeof(int32_t), "segmented walk flags");
+      rc = ctx->d_ftab.grow(ctx, K * nt * (size_t)ctx->RP, "segmented walk class table");
+      if (!rc) rc = ctx->d_fseg.grow(ctx, K * (size_t)nseg * ctx->RP * sizeof(int32_t), "segmented walk segment maps");
+      if (!rc) rc = ctx->d_fneed.grow(ctx, (K + 1) * sizeof(int32_t), "segmented walk flags");
       if (rc) return rc;
     }
+    const PinfDev D = pinf_dev(ctx);
     // k_pinf_start also zeroes the walk's fallback counters (d_flags[2..3]) and, for the segmented walk, fneed
-    HIP_TRY(ctx, launch_pinf_start(bs, P, Lv, D, (int)B_use, ctx->d_start, ctx->d_flags + 2, fwalk ? D.fneed : nullptr));
+    HIP_TRY(ctx, launch_pinf_start(bs, P, Lv, D, (int)B_use, start, walk_flags, fwalk ? D.fneed : nullptr));
     if (fwalk) {
       ev_begin(ctx, 1, "k_pinf_fwalk", bs);
-      HIP_TRY(ctx, launch_pinf_fwalk(bs, P, Lv, D, ctx->d_start, ctx->d_ranks));
+      HIP_TRY(ctx, launch_pinf_fwalk(bs, P, Lv, D, start, ranks));
       // subproblems whose chain met a state-dependent row: the serial walk (the others return at once)
-      HIP_TRY(ctx, launch_pinf_walk(bs, P, Lv, D, ctx->d_start, ctx->d_ranks, ctx->d_flags + 2, D.fneed));
+      HIP_TRY(ctx, launch_pinf_walk(bs, P, Lv, D, start, ranks, walk_flags, D.fneed));
       ev_end(ctx, 1, 1, bs);
     } else {
       ev_begin(ctx, 1, "k_pinf_walk", bs);
-      HIP_TRY(ctx, launch_pinf_walk(bs, P, Lv, D, ctx->d_start, ctx->d_ranks, ctx->d_flags + 2, nullptr));
+      HIP_TRY(ctx, launch_pinf_walk(bs, P, Lv, D, start, ranks, walk_flags, nullptr));
       ev_end(ctx, 1, 1, bs);
     }
   }
-  HIP_TRY(ctx, launch_expand(bs, P, Lv, ctx->d_start, ctx->d_ranks, d_u_out, d_phi_star, d_status));
+  HIP_TRY(ctx, launch_expand(bs, P, Lv, start, ranks, d_u_out, d_phi_star, d_status));
   if (async_bt) {
     HIP_TRY(ctx, hipEventRecord(ctx->ev_bt[ctx->slot], bs));
     ctx->bt_rec[ctx->slot] = true;
@@ -688,12 +648,9 @@ int run_backtrack(mioc_ctx *ctx, int64_t B_use, double *d_u_out, double *d_phi_s
 int check_run(mioc_ctx *ctx) {
   if (!ctx->run_pending) return MIOC_OK;
   ctx->run_pending = false;
-  if (ctx->h_run_err && *ctx->h_run_err) {
+  if (ctx->h_run_err[0]) {
     ctx->have_dp = false;
-    ctx->n_persist_fallbacks += 1;
-    ctx->force_steps = true;
-    const int rc = run_bellman(ctx);
-    ctx->force_steps = false;
+    const int rc = redo_unsegmented(ctx);
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
@@ -708,7 +665,7 @@ int check_ready(mioc_ctx *ctx) {
   return MIOC_OK;
 }
 
-// The argument checks of a bellman call.  They run before begin_dp swaps the DP slot, so that a call rejected here
+// The argument checks of a bellman call.  They run before begin_dp flips the DP slot, so that a call rejected here
 // changes nothing: the previous DP, its inputs and its backtrack result stay readable (include/mioc.h, mioc_bellman).
 int check_problem(mioc_ctx *ctx, int64_t K, int64_t nx, int64_t nt, int64_t B, double dt) {
   if (nx != ctx->M) return fail(ctx, MIOC_EINVAL, "nx does not match the number of controls in the level table");
@@ -730,13 +687,10 @@ int set_problem(mioc_ctx *ctx, int64_t K, int64_t nx, int64_t nt, int64_t B, dou
   ctx->have_dp = false;
   ctx->have_path = false;
   ctx->run_pending = false;  // a superseded DP's timeout word concerns nobody (run_bellman arms it again)
-  size_t need = (size_t)K * nx * nt * sizeof(double);
-  size_t cap = ctx->in_cap, cap2 = ctx->in_cap;
-  int rc = grow(ctx, &ctx->d_df, &cap, need, "df copy");
-  if (!rc) rc = grow(ctx, &ctx->d_uold, &cap2, need, "u_old copy");
-  if (rc) return rc;
-  ctx->in_cap = std::min(cap, cap2);
-  return MIOC_OK;
+  const size_t need = (size_t)K * nx * nt * sizeof(double);
+  int rc = ctx->cur().df.grow(ctx, need, "df copy");
+  if (!rc) rc = ctx->cur().uold.grow(ctx, need, "u_old copy");
+  return rc;
 }
 
 }  // namespace
@@ -748,11 +702,6 @@ int mioc::join_bt(mioc_ctx *ctx) {
   if (hipStreamWaitEvent(ctx->stream, ctx->ev_bt[ctx->bt_last], 0) != hipSuccess)
     return fail(ctx, MIOC_EHIP, "hipStreamWaitEvent failed");
   return MIOC_OK;
-}
-
-// the forward-state scratch shared by mioc_ode_eval_device and mioc_ode_program_eval_device (mioc_ode_rtc.cpp)
-int mioc::grow_ode_state(mioc_ctx *ctx, size_t need_bytes) {
-  return grow(ctx, &ctx->d_ode_state, &ctx->ode_cap, need_bytes, "ODE states");
 }
 
 // ==================================================================================================
@@ -778,7 +727,11 @@ int32_t mioc_create(int32_t device, mioc_ctx **out) {
       hipEventCreateWithFlags(&ctx->ev_dp, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->ev_bt[0], hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->ev_bt[1], hipEventDisableTiming) != hipSuccess ||
-      hipMalloc(&ctx->d_flags, 16) != hipSuccess || hipMalloc(&ctx->d_pred_own, 64) != hipSuccess || hipHostMalloc(&ctx->h_flags, 16, 0) != hipSuccess) {
+      hipDeviceGetAttribute(&ctx->ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
+      hipDeviceGetAttribute(&ctx->cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) != hipSuccess ||
+      hipDeviceGetAttribute(&ctx->wg_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess ||
+      !ctx->d_flags.alloc(16) || !ctx->d_pred_own.alloc(64) || !ctx->h_flags.alloc() || !ctx->h_run_err.alloc() ||
+      !ctx->h_trm_poll.alloc()) {
     free_all(ctx);
     delete ctx;
     return MIOC_EHIP;
@@ -800,42 +753,30 @@ const char *mioc_last_error(const mioc_ctx *ctx) { return ctx ? ctx->err.c_str()
 
 int32_t mioc_set_option(mioc_ctx *ctx, int32_t option, int64_t value) {
   if (!ctx) return MIOC_EINVAL;
-  if (option == MIOC_OPT_ALGO) {
-    if (value < MIOC_ALGO_AUTO || value > MIOC_ALGO_FUSED_SEPARABLE) return fail(ctx, MIOC_EINVAL, "unknown algorithm");
-    ctx->opt_algo = value;
-    return MIOC_OK;
-  }
-  if (option == MIOC_OPT_TIMING) {
-    ctx->timing = value != 0;
-    return MIOC_OK;
-  }
-  if (option == MIOC_OPT_PERSIST) {
-    ctx->opt_persist = value != 0;
-    return MIOC_OK;
-  }
-  if (option == MIOC_OPT_PRED_FMA) {
-    ctx->pred_fma = value != 0;
-    return MIOC_OK;
-  }
-  if (option == MIOC_OPT_SPIN_LIMIT) {
-    if (value < 1 || value > (1ll << 30)) return fail(ctx, MIOC_EINVAL, "spin limit must be in [1, 2^30]");
-    ctx->spin_limit = (unsigned)value;
-    return MIOC_OK;
-  }
-  if (option == MIOC_OPT_SDT_BUFFERS) {
-    if (value < 4 || value > kSdtMaxBuffers) return fail(ctx, MIOC_EINVAL, "staging buffers must be in [4, 256]");
-    ctx->opt_nb = (int)value;
-    return MIOC_OK;
-  }
-  if (option == MIOC_OPT_PINF_WALK) {
-    if (value < -1 || value > 1) return fail(ctx, MIOC_EINVAL, "p=Inf walk option must be -1, 0 or 1");
-    ctx->opt_pinf_walk = (int)value;
-    return MIOC_OK;
-  }
-  if (option == MIOC_OPT_FSEP_SEGMENTS) {
-    if (value < -1 || value > 8) return fail(ctx, MIOC_EINVAL, "fused separable segments must be in [-1, 8]");
-    ctx->opt_fsep_seg = (int)value;
-    return MIOC_OK;
+  switch (option) {
+    case MIOC_OPT_ALGO:
+      if (value < MIOC_ALGO_AUTO || value > MIOC_ALGO_FUSED_SEPARABLE) return fail(ctx, MIOC_EINVAL, "unknown algorithm");
+      ctx->opt_algo = value;
+      return MIOC_OK;
+    case MIOC_OPT_TIMING: ctx->timing = value != 0; return MIOC_OK;
+    case MIOC_OPT_PERSIST: ctx->opt_persist = value != 0; return MIOC_OK;
+    case MIOC_OPT_PRED_FMA: ctx->pred_fma = value != 0; return MIOC_OK;
+    case MIOC_OPT_SPIN_LIMIT:
+      if (value < 1 || value > (1ll << 30)) return fail(ctx, MIOC_EINVAL, "spin limit must be in [1, 2^30]");
+      ctx->spin_limit = (unsigned)value;
+      return MIOC_OK;
+    case MIOC_OPT_SDT_BUFFERS:
+      if (value < 4 || value > kSdtMaxBuffers) return fail(ctx, MIOC_EINVAL, "staging buffers must be in [4, 256]");
+      ctx->opt_nb = (int)value;
+      return MIOC_OK;
+    case MIOC_OPT_PINF_WALK:
+      if (value < -1 || value > 1) return fail(ctx, MIOC_EINVAL, "p=Inf walk option must be -1, 0 or 1");
+      ctx->opt_pinf_walk = (int)value;
+      return MIOC_OK;
+    case MIOC_OPT_FSEP_SEGMENTS:
+      if (value < -1 || value > 8) return fail(ctx, MIOC_EINVAL, "fused separable segments must be in [-1, 8]");
+      ctx->opt_fsep_seg = (int)value;
+      return MIOC_OK;
   }
   return fail(ctx, MIOC_EINVAL, "unknown option");
 }
@@ -888,13 +829,6 @@ int32_t mioc_set_levels(mioc_ctx *ctx, int64_t M, const int64_t *counts, const i
     ctx->numax_h[m] = (double)hi;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  size_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;
-  void *olds[] = {ctx->d_nuval, ctx->d_nuint, ctx->d_gidx, ctx->d_numin, ctx->d_numax,
-                  ctx->d_vals,  ctx->d_voff,  ctx->d_g2r};
-  for (void *p : olds)
-    if (p) hipFree(p);
-  ctx->d_nuval = nullptr, ctx->d_nuint = nullptr, ctx->d_gidx = nullptr, ctx->d_numin = nullptr, ctx->d_numax = nullptr;
-  ctx->d_vals = nullptr, ctx->d_voff = nullptr, ctx->d_g2r = nullptr;
   // grid tuple -> rank, for the backtrack's guess "the level equal to u_old" (only where it is small)
   const bool want_g2r = Lgrid <= ((int64_t)1 << 22);
   std::vector<int32_t> vals32(off[M]), voff32(M + 1), g2r;
@@ -904,25 +838,25 @@ int32_t mioc_set_levels(mioc_ctx *ctx, int64_t M, const int64_t *counts, const i
     g2r.assign(Lgrid, -1);
     for (int64_t r = L - 1; r >= 0; --r) g2r[gidx[r]] = (int32_t)r;
   }
-  size_t c5 = 0, c6 = 0, c7 = 0;
-  int rc = grow(ctx, &ctx->d_nuval, &c0, L * M * sizeof(double), "levels");
-  if (!rc) rc = grow(ctx, &ctx->d_nuint, &c1, L * M * sizeof(int32_t), "levels");
-  if (!rc) rc = grow(ctx, &ctx->d_gidx, &c2, L * sizeof(int32_t), "levels");
-  if (!rc) rc = grow(ctx, &ctx->d_numin, &c3, M * sizeof(double), "levels");
-  if (!rc) rc = grow(ctx, &ctx->d_numax, &c4, M * sizeof(double), "levels");
-  if (!rc) rc = grow(ctx, &ctx->d_vals, &c5, off[M] * sizeof(int32_t), "levels");
-  if (!rc) rc = grow(ctx, &ctx->d_voff, &c6, (M + 1) * sizeof(int32_t), "levels");
-  if (!rc && want_g2r) rc = grow(ctx, &ctx->d_g2r, &c7, Lgrid * sizeof(int32_t), "levels");
+  int rc = ctx->d_nuval.grow(ctx, L * M * sizeof(double), "levels");
+  if (!rc) rc = ctx->d_nuint.grow(ctx, L * M * sizeof(int32_t), "levels");
+  if (!rc) rc = ctx->d_gidx.grow(ctx, L * sizeof(int32_t), "levels");
+  if (!rc) rc = ctx->d_numin.grow(ctx, M * sizeof(double), "levels");
+  if (!rc) rc = ctx->d_numax.grow(ctx, M * sizeof(double), "levels");
+  if (!rc) rc = ctx->d_vals.grow(ctx, off[M] * sizeof(int32_t), "levels");
+  if (!rc) rc = ctx->d_voff.grow(ctx, (M + 1) * sizeof(int32_t), "levels");
+  ctx->d_g2r.reset();  // (a grid too large for the lookup: a null pointer)
+  if (!rc && want_g2r) rc = ctx->d_g2r.grow(ctx, Lgrid * sizeof(int32_t), "levels");
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy(ctx->d_vals, vals32.data(), off[M] * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_voff, voff32.data(), (M + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->d_vals.get(), vals32.data(), off[M] * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->d_voff.get(), voff32.data(), (M + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
   if (want_g2r)
-    HIP_TRY(ctx, hipMemcpy(ctx->d_g2r, g2r.data(), Lgrid * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_nuval, ctx->nuval_h.data(), L * M * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_nuint, nuint.data(), L * M * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_gidx, gidx.data(), L * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_numin, ctx->numin_h.data(), M * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_numax, ctx->numax_h.data(), M * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_g2r.get(), g2r.data(), Lgrid * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->d_nuval.get(), ctx->nuval_h.data(), L * M * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->d_nuint.get(), nuint.data(), L * M * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->d_gidx.get(), gidx.data(), L * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->d_numin.get(), ctx->numin_h.data(), M * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->d_numax.get(), ctx->numax_h.data(), M * sizeof(double), hipMemcpyHostToDevice));
   // pyramid domain: product iterator in grid order, consecutive integer levels, dim 0 <= 8 levels
   {
     // a product grid of consecutive integer levels in iterator (grid) order
@@ -987,8 +921,8 @@ int32_t mioc_bellman_batch_device(mioc_ctx *ctx, int64_t K, const double *d_df, 
   rc = set_problem(ctx, K, nx, nt, B, dt);
   if (rc) return rc;
   const size_t bytes = (size_t)K * nx * nt * sizeof(double);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_df, d_df, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_uold, d_u_old, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->cur().df.get(), d_df, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->cur().uold.get(), d_u_old, bytes, hipMemcpyDeviceToDevice, ctx->stream));
   return run_bellman(ctx);
 }
 
@@ -1004,8 +938,8 @@ int32_t mioc_bellman(mioc_ctx *ctx, const double *df, const double *u_old, int64
   rc = set_problem(ctx, 1, nx, nt, B, dt);
   if (rc) return rc;
   const size_t bytes = (size_t)nx * nt * sizeof(double);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_df, df, bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_uold, u_old, bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->cur().df.get(), df, bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->cur().uold.get(), u_old, bytes, hipMemcpyHostToDevice, ctx->stream));
   rc = run_bellman(ctx);
   if (rc) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1047,19 +981,18 @@ int32_t mioc_backtrack(mioc_ctx *ctx, int64_t B_use, double *u_out, double *phi_
   if (!ctx->have_dp) return fail(ctx, MIOC_ESTATE, "backtrack called before bellman");
   if (ctx->K != 1) return fail(ctx, MIOC_ESTATE, "host backtrack after a batched bellman: use the batch API");
   const size_t n = (size_t)ctx->M * ctx->nt;
-  size_t c1 = 0, c2 = 0;
-  rc = grow(ctx, &ctx->d_uout_own, &ctx->uout_cap, n * sizeof(double), "u staging");
-  if (!rc && !ctx->d_phistar_own) rc = grow(ctx, &ctx->d_phistar_own, &c1, 16, "phi staging");
-  if (!rc && !ctx->d_status_own) rc = grow(ctx, &ctx->d_status_own, &c2, 16, "status staging");
+  rc = ctx->d_uout_own.grow(ctx, n * sizeof(double), "u staging");
+  if (!rc) rc = ctx->d_phistar_own.grow(ctx, 16, "phi staging");
+  if (!rc) rc = ctx->d_status_own.grow(ctx, 16, "status staging");
   if (rc) return rc;
-  rc = run_backtrack(ctx, B_use, ctx->d_uout_own, ctx->d_phistar_own, ctx->d_status_own);
+  rc = run_backtrack(ctx, B_use, ctx->d_uout_own.get(), ctx->d_phistar_own.get(), ctx->d_status_own.get());
   if (!rc) rc = join_bt(ctx);  // the copies below run on the context's stream
   if (rc) return rc;
   double ps = 0.0;
   int32_t st = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(u_out, ctx->d_uout_own, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(&ps, ctx->d_phistar_own, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(&st, ctx->d_status_own, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(u_out, ctx->d_uout_own.get(), n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&ps, ctx->d_phistar_own.get(), sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&st, ctx->d_status_own.get(), sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ev_collect(ctx);
   if (phi_star) *phi_star = ps;
@@ -1088,30 +1021,27 @@ static int32_t batch_host(mioc_ctx *ctx, int64_t K, const double *df, const doub
   rc = set_problem(ctx, K, nx, nt, B, dt);
   if (rc) return rc;
   const size_t n = (size_t)K * nx * nt;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_df, df, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_uold, u_old, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->cur().df.get(), df, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->cur().uold.get(), u_old, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   rc = run_bellman(ctx);
   if (rc) return rc;
-  double *d_u = nullptr, *d_phi = nullptr;
-  int32_t *d_st = nullptr;
-  size_t c0 = 0, c1 = 0, c2 = 0;
-  rc = grow(ctx, &d_u, &c0, n * sizeof(double), "multi-device u staging");
-  if (!rc) rc = grow(ctx, &d_phi, &c1, (size_t)K * sizeof(double), "multi-device phi staging");
-  if (!rc) rc = grow(ctx, &d_st, &c2, (size_t)K * sizeof(int32_t), "multi-device status staging");
-  if (!rc) rc = run_backtrack(ctx, B_use, d_u, d_phi, d_st);
+  DevBuf<double> d_u, d_phi;
+  DevBuf<int32_t> d_st;
+  rc = d_u.grow(ctx, n * sizeof(double), "multi-device u staging");
+  if (!rc) rc = d_phi.grow(ctx, (size_t)K * sizeof(double), "multi-device phi staging");
+  if (!rc) rc = d_st.grow(ctx, (size_t)K * sizeof(int32_t), "multi-device status staging");
+  if (!rc) rc = run_backtrack(ctx, B_use, d_u.get(), d_phi.get(), d_st.get());
   if (!rc) rc = join_bt(ctx);  // the copies below run on the context's stream
-  if (!rc && hipMemcpyAsync(u_out, d_u, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+  if (!rc && hipMemcpyAsync(u_out, d_u.get(), n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
     rc = fail(ctx, MIOC_EHIP, "u copy-out failed");
   if (!rc && phi_star &&
-      hipMemcpyAsync(phi_star, d_phi, K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+      hipMemcpyAsync(phi_star, d_phi.get(), K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
     rc = fail(ctx, MIOC_EHIP, "phi copy-out failed");
   if (!rc && status &&
-      hipMemcpyAsync(status, d_st, K * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+      hipMemcpyAsync(status, d_st.get(), K * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
     rc = fail(ctx, MIOC_EHIP, "status copy-out failed");
   if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) rc = fail(ctx, MIOC_EHIP, "hipStreamSynchronize failed");
   if (!rc) rc = check_run(ctx);
-  for (void *p : {(void *)d_u, (void *)d_phi, (void *)d_st})
-    if (p) hipFree(p);
   ev_collect(ctx);
   return rc;
 }
@@ -1135,12 +1065,12 @@ int32_t mioc_ode_eval_device(mioc_ctx *ctx, int32_t problem, int64_t K, const do
   for (int q = 0; q < np; ++q) par[q] = params ? params[q] : def[q];
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   {  // k_ode_eval stores every restart's forward states, J-only calls included
-    int rc = grow(ctx, &ctx->d_ode_state, &ctx->ode_cap, (size_t)K * nt * 2 * sizeof(double), "ODE states");
+    int rc = ctx->d_ode_state.grow(ctx, (size_t)K * nt * 2 * sizeof(double), "ODE states");
     if (rc) return rc;
   }
   const double tau = (T1 - T0) / (double)nt;  // ODEObjective.jl: τ = (T1 - T0) / nt
   HIP_TRY(ctx, launch_ode_eval(ctx->stream, ctx->gate, problem, (int)K, (int)nt, tau, par, np - 2, d_x, d_J, d_df,
-                               ctx->d_ode_state));
+                               ctx->d_ode_state.get()));
   return MIOC_OK;
 }
 
@@ -1217,7 +1147,7 @@ int32_t mioc_get_ranks_device(mioc_ctx *ctx, int32_t *d_ranks_out) {
   MIOC_JOIN_BT(ctx);
   if (!ctx->have_path) return fail(ctx, MIOC_ESTATE, "no backtrack result to read");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpyAsync(d_ranks_out, ctx->d_ranks, (size_t)ctx->K * ctx->nt * sizeof(int32_t),
+  HIP_TRY(ctx, hipMemcpyAsync(d_ranks_out, ctx->d_ranks.get(), (size_t)ctx->K * ctx->nt * sizeof(int32_t),
                               hipMemcpyDeviceToDevice, ctx->stream));
   return MIOC_OK;
 }
@@ -1239,16 +1169,16 @@ TrmDev trm_dev(const mioc_ctx *ctx, int mode, int64_t K, int64_t nt) {
   T.mode = mode;
   T.gate = ctx->gate;
   T.fma = ctx->pred_fma ? 1 : 0;
-  T.df = ctx->d_df;
-  T.uold = ctx->d_uold;
-  T.ranks = ctx->d_ranks;
-  T.nuval = ctx->d_nuval;
-  T.vals = ctx->d_vals;
-  T.voff = ctx->d_voff;
-  T.g2r = ctx->d_g2r;
-  T.tvw = ctx->d_tvw;
+  T.df = ctx->cur().df.get();
+  T.uold = ctx->cur().uold.get();
+  T.ranks = ctx->d_ranks.get();
+  T.nuval = ctx->d_nuval.get();
+  T.vals = ctx->d_vals.get();
+  T.voff = ctx->d_voff.get();
+  T.g2r = ctx->d_g2r.get();
+  T.tvw = ctx->d_tvw.get();
   T.tvw_len = ctx->tvw_len;
-  T.err = reinterpret_cast<int32_t *>(ctx->d_pred_own + 4);
+  T.err = reinterpret_cast<int32_t *>(ctx->d_pred_own.get() + 4);
   return T;
 }
 
@@ -1256,7 +1186,7 @@ int trm_ready(mioc_ctx *ctx) {
   if (!ctx) return MIOC_EINVAL;
   MIOC_JOIN_BT(ctx);
   if (!ctx->have_levels || !ctx->have_cost) return fail(ctx, MIOC_ESTATE, "levels and cost must be set first");
-  if (ctx->p_kind == MIOC_P_TABLE && !ctx->d_g2r)
+  if (ctx->p_kind == MIOC_P_TABLE && !ctx->d_g2r.get())
     return fail(ctx, MIOC_EINVAL, "TV_p with MIOC_P_TABLE needs the level grid lookup (grid too large)");
   if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, MIOC_EHIP, "hipSetDevice failed");
   return MIOC_OK;
@@ -1264,7 +1194,7 @@ int trm_ready(mioc_ctx *ctx) {
 
 int trm_check_err(mioc_ctx *ctx) {
   int32_t e = 0;
-  HIP_TRY(ctx, hipMemcpy(&e, ctx->d_pred_own + 4, sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(&e, ctx->d_pred_own.get() + 4, sizeof(int32_t), hipMemcpyDeviceToHost));
   if (e) return fail(ctx, MIOC_EINVAL, "TV_p: a control difference is outside the weight table (MIOC_P_INTLUT key "
                                        "beyond table_len, or MIOC_P_TABLE control off the level grid)");
   return MIOC_OK;
@@ -1276,10 +1206,10 @@ int trm_check_err(mioc_ctx *ctx) {
 int32_t mioc_pred(mioc_ctx *ctx, double *int_val, double *tv_old, double *tv_new, double *pred) {
   int rc = trm_ready(ctx);
   if (rc) return rc;
-  if (!ctx->have_path || !ctx->d_df || !ctx->d_uold || !ctx->d_ranks)
+  if (!ctx->have_path)
     return fail(ctx, MIOC_ESTATE, "pred needs a backtrack result (mioc_backtrack first)");
   if (ctx->K != 1) return fail(ctx, MIOC_ESTATE, "host pred after a batched bellman: use mioc_pred_batch_device");
-  double *o = ctx->d_pred_own;
+  double *o = ctx->d_pred_own.get();
   TrmDev T = trm_dev(ctx, 7, 1, ctx->nt);
   T.out_int = o, T.out_told = o + 1, T.out_tnew = o + 2, T.out_pred = o + 3;
   if (!ctx->trm_pending) HIP_TRY(ctx, hipMemsetAsync(o + 4, 0, sizeof(double), ctx->stream));
@@ -1301,13 +1231,13 @@ int32_t mioc_pred(mioc_ctx *ctx, double *int_val, double *tv_old, double *tv_new
 int32_t mioc_pred_batch_device(mioc_ctx *ctx, double *d_int_val, double *d_tv_old, double *d_tv_new, double *d_pred) {
   int rc = trm_ready(ctx);
   if (rc) return rc;
-  if (!ctx->have_path || !ctx->d_df || !ctx->d_uold || !ctx->d_ranks)
+  if (!ctx->have_path)
     return fail(ctx, MIOC_ESTATE, "pred needs a backtrack result");
   TrmDev T = trm_dev(ctx, 7, ctx->K, ctx->nt);
   T.out_int = d_int_val, T.out_told = d_tv_old, T.out_tnew = d_tv_new, T.out_pred = d_pred;
   // the error flag is cleared by the first enqueue after a check only: an error of an earlier, not yet synchronised
   // TV / pred call stays visible to the next mioc_synchronize
-  if (!ctx->trm_pending) HIP_TRY(ctx, hipMemsetAsync(ctx->d_pred_own + 4, 0, sizeof(double), ctx->stream));
+  if (!ctx->trm_pending) HIP_TRY(ctx, hipMemsetAsync(ctx->d_pred_own.get() + 4, 0, sizeof(double), ctx->stream));
   HIP_TRY(ctx, launch_trm_pred(ctx->stream, T));
   ctx->trm_pending = true;
   return MIOC_OK;
@@ -1324,7 +1254,7 @@ int32_t mioc_tv_device(mioc_ctx *ctx, int64_t K, const double *d_u, int64_t nx, 
   T.out_tnew = d_tv;
   // the error flag is cleared by the first enqueue after a check only: an error of an earlier, not yet synchronised
   // TV / pred call stays visible to the next mioc_synchronize
-  if (!ctx->trm_pending) HIP_TRY(ctx, hipMemsetAsync(ctx->d_pred_own + 4, 0, sizeof(double), ctx->stream));
+  if (!ctx->trm_pending) HIP_TRY(ctx, hipMemsetAsync(ctx->d_pred_own.get() + 4, 0, sizeof(double), ctx->stream));
   HIP_TRY(ctx, launch_trm_pred(ctx->stream, T));
   ctx->trm_pending = true;
   return MIOC_OK;
@@ -1387,8 +1317,7 @@ int32_t mioc_trm_poll(mioc_ctx *ctx, const void *d_state, int32_t *out) {
   if (!ctx || !d_state || !out) return MIOC_EINVAL;
   MIOC_JOIN_BT(ctx);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!ctx->h_trm_poll) HIP_TRY(ctx, hipHostMalloc(&ctx->h_trm_poll, 16, 0));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_trm_poll, d_state, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_trm_poll.get(), d_state, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   out[0] = ctx->h_trm_poll[0];
   out[1] = ctx->h_trm_poll[1];
@@ -1411,7 +1340,7 @@ int32_t mioc_reset_stats(mioc_ctx *ctx) {
   return MIOC_OK;
 }
 
-int32_t mioc_last_algo(mioc_ctx *ctx) { return ctx ? ctx->algo : MIOC_EINVAL; }
+int32_t mioc_last_algo(mioc_ctx *ctx) { return ctx ? ctx->lay.algo : MIOC_EINVAL; }
 
 int32_t mioc_diagnostics(mioc_ctx *ctx, int64_t *counters, int32_t n) {
   if (!ctx || !counters || n < 0) return MIOC_EINVAL;
@@ -1419,22 +1348,23 @@ int32_t mioc_diagnostics(mioc_ctx *ctx, int64_t *counters, int32_t n) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0}, f[4] = {0, 0, 0, 0};
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->d_counters) HIP_TRY(ctx, hipMemcpy(c, ctx->d_counters, sizeof c, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(f, ctx->d_flags, sizeof f, hipMemcpyDeviceToHost));
+  if (ctx->d_counters.get()) HIP_TRY(ctx, hipMemcpy(c, ctx->d_counters.get(), sizeof c, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(f, ctx->d_flags.get(), sizeof f, hipMemcpyDeviceToHost));
   // slot 6: the separable transform's persistent DPs redone with per-step launches (cooperative launch refused or a
   // dependency wait timed out) -- its kernels write no c[6]; the pyramid's value-collision count otherwise
   // slot 8: row segments per subproblem of the last fused separable DP (0: the one-lane-per-row kernel)
   // (p = Inf: plus the device-side redo of the last DP, counted by the gated one-workgroup recursion in c[6])
-  const int64_t c6 = ctx->algo == MIOC_ALGO_SEPARABLE || ctx->algo == MIOC_ALGO_FUSED_SEPARABLE
+  const int algo = ctx->lay.algo;
+  const int64_t c6 = algo == MIOC_ALGO_SEPARABLE || algo == MIOC_ALGO_FUSED_SEPARABLE
                          ? ctx->n_persist_fallbacks
-                         : ctx->algo == MIOC_ALGO_PINF ? ctx->n_persist_fallbacks + c[6] : c[6];
+                         : algo == MIOC_ALGO_PINF ? ctx->n_persist_fallbacks + c[6] : c[6];
   // slot 9: after a p=Inf segmented walk, its subproblems left to the serial walk (-1: the serial walk ran alone)
   int32_t fserial = -1;
-  if (ctx->algo == MIOC_ALGO_PINF && ctx->last_pinf_fwalk && ctx->pinf.fneed)
-    HIP_TRY(ctx, hipMemcpy(&fserial, ctx->pinf.fneed + ctx->K, sizeof fserial, hipMemcpyDeviceToHost));
+  if (algo == MIOC_ALGO_PINF && ctx->last_pinf_fwalk && ctx->d_fneed.get())
+    HIP_TRY(ctx, hipMemcpy(&fserial, ctx->d_fneed.get() + ctx->K, sizeof fserial, hipMemcpyDeviceToHost));
   // slot 3: internal-consistency failures of the backtrack (f[3]) and of the DP's tables (c[3]: seam-list overflow)
   const int64_t all[10] = {c[0], c[1], f[2], (int64_t)f[3] + c[3], c[4], c[5], c6, ctx->occupancy,
-                           ctx->algo == MIOC_ALGO_FUSED_SEPARABLE ? ctx->last_fsep_seg : 0, fserial};
+                           algo == MIOC_ALGO_FUSED_SEPARABLE ? ctx->last_fsep_seg : 0, fserial};
   for (int32_t q = 0; q < n && q < 10; ++q) counters[q] = all[q];
   return MIOC_OK;
 }
@@ -1445,7 +1375,7 @@ int32_t mioc_get_argmin_table(mioc_ctx *ctx, int64_t k, int64_t step, int32_t *U
   if (!ctx->have_dp) return fail(ctx, MIOC_ESTATE, "no bellman result to read");
   if (k < 0 || k >= ctx->K || step < 0 || step + 1 >= ctx->nt)
     return fail(ctx, MIOC_EINVAL, "subproblem or step out of range (0 <= step < nt-1)");
-  if (ctx->algo == MIOC_ALGO_PINF)
+  if (ctx->lay.algo == MIOC_ALGO_PINF)
     return fail(ctx, MIOC_EINVAL, "the p=Inf collapse keeps per-budget class tables, not U");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1455,7 +1385,7 @@ int32_t mioc_get_argmin_table(mioc_ctx *ctx, int64_t k, int64_t step, int32_t *U
   }
   const int64_t R = ctx->B + 1, L = ctx->L, M = ctx->M, nt = ctx->nt;
   std::vector<double> uo(M);
-  HIP_TRY(ctx, hipMemcpy(uo.data(), ctx->d_uold + ((size_t)k * nt + step) * M, M * sizeof(double),
+  HIP_TRY(ctx, hipMemcpy(uo.data(), ctx->cur().uold.get() + ((size_t)k * nt + step) * M, M * sizeof(double),
                          hipMemcpyDeviceToHost));
   std::vector<int32_t> out((size_t)R * ctx->Lgrid, -1);
   auto bt = [&](int64_t r) {
@@ -1463,11 +1393,11 @@ int32_t mioc_get_argmin_table(mioc_ctx *ctx, int64_t k, int64_t step, int32_t *U
     for (int64_t m = 0; m < M; ++m) b += (int64_t)std::fabs(ctx->nuval_h[r * M + m] - uo[m]);
     return b;
   };
-  const size_t step_cells = (size_t)R * L;
-  if (ctx->algo == MIOC_ALGO_PYRAMID || ctx->algo == MIOC_ALGO_SEPARABLE) {  // staged: UU_i[c'][l] = U_i[l, c' + b̃_l(i)]
-    std::vector<uint16_t> uu(step_cells);
-    const uint16_t *src = (const uint16_t *)ctx->d_U + ((size_t)k * (nt - 1) + step) * step_cells;
-    HIP_TRY(ctx, hipMemcpy(uu.data(), src, step_cells * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  const DpLayout &Y = ctx->lay;  // (after check_run: a redone DP has its own layout)
+  if (Y.algo == MIOC_ALGO_PYRAMID || Y.algo == MIOC_ALGO_SEPARABLE) {  // staged: UU_i[c'][l] = U_i[l, c' + b̃_l(i)]
+    std::vector<uint16_t> uu(Y.s_stride);
+    const uint16_t *src = (const uint16_t *)ctx->d_U.get() + (size_t)k * Y.uu_stride_k + (size_t)step * Y.s_stride;
+    HIP_TRY(ctx, hipMemcpy(uu.data(), src, Y.s_stride * sizeof(uint16_t), hipMemcpyDeviceToHost));
     for (int64_t r = 0; r < L; ++r) {
       const int64_t b = bt(r);
       for (int64_t c = b; c < R; ++c) {  // 0xFFFF: a cell the separable transform left unwritten (Φ = +Inf)
@@ -1476,15 +1406,15 @@ int32_t mioc_get_argmin_table(mioc_ctx *ctx, int64_t k, int64_t step, int32_t *U
       }
     }
   } else {  // generic: U_i[l][c]
-    std::vector<unsigned char> raw(step_cells * ctx->ubytes);
-    const unsigned char *src = (const unsigned char *)ctx->d_U + ((size_t)k * (nt - 1) + step) * step_cells * ctx->ubytes;
+    std::vector<unsigned char> raw(Y.s_stride * Y.ubytes);
+    const unsigned char *src = ctx->d_U.get() + ((size_t)k * Y.u_stride_k + (size_t)step * Y.s_stride) * Y.ubytes;
     HIP_TRY(ctx, hipMemcpy(raw.data(), src, raw.size(), hipMemcpyDeviceToHost));
     for (int64_t r = 0; r < L; ++r) {
       const int64_t b = bt(r);
       for (int64_t c = b; c < R; ++c) {
         const size_t q = (size_t)r * R + c;
         out[c + R * ctx->gidx_h[r]] =
-            ctx->ubytes == 1 ? (int32_t)raw[q] : (int32_t)reinterpret_cast<const uint16_t *>(raw.data())[q];
+            Y.ubytes == 1 ? (int32_t)raw[q] : (int32_t)reinterpret_cast<const uint16_t *>(raw.data())[q];
       }
     }
   }

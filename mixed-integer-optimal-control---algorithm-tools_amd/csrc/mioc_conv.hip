@@ -43,20 +43,13 @@ struct ConvState {
   bool ready = false;  // kappa / fvec on the device match nt (false after a failed setup)
   int64_t nt = 0;
   double tau = 0.0;
-  double *d_kappa = nullptr;  // [nt]
-  double *d_fvec = nullptr;   // [nt + 1]
-  double *d_v = nullptr;      // [K][nt + 1] v = K·xᵀ − fvec, then [K][nt + 16] w = M·v, between the launches
-  size_t v_cap = 0;
-  double *d_io = nullptr;     // host entry staging: x, df, J
-  size_t io_cap = 0;
+  DevBuf<double> d_kappa;  // [nt]
+  DevBuf<double> d_fvec;   // [nt + 1]
+  DevBuf<double> d_v;      // [K][nt + 1] v = K·xᵀ − fvec, then [K][nt + 16] w = M·v, between the launches
+  DevBuf<double> d_io;     // host entry staging: x, df, J
 };
 
-void conv_free(ConvState *c) {
-  if (!c) return;
-  for (double *p : {c->d_kappa, c->d_fvec, c->d_v, c->d_io})
-    if (p) hipFree(p);
-  delete c;
-}
+void conv_free(ConvState *c) { delete c; }
 
 namespace {
 
@@ -276,28 +269,11 @@ int conv_fail(mioc_ctx *ctx, int code, const std::string &msg) {
   return code;
 }
 
-int conv_upload(mioc_ctx *ctx, double **dst, const double *src, size_t n, const char *what) {
-  if (*dst) hipFree(*dst), *dst = nullptr;
-  if (hipMalloc(reinterpret_cast<void **>(dst), n * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    *dst = nullptr;
+int conv_upload(mioc_ctx *ctx, DevBuf<double> &dst, const double *src, size_t n, const char *what) {
+  if (!dst.alloc(n * sizeof(double)))
     return conv_fail(ctx, MIOC_ENOMEM, std::string("cannot allocate the convolution ") + what);
-  }
-  if (hipMemcpy(*dst, src, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+  if (hipMemcpy(dst.get(), src, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
     return conv_fail(ctx, MIOC_EHIP, std::string("convolution upload failed: ") + what);
-  return MIOC_OK;
-}
-
-// grows a context-owned device buffer to `need` bytes (contents are not kept)
-int conv_grow(mioc_ctx *ctx, double **buf, size_t *cap, size_t need, const char *what) {
-  if (*cap >= need) return MIOC_OK;
-  if (*buf) hipFree(*buf), *buf = nullptr, *cap = 0;
-  if (hipMalloc(reinterpret_cast<void **>(buf), need) != hipSuccess) {
-    (void)hipGetLastError();
-    *buf = nullptr;
-    return conv_fail(ctx, MIOC_ENOMEM, std::string("convolution: cannot allocate the ") + what);
-  }
-  *cap = need;
   return MIOC_OK;
 }
 
@@ -329,8 +305,8 @@ int32_t mioc_conv_setup(mioc_ctx *ctx, int64_t nt, double T0, double T1, const d
   // evals enqueued earlier may still read the tables that are replaced below
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return conv_fail(ctx, MIOC_EHIP, "hipStreamSynchronize failed");
   int rc;
-  if ((rc = conv_upload(ctx, &c->d_kappa, kappa, (size_t)nt, "kappa")) ||
-      (rc = conv_upload(ctx, &c->d_fvec, fvec, (size_t)nt + 1, "fvec")))
+  if ((rc = conv_upload(ctx, c->d_kappa, kappa, (size_t)nt, "kappa")) ||
+      (rc = conv_upload(ctx, c->d_fvec, fvec, (size_t)nt + 1, "fvec")))
     return rc;
   c->ready = true;
   return MIOC_OK;
@@ -345,12 +321,12 @@ int32_t mioc_conv_eval_device(mioc_ctx *ctx, int64_t K, const double *d_x, doubl
   if (K < 1 || K > INT32_MAX || !d_x || rtiles * gcmax > INT32_MAX)
     return conv_fail(ctx, MIOC_EINVAL, "convolution: bad K / x");
   if (hipSetDevice(ctx->device) != hipSuccess) return conv_fail(ctx, MIOC_EHIP, "hipSetDevice failed");
-  int rc;
   const size_t nv = (size_t)K * (c->nt + 1), nw = d_df ? (size_t)K * (c->nt + 16) : 0;
-  if ((rc = conv_grow(ctx, &c->d_v, &c->v_cap, (nv + nw) * sizeof(double), "v / w scratch"))) return rc;
+  if (c->d_v.bytes() < (nv + nw) * sizeof(double) && !c->d_v.alloc((nv + nw) * sizeof(double)))
+    return conv_fail(ctx, MIOC_ENOMEM, "convolution: cannot allocate the v / w scratch");
   ConvArgs A;
-  A.kappa = c->d_kappa, A.fvec = c->d_fvec, A.X = d_x;
-  A.V = c->d_v, A.W = c->d_v + nv, A.J = d_J, A.DF = d_df;
+  A.kappa = c->d_kappa.get(), A.fvec = c->d_fvec.get(), A.X = d_x;
+  A.V = c->d_v.get(), A.W = c->d_v.get() + nv, A.J = d_J, A.DF = d_df;
   A.K = (int)K, A.nt = (int)c->nt, A.rtiles = (int)rtiles;
   A.md_end = c->tau / 3, A.md_in = 2.0 / 3.0 * c->tau, A.m_off = c->tau / 6;  // example_convolution.jl:89-96
   A.gate = ctx->gate;
@@ -376,12 +352,13 @@ int32_t mioc_conv_eval(mioc_ctx *ctx, int64_t K, const double *x, double *J, dou
   if (K < 1 || K > INT32_MAX || !x || (!J && !df)) return conv_fail(ctx, MIOC_EINVAL, "convolution: bad K / x / outputs");
   if (hipSetDevice(ctx->device) != hipSuccess) return conv_fail(ctx, MIOC_EHIP, "hipSetDevice failed");
   const size_t nxt = (size_t)K * c->nt;
-  int rc;
-  if ((rc = conv_grow(ctx, &c->d_io, &c->io_cap, (2 * nxt + K) * sizeof(double), "host-entry staging"))) return rc;
-  double *dx = c->d_io, *ddf = c->d_io + nxt, *dJ = c->d_io + 2 * nxt;
+  const size_t need = (2 * nxt + K) * sizeof(double);
+  if (c->d_io.bytes() < need && !c->d_io.alloc(need))
+    return conv_fail(ctx, MIOC_ENOMEM, "convolution: cannot allocate the host-entry staging");
+  double *dx = c->d_io.get(), *ddf = dx + nxt, *dJ = dx + 2 * nxt;
   if (hipMemcpyAsync(dx, x, nxt * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
     return conv_fail(ctx, MIOC_EHIP, "convolution: x copy-in failed");
-  rc = mioc_conv_eval_device(ctx, K, dx, J ? dJ : nullptr, df ? ddf : nullptr);
+  const int rc = mioc_conv_eval_device(ctx, K, dx, J ? dJ : nullptr, df ? ddf : nullptr);
   if (rc) return rc;
   if (J && hipMemcpyAsync(J, dJ, K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
     return conv_fail(ctx, MIOC_EHIP, "convolution: J copy-out failed");

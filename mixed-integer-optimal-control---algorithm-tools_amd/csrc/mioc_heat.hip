@@ -34,28 +34,20 @@ struct HeatState {
   bool ready = false;  // every device table matches N / Np / nx / nt (false after a failed setup)
   int64_t N = 0, Np = 0, nx = 0, nt = 0;
   double tau = 0.0, gamma = 0.0;
-  double *d_sinv = nullptr, *d_sinvT = nullptr;                    // A-operand order, [Np/16][Np/8][64] double2
-  double *d_minvF = nullptr;                                        // [Np][nx] row-major, zero-padded
-  double *d_state0 = nullptr;                                       // [Np]
-  double *d_yd = nullptr;                                           // [nt + 1][Np]
-  double *d_gy = nullptr;                                           // [tiles][nt][Np][16] Gy_i between the sweeps
-  size_t gy_cap = 0;
-  double *d_io = nullptr;                                           // host entry staging: x, df, J
-  size_t io_cap = 0;
-  double *d_msinv = nullptr;                                        // M·S⁻¹ in the A-operand order
-  double *d_myd = nullptr;                                          // [nt + 1][Np] M·yd_j
-  double *d_gy0 = nullptr;                                          // [Np] M·(state0 − yd_0)
-  double g0 = 0.0;                                                  // (state0 − yd_0)ᵀ M (state0 − yd_0)
-  double *d_sc = nullptr;                                           // [tiles][2][Np][16] y, z for Np > 512
-  size_t sc_cap = 0;
+  DevBuf<double> d_sinv, d_sinvT;  // A-operand order, [Np/16][Np/8][64] double2
+  DevBuf<double> d_minvF;          // [Np][nx] row-major, zero-padded
+  DevBuf<double> d_state0;         // [Np]
+  DevBuf<double> d_yd;             // [nt + 1][Np]
+  DevBuf<double> d_gy;             // [tiles][nt][Np][16] Gy_i between the sweeps
+  DevBuf<double> d_io;             // host entry staging: x, df, J
+  DevBuf<double> d_msinv;          // M·S⁻¹ in the A-operand order
+  DevBuf<double> d_myd;            // [nt + 1][Np] M·yd_j
+  DevBuf<double> d_gy0;            // [Np] M·(state0 − yd_0)
+  double g0 = 0.0;                 // (state0 − yd_0)ᵀ M (state0 − yd_0)
+  DevBuf<double> d_sc;             // [tiles][2][Np][16] y, z for Np > 512
 };
 
-void heat_free(HeatState *h) {
-  if (!h) return;
-  for (double *p : {h->d_sinv, h->d_sinvT, h->d_minvF, h->d_state0, h->d_yd, h->d_gy, h->d_io, h->d_msinv, h->d_myd, h->d_gy0, h->d_sc})
-    if (p) hipFree(p);
-  delete h;
-}
+void heat_free(HeatState *h) { delete h; }
 
 namespace {
 
@@ -357,14 +349,10 @@ int heat_fail(mioc_ctx *ctx, int code, const std::string &msg) {
   return code;
 }
 
-int upload(mioc_ctx *ctx, double **dst, const std::vector<double> &src, const char *what) {
-  if (*dst) hipFree(*dst), *dst = nullptr;
-  if (hipMalloc(reinterpret_cast<void **>(dst), src.size() * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    *dst = nullptr;
+int upload(mioc_ctx *ctx, DevBuf<double> &dst, const std::vector<double> &src, const char *what) {
+  if (!dst.alloc(src.size() * sizeof(double)))
     return heat_fail(ctx, MIOC_ENOMEM, std::string("cannot allocate the heat ") + what);
-  }
-  if (hipMemcpy(*dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+  if (hipMemcpy(dst.get(), src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
     return heat_fail(ctx, MIOC_EHIP, std::string("heat upload failed: ") + what);
   return MIOC_OK;
 }
@@ -406,10 +394,10 @@ int32_t mioc_heat_setup(mioc_ctx *ctx, int64_t N, int64_t nx, int64_t nt, double
   h->N = N, h->Np = Np, h->nx = nx, h->nt = nt, h->tau = tau, h->gamma = gamma;
   if (hipSetDevice(ctx->device) != hipSuccess) return heat_fail(ctx, MIOC_EHIP, "hipSetDevice failed");
   int rc;
-  if ((rc = upload(ctx, &h->d_sinv, swizzle(N, Np, [&](int64_t r, int64_t c) { return Si[(size_t)c * N + r]; }),
+  if ((rc = upload(ctx, h->d_sinv, swizzle(N, Np, [&](int64_t r, int64_t c) { return Si[(size_t)c * N + r]; }),
                    "S^-1")))
     return rc;
-  if ((rc = upload(ctx, &h->d_sinvT, swizzle(N, Np, [&](int64_t r, int64_t c) { return Si[(size_t)r * N + c]; }),
+  if ((rc = upload(ctx, h->d_sinvT, swizzle(N, Np, [&](int64_t r, int64_t c) { return Si[(size_t)r * N + c]; }),
                    "S^-T")))
     return rc;
   // M·S⁻¹ (column-major), M·yd_j, Gy_0 = M·(state0 − yd_0) and g0 = (state0 − yd_0)ᵀ Gy_0 for the fused step
@@ -433,9 +421,9 @@ int32_t mioc_heat_setup(mioc_ctx *ctx, int64_t N, int64_t nx, int64_t nt, double
   }
   for (int64_t r = 0; r < N; ++r) g0 += (state0[r] - yd[r]) * gy0[r];
   h->g0 = g0;
-  if ((rc = upload(ctx, &h->d_msinv, swizzle(N, Np, [&](int64_t r, int64_t c) { return MS[(size_t)c * N + r]; }),
+  if ((rc = upload(ctx, h->d_msinv, swizzle(N, Np, [&](int64_t r, int64_t c) { return MS[(size_t)c * N + r]; }),
                    "M S^-1")) ||
-      (rc = upload(ctx, &h->d_myd, myd, "M yd")) || (rc = upload(ctx, &h->d_gy0, gy0, "Gy_0")))
+      (rc = upload(ctx, h->d_myd, myd, "M yd")) || (rc = upload(ctx, h->d_gy0, gy0, "Gy_0")))
     return rc;
   std::vector<double> f((size_t)Np * nx, 0.0), y0(Np, 0.0), ydp((size_t)(nt + 1) * Np, 0.0);
   for (int64_t r = 0; r < N; ++r) {
@@ -444,8 +432,8 @@ int32_t mioc_heat_setup(mioc_ctx *ctx, int64_t N, int64_t nx, int64_t nt, double
   }
   for (int64_t j = 0; j <= nt; ++j)
     for (int64_t r = 0; r < N; ++r) ydp[(size_t)j * Np + r] = yd[(size_t)j * N + r];
-  if ((rc = upload(ctx, &h->d_minvF, f, "M_invF")) || (rc = upload(ctx, &h->d_state0, y0, "state0")) ||
-      (rc = upload(ctx, &h->d_yd, ydp, "yd")))
+  if ((rc = upload(ctx, h->d_minvF, f, "M_invF")) || (rc = upload(ctx, h->d_state0, y0, "state0")) ||
+      (rc = upload(ctx, h->d_yd, ydp, "yd")))
     return rc;
   h->ready = true;
   return MIOC_OK;
@@ -460,38 +448,25 @@ int32_t mioc_heat_eval_device(mioc_ctx *ctx, int64_t K, const double *d_x, doubl
   if (hipSetDevice(ctx->device) != hipSuccess) return heat_fail(ctx, MIOC_EHIP, "hipSetDevice failed");
   const int64_t tiles = (K + 15) / 16;
   const size_t need = (size_t)tiles * h->nt * h->Np * 16 * sizeof(double);
-  if (d_df && h->gy_cap < need) {
-    if (h->d_gy) hipFree(h->d_gy), h->d_gy = nullptr, h->gy_cap = 0;
-    if (hipMalloc(reinterpret_cast<void **>(&h->d_gy), need) != hipSuccess) {
-      (void)hipGetLastError();
-      h->d_gy = nullptr;
-      return heat_fail(ctx, MIOC_ENOMEM, "heat: cannot allocate the Gy scratch");
-    }
-    h->gy_cap = need;
-  }
+  if (d_df && h->d_gy.bytes() < need && !h->d_gy.alloc(need))
+    return heat_fail(ctx, MIOC_ENOMEM, "heat: cannot allocate the Gy scratch");
   HeatArgs A;
-  A.sinv = reinterpret_cast<const d2 *>(h->d_sinv);
-  A.sinvT = reinterpret_cast<const d2 *>(h->d_sinvT);
-  A.msinv = reinterpret_cast<const d2 *>(h->d_msinv);
-  A.minvF = h->d_minvF, A.state0 = h->d_state0, A.yd = h->d_yd, A.myd = h->d_myd, A.gy0 = h->d_gy0, A.g0 = h->g0;
+  A.sinv = reinterpret_cast<const d2 *>(h->d_sinv.get());
+  A.sinvT = reinterpret_cast<const d2 *>(h->d_sinvT.get());
+  A.msinv = reinterpret_cast<const d2 *>(h->d_msinv.get());
+  A.minvF = h->d_minvF.get(), A.state0 = h->d_state0.get(), A.yd = h->d_yd.get(), A.myd = h->d_myd.get();
+  A.gy0 = h->d_gy0.get(), A.g0 = h->g0;
   A.X = d_x, A.J = d_J, A.DF = d_df;
-  A.GY = h->d_gy;
+  A.GY = h->d_gy.get();
   A.K = (int)K, A.nx = (int)h->nx, A.nt = (int)h->nt, A.Np = (int)h->Np;
   A.tau = h->tau, A.gamma = h->gamma;
   A.gate = ctx->gate;
   A.SC = nullptr;
   if (h->Np > HMAXN_LDS) {
     const size_t sneed = (size_t)tiles * 2 * h->Np * 16 * sizeof(double);
-    if (h->sc_cap < sneed) {
-      if (h->d_sc) hipFree(h->d_sc), h->d_sc = nullptr, h->sc_cap = 0;
-      if (hipMalloc(reinterpret_cast<void **>(&h->d_sc), sneed) != hipSuccess) {
-        (void)hipGetLastError();
-        h->d_sc = nullptr;
-        return heat_fail(ctx, MIOC_ENOMEM, "heat: cannot allocate the state scratch");
-      }
-      h->sc_cap = sneed;
-    }
-    A.SC = h->d_sc;
+    if (h->d_sc.bytes() < sneed && !h->d_sc.alloc(sneed))
+      return heat_fail(ctx, MIOC_ENOMEM, "heat: cannot allocate the state scratch");
+    A.SC = h->d_sc.get();
   }
   const hipError_t e = launch_heat(ctx->stream, A, (int)tiles);
   if (e != hipSuccess) return heat_fail(ctx, MIOC_EHIP, std::string("k_heat_run: ") + hipGetErrorString(e));
@@ -506,16 +481,9 @@ int32_t mioc_heat_eval(mioc_ctx *ctx, int64_t K, const double *x, double *J, dou
   if (K < 1 || K > INT32_MAX || !x || (!J && !df)) return heat_fail(ctx, MIOC_EINVAL, "heat: bad K / x / outputs");
   if (hipSetDevice(ctx->device) != hipSuccess) return heat_fail(ctx, MIOC_EHIP, "hipSetDevice failed");
   const size_t nxt = (size_t)K * h->nx * h->nt, need = (2 * nxt + K) * sizeof(double);
-  if (h->io_cap < need) {
-    if (h->d_io) hipFree(h->d_io), h->d_io = nullptr, h->io_cap = 0;
-    if (hipMalloc(reinterpret_cast<void **>(&h->d_io), need) != hipSuccess) {
-      (void)hipGetLastError();
-      h->d_io = nullptr;
-      return heat_fail(ctx, MIOC_ENOMEM, "heat: cannot allocate the host-entry staging");
-    }
-    h->io_cap = need;
-  }
-  double *dx = h->d_io, *ddf = h->d_io + nxt, *dJ = h->d_io + 2 * nxt;
+  if (h->d_io.bytes() < need && !h->d_io.alloc(need))
+    return heat_fail(ctx, MIOC_ENOMEM, "heat: cannot allocate the host-entry staging");
+  double *dx = h->d_io.get(), *ddf = dx + nxt, *dJ = dx + 2 * nxt;
   if (hipMemcpyAsync(dx, x, nxt * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
     return heat_fail(ctx, MIOC_EHIP, "heat: x copy-in failed");
   int rc = mioc_heat_eval_device(ctx, K, dx, J ? dJ : nullptr, df ? ddf : nullptr);

@@ -1,10 +1,15 @@
 // mioc_internal.h -- context and kernel-launch declarations shared by the C ABI (mioc_api.cpp)
-// and the gfx950 kernels (mioc_generic.hip, mioc_pinf.hip).
+// and the gfx950 kernels (mioc_*.hip).
+// Device memory is owned: every buffer of the context, of its two DP slots (mioc_ctx::Slot) and of the heat and
+// convolution objectives is a DevBuf (pointer + capacity, freed by its destructor), pinned host words are
+// PinnedWords.  The strides of the last DP's tables are computed once per bellman call into mioc_ctx::lay (DpLayout),
+// which the backtrack and the read-back entry points use.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -14,6 +19,60 @@ namespace mioc {
 
 constexpr int kMaxM = 8;          // controls per tuple supported by the kernels
 constexpr int kRowTile = 64;      // budget rows per lane-tile; fronts are padded to a multiple
+
+// An owned device buffer: a pointer and its capacity in bytes.  Move-only (no copies: the move members suppress
+// them); the destructor frees.
+template <typename T>
+struct DevBuf {
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) reset(), p = o.p, cap = o.cap, o.p = nullptr, o.cap = 0;
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  T *get() const { return p; }
+  size_t bytes() const { return cap; }
+  void reset() {
+    if (p) hipFree(p);
+    p = nullptr, cap = 0;
+  }
+  // exactly `bytes`, contents not kept; false (and empty) when the device has no room.  No synchronisation: for
+  // buffers that nothing in flight reads, and callers that word their own error
+  bool alloc(size_t bytes) {
+    reset();
+    if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      return false;
+    }
+    cap = bytes;
+    return true;
+  }
+  // at least need_bytes (contents not kept): the buffer stays if it is large enough, else the device is synchronised
+  // (the old buffer may still be read by a backtrack in flight on the other stream) and it is replaced
+  int grow(mioc_ctx *ctx, size_t need_bytes, const char *what);
+
+ private:
+  T *p = nullptr;
+  size_t cap = 0;
+};
+
+// One pinned host allocation of four 32-bit words, the target of small device-to-host copies.
+struct PinnedWord {
+  PinnedWord() = default;
+  PinnedWord(const PinnedWord &) = delete;
+  PinnedWord &operator=(const PinnedWord &) = delete;
+  ~PinnedWord() {
+    if (p) hipHostFree(p);
+  }
+  bool alloc() { return hipHostMalloc(reinterpret_cast<void **>(&p), 16, 0) == hipSuccess; }
+  int32_t *get() const { return p; }
+  int32_t &operator[](int i) const { return p[i]; }
+
+ private:
+  int32_t *p = nullptr;
+};
 
 // Device-side view of the flattened level table + switching cost, passed by value to kernels.
 struct LevelsDev {
@@ -277,19 +336,36 @@ int join_bt(mioc_ctx *ctx);
     if (rcj_) return rcj_;                        \
   } while (0)
 
-int grow_ode_state(mioc_ctx *ctx, size_t need_bytes);  // mioc_api.cpp: grows mioc_ctx::d_ode_state
-
 struct HeatState;  // mioc_heat.hip: the PDE heat objective's device matrices (mioc_heat_setup)
 void heat_free(HeatState *h);
 struct ConvState;  // mioc_conv.hip: the convolution objective's device tables (mioc_conv_setup)
 void conv_free(ConvState *c);
 
+// Where the tables of the last DP lie: filled once by run_bellman (mioc_api.cpp), read by the backtrack, the timeout
+// check and the read-back entry points.
+struct DpLayout {
+  int algo = 0;
+  int ubytes = 1;            // bytes per argmin cell
+  size_t s_stride = 0;       // cells of one step's front / argmin table: (B + 1)·L
+  size_t stage_kstride = 0;  // doubles between two subproblems' staging blocks (pyramid / separable)
+  size_t uu_stride_k = 0;    // cells between two subproblems' staged argmin tables UU
+  size_t u_stride_k = 0;     // cells between two subproblems' argmin tables U (generic / fused)
+  size_t front_stride = 0;   // doubles of one subproblem's front: L·RP
+  // the timeout word of a DP whose workgroups hand rows to each other (run_pending): buffer and word offset
+  const DevBuf<int32_t> *err_buf = nullptr;
+  size_t err_off = 0;
+};
+
 }  // namespace mioc
 
 // ---- the context ----------------------------------------------------------------------------------
 struct mioc_ctx {
+  template <typename T>
+  using Buf = mioc::DevBuf<T>;
+
   int device = 0;
-  int ncu = 0;  // the device's compute units (cached on first use)
+  int ncu = 0;                     // the device's compute units, a CU's LDS and a workgroup's largest LDS share
+  int cu_lds = 0, wg_lds = 0;      // (queried once, mioc_create)
   hipStream_t stream = nullptr;
   std::string err;
   int64_t opt_algo = MIOC_ALGO_AUTO;
@@ -303,11 +379,9 @@ struct mioc_ctx {
   std::vector<double> nuval_h;     // [L][M]
   std::vector<int32_t> gidx_h;     // [L] grid-linear index of each admissible tuple
   std::vector<double> numin_h, numax_h;
-  double *d_nuval = nullptr;
-  int32_t *d_nuint = nullptr;
-  int32_t *d_gidx = nullptr;
-  int32_t *d_vals = nullptr, *d_voff = nullptr, *d_g2r = nullptr;
-  double *d_numin = nullptr, *d_numax = nullptr;
+  Buf<double> d_nuval;
+  Buf<int32_t> d_nuint, d_gidx, d_vals, d_voff, d_g2r;
+  Buf<double> d_numin, d_numax;
 
   // cost
   bool have_cost = false;
@@ -315,27 +389,21 @@ struct mioc_ctx {
   int64_t p_int = 1;
   double beta = 0.0;
   std::vector<double> table;
-  double *d_costlut = nullptr;
-  double *d_costtab = nullptr;
-  double *d_tvw = nullptr;         // unscaled weight table for TV_p (MIOC_P_INTLUT / MIOC_P_TABLE)
+  Buf<double> d_costlut, d_costtab;
+  Buf<double> d_tvw;               // unscaled weight table for TV_p (MIOC_P_INTLUT / MIOC_P_TABLE)
   int64_t tvw_len = 0;
   bool pred_fma = false;           // MIOC_OPT_PRED_FMA
-  double *d_pred_own = nullptr;    // mioc_pred staging: 4 doubles, then the TV error flag (int32)
+  Buf<double> d_pred_own;          // mioc_pred staging: 4 doubles, then the TV error flag (int32)
   bool trm_pending = false;
   const int32_t *Bvec = nullptr;   // per-subproblem B' of the running backtrack (mioc_backtrack_batch_budgets_device)
-  double *d_ode_state = nullptr;   // forward states: [K][nt][2] of mioc_ode_eval_device, [nt][ny][K] of an ODE program
-  size_t ode_cap = 0;
+  Buf<double> d_ode_state;         // forward states: [K][nt][2] of mioc_ode_eval_device, [nt][ny][K] of an ODE program
   mioc::HeatState *heat = nullptr; // mioc_heat_setup / mioc_heat_eval_device
   mioc::ConvState *conv = nullptr; // mioc_conv_setup / mioc_conv_eval_device
   int64_t costlut_len = 0;
 
-  // owned problem inputs (device)
-  double *d_df = nullptr, *d_uold = nullptr;
-  size_t in_cap = 0;               // doubles per array
-
-  // last DP
+  // last DP (its inputs are the current slot's, below)
   bool have_dp = false;
-  int algo = 0;
+  mioc::DpLayout lay;
   int K = 0, nt = 0, B = 0, RP = 0;
   double dt = 0.0;
 
@@ -343,61 +411,48 @@ struct mioc_ctx {
   bool pyr_ok = false;
   bool grid_ok = false;            // product grid of consecutive integer levels in grid order (PyrGeom valid)
   mioc::PyrGeom pyr;
-  double *d_stage = nullptr;       // [2][K][B+1][L] source-row-major fronts, each row in sphere order
-  size_t stage_cap = 0;
-  uint32_t *d_perm = nullptr;      // [K][nt][L] sphere order of u_old(i): rank | (L1 distance << 16)
-  int32_t *d_same2 = nullptr;      // [K][nt] u_old(i) == u_old(i+2) (the persistent separable driver's order reuse)
-  size_t same2_cap = 0;
-  uint16_t *d_strad = nullptr;     // [K][nt][8][32] seam-straddling pairs per wave (k_sdt_run's 8-wave layout)
-  size_t strad_cap = 0;
-  size_t perm_cap = 0;
+  Buf<double> d_stage;             // [2][K][B+1][L] source-row-major fronts, each row in sphere order
+  Buf<uint32_t> d_perm;            // [K][nt][L] sphere order of u_old(i): rank | (L1 distance << 16)
+  Buf<int32_t> d_same2;            // [K][nt] u_old(i) == u_old(i+2) (the persistent separable driver's order reuse)
+  Buf<uint16_t> d_strad;           // [K][nt][8][32] seam-straddling pairs per wave (k_sdt_run's 8-wave layout)
   bool opt_persist = true;         // separable transform: one persistent launch (MIOC_OPT_PERSIST)
   bool force_steps = false;        // redo of a persistent DP whose waits timed out: per-step launches
   int64_t n_persist_fallbacks = 0; // persistent DPs redone with per-step launches (mioc_diagnostics slot 6 after a separable DP)
-  int32_t *d_runflags = nullptr;   // persistent DP: [K][B+1] done, [K][B+1] loaded, err
-  double *d_chain = nullptr;       // persistent DP: V[k][i] = Φ_i[j0(i), 0], the row-0 chain (k_sdt_chain)
-  size_t chain_cap = 0;
+  Buf<int32_t> d_runflags;         // persistent DP: [K][B+1] done, [K][B+1] loaded, err; p = Inf: segment flags, err
+  Buf<double> d_chain;             // persistent DP: V[k][i] = Φ_i[j0(i), 0], the row-0 chain (k_sdt_chain)
   unsigned spin_limit = 1u << 24;  // persistent DP: polls before a dependency wait gives up (MIOC_OPT_SPIN_LIMIT)
-  size_t stage_kstride = 0;        // doubles between two subproblems' staging blocks in the last pyramid / sdt DP
   int opt_nb = mioc::kSdtDefaultBuffers;  // staging buffers of a persistent separable DP (MIOC_OPT_SDT_BUFFERS)
   const int32_t *gate = nullptr;   // device TRM control (mioc_trm_attach): the state block's gate word
-  int32_t *h_trm_poll = nullptr;   // pinned: the gate and any-active words (mioc_trm_poll)
+  mioc::PinnedWord h_trm_poll;     // pinned: the gate and any-active words (mioc_trm_poll)
   int opt_fsep_seg = 0;            // fused separable DP: row segments (MIOC_OPT_FSEP_SEGMENTS)
-  double *d_ring = nullptr;        // fused separable DP, S > 1: the segments' outbox rings
-  size_t ring_cap = 0;
-  int32_t *d_segflags = nullptr;   // ... and their flags (+ err)
-  size_t segflag_cap = 0;
+  Buf<double> d_ring;              // fused separable DP, S > 1: the segments' outbox rings
+  Buf<int32_t> d_segflags;         // ... and their flags (+ err)
   int last_fsep_seg = 0;           // segments of the last fused separable launch (0: the mioc_fused.hip kernel)
-  size_t runflag_cap = 0;
-  int32_t *h_run_err = nullptr;    // pinned copy of err
+  mioc::PinnedWord h_run_err;      // pinned copy of err (lay.err_buf, lay.err_off)
   bool run_pending = false;
-  int32_t *d_counters = nullptr;   // [8] diagnostics: value-collision targets, multi-level targets, ...
+  Buf<int32_t> d_counters;         // [8] diagnostics: value-collision targets, multi-level targets, ...
   int64_t occupancy = 0;           // diagnostics [7]: resident workgroups per CU of the last fused launch
 
   // generic buffers
-  double *d_front = nullptr;       // [2][K][L][RP]
-  size_t front_cap = 0;            // bytes
-  void *d_U = nullptr;             // [K][nt-1][L][B+1] uint8 / uint16
-  size_t U_cap = 0;                // bytes
-  int ubytes = 1;
+  Buf<double> d_front;             // [2][K][L][RP]
+  Buf<unsigned char> d_U;          // [K][nt-1][L][B+1] uint8 / uint16
 
-  // p = Inf buffers
-  mioc::PinfDev pinf;
-  size_t pinf_cap_k = 0, pinf_cap_R = 0, pinf_cap_kabs = 0, pinf_cap_ftab = 0, pinf_cap_fseg = 0, pinf_cap_fneed = 0;
+  // p = Inf: the class-row geometry and walk plan of the last DP (PinfDev, built by pinf_dev), the segmented walk's tables
+  int pinf_BW = 0, pinf_BWP = 0, pinf_CH = 0, pinf_W = 0;
+  Buf<uint8_t> d_ftab;
+  Buf<int32_t> d_fseg, d_fneed;
   int opt_pinf_walk = 0;           // p = Inf backtrack: 0 auto, 1 segmented walk, -1 serial (MIOC_OPT_PINF_WALK)
   bool last_pinf_fwalk = false;    // the last p = Inf backtrack ran the segmented walk
 
   // backtrack scratch
   bool have_path = false;          // d_ranks holds the controls of the last backtrack
-  mioc::Start *d_start = nullptr;
-  int32_t *d_ranks = nullptr;      // [K][nt] level ranks of the path, then [K][nt] ranks of u_old
-  size_t ranks_cap = 0;
-  int32_t *d_flags = nullptr;      // [4] validation flags / counters
-  int32_t *h_flags = nullptr;      // pinned mirror
-  double *d_uout_own = nullptr;    // host-API backtrack output staging
-  double *d_phistar_own = nullptr;
-  int32_t *d_status_own = nullptr;
-  size_t uout_cap = 0;
+  Buf<mioc::Start> d_start;
+  Buf<int32_t> d_ranks;            // [K][nt] level ranks of the path, then [K][nt] ranks of u_old
+  Buf<int32_t> d_flags;            // [4] validation flags / counters
+  mioc::PinnedWord h_flags;        // pinned mirror
+  Buf<double> d_uout_own;          // host-API backtrack output staging
+  Buf<double> d_phistar_own;
+  Buf<int32_t> d_status_own;
 
   // p = Inf backtrack overlapping the next DP: it runs on bstream (the next bellman's kernels on `stream` meanwhile),
   // so every DP owns one of two slots of its inputs and p = Inf tables (the backtrack of DP n reads slot n % 2 while
@@ -410,12 +465,12 @@ struct mioc_ctx {
   int bt_last = 0;
   int slot = 0;  // the last bellman's slot
   struct Slot {
-    double *df = nullptr, *uold = nullptr;
-    size_t in_cap = 0;
-    double *kmin = nullptr, *k2 = nullptr, *R = nullptr, *kabs = nullptr;
-    int32_t *kfirst = nullptr;
-    size_t cap_k = 0, cap_R = 0, cap_kabs = 0;
+    Buf<double> df, uold;          // [K][nt][M] each
+    Buf<double> kmin, k2, R, kabs; // the p = Inf tables (PinfDev)
+    Buf<int32_t> kfirst;
   } slots[2];
+  Slot &cur() { return slots[slot]; }
+  const Slot &cur() const { return slots[slot]; }
 
   // timing
   struct EvPair {
@@ -428,3 +483,15 @@ struct mioc_ctx {
   int64_t stat_launches[4] = {};
   const char *stat_name[4] = {"", "", "", ""};
 };
+
+template <typename T>
+int mioc::DevBuf<T>::grow(mioc_ctx *ctx, size_t need_bytes, const char *what) {
+  if (p && cap >= need_bytes) return MIOC_OK;
+  if (p) (void)hipDeviceSynchronize();
+  if (need_bytes == 0) need_bytes = 16;
+  if (alloc(need_bytes)) return MIOC_OK;
+  char buf[160];
+  std::snprintf(buf, sizeof buf, "cannot allocate %.3f GB for %s", need_bytes / 1e9, what);
+  if (ctx) ctx->err = buf;
+  return MIOC_ENOMEM;
+}

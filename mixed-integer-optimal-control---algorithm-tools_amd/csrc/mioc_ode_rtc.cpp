@@ -467,13 +467,13 @@ int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int6
   }
   const bool euler = prog->integrator == MIOC_ODE_INT_EULER;
   if (euler) {  // forward states [nt][ny][K]
-    const int rc = mioc::grow_ode_state(ctx, (size_t)K * (size_t)nt * (size_t)prog->ny * sizeof(double));
+    const int rc = ctx->d_ode_state.grow(ctx, (size_t)K * (size_t)nt * (size_t)prog->ny * sizeof(double), "ODE states");
     if (rc) return rc;
   } else if (d_df) {  // the state at every substep start [nt * substeps][ny][K]; a value-only call stores nothing
     // K * nt < 2^62 and per <= 64 * 8 * 8: the product is taken only once it is known to stay below 2^46
     const uint64_t cells = (uint64_t)K * (uint64_t)nt, per = (uint64_t)(prog->substeps * prog->ny) * sizeof(double);
     if (cells > ((uint64_t)1 << 46) / per) return fail(ctx, MIOC_ENOMEM, "the ODE states of all substeps exceed 64 TiB");
-    const int rc = mioc::grow_ode_state(ctx, (size_t)(cells * per));
+    const int rc = ctx->d_ode_state.grow(ctx, (size_t)(cells * per), "ODE states");
     if (rc) return rc;
   }
   int Ki = (int)K, nti = (int)nt, ms = prog->substeps;
@@ -483,7 +483,7 @@ int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int6
   for (int r = 0; r < prog->ny; ++r) par[r] = state0[r];
   for (int q = 0; q < prog->np; ++q) par[prog->ny + q] = params[q];
   const double *X = d_x;
-  double *ST = ctx->d_ode_state;
+  double *ST = ctx->d_ode_state.get();
   const int32_t *gate = ctx->gate;
   void *args_euler[] = {&Ki, &nti, &t0, &tau, par, &X, &d_J, &d_df, &ST, &gate};
   void *args_rk[] = {&Ki, &nti, &ms, &t0, &tau, &h, par, &X, &d_J, &d_df, &ST, &gate};
