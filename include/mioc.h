@@ -338,6 +338,48 @@ int32_t mioc_ode_eval_device(mioc_ctx *ctx, int32_t problem, int64_t K, const do
  *   scratch    with d_df the state at every substep start is stored: K * nt * m * ny doubles of the context's ODE
  *              scratch, grown on demand (MIOC_ENOMEM if that fails); a value-only call (d_df NULL) stores nothing.
  *
+ * Implicit integrators.  MIOC_ODE_INT_BEULER (backward Euler: theta = 1, order 1, L-stable) and MIOC_ODE_INT_MIDPOINT
+ * (the implicit midpoint rule: theta = 1/2, order 2, A-stable) are for dynamics with fast decaying modes, where an
+ * explicit scheme's substep is bounded by stability and not by accuracy.  The reference has no such scheme for its ODE
+ * family; it is defined here.  The grid is the one above (h = tau/m, substep n = i*m + j, x_i held over interval i);
+ * every hook sees i = the control interval and t = the stage time t_s = (T0 + n*h) + theta*h.
+ *   forward    the stage slope k solves k = F(t_s, Y, x_i) with the stage state Y = y_n + (theta*h)*k; then
+ *              y_{n+1} = y_n + h*k, q_{n+1} = q_n + h*G(t_s, Y, x_i), q_0 = 0 and J = q_{nt*m} (a quadrature cost, as
+ *              for Heun / RK4).
+ *   Newton     k = F(t_s, y_n, x_i) to start, then at most MIOC_ODE_NEWTON_MAX = 12 times: Y = y_n + (theta*h)*k;
+ *              r = F(Y) - k;  A = I - (theta*h)*Fy(Y);  solve A*delta = r;  k = k + delta.  The iteration stops after
+ *              the update for which every component r has |delta_r| <= MIOC_ODE_NEWTON_TOL * max(1, max_r |k_r|)
+ *              (1e-10, k the updated slope) and a finite k_r; the comparison is made component by component, so a
+ *              NaN fails it.  The update is quadratic: the accepted k is converged to rounding.  Y, G and y_{n+1}
+ *              are then taken from the accepted k.
+ *   failure    a substep whose iteration has not stopped after MIOC_ODE_NEWTON_MAX updates (no real root, a singular
+ *              A through its non-finite delta, non-finite hooks) fails its restart: that restart's J and every entry
+ *              of its df row are NaN, no other restart is affected, and the call returns MIOC_OK (the kernel is
+ *              asynchronous); the next mioc_bellman_* that is given the row reports MIOC_ENONFINITE.  The iteration
+ *              is capped, so the launch always ends.
+ *   solve      dense Gaussian elimination in registers, A and the right-hand side b overwritten.  For each column
+ *              c = 0..ny-1: for each r = c+1..ny-1 in turn, rows r and c (of A from column c on, and of b) change
+ *              places if |A[r][c]| > |A[c][c]| (partial pivoting by conditional swaps); then for each r > c:
+ *              f = A[r][c] / A[c][c] (the IEEE quotient), A[r][e] = A[r][e] - f*A[c][e] for e > c, b[r] = b[r] - f*b[c].
+ *              Back substitution for r = ny-1..0, the sum left to right:
+ *              delta[r] = ((b[r] - A[r][r+1]*delta[r+1]) - A[r][r+2]*delta[r+2] - ...) / A[r][r].
+ *   gradient   the exact derivative of that J by the implicit function theorem; no Newton and no F call.  w = 0 after
+ *              the last substep; per substep n = nt*m-1..0, with Fy, Gy, Fu, Gu at the stored stage state Y:
+ *                kbar = h*w + ((theta*h)*h)*Gy;   solve (I - (theta*h)*Fy)' mu = kbar   (the solve above);
+ *                xbar_i += Fu' mu + h*Gu;   w = w + (Fy' mu + h*Gy);   df[m, i] = xbar_i[m] / tau as above.
+ *              A singular transposed matrix makes w, and with it the df columns of that and all earlier intervals, NaN.
+ *   hooks      F at (t_s, y_n) once per substep, then F and Fy at (t_s, Y) once per Newton update, G at the accepted
+ *              Y, forward; Fy, Gy, Fu, Gu at the stored Y of every substep backwards.  fy is zeroed once per evaluation
+ *              before the forward sweep, fu, gy and gu once before the backward sweep.
+ *   rounding   theta*h and (theta*h)*h are rounded once; t_s = (T0 + (double)n*h) + theta*h; every sum left to right:
+ *                Y[r] = y[r] + (theta h)*k[r];  r[r] = f[r] - k[r];  A[r][c] = (r == c ? 1.0 : 0.0) - (theta h)*fy[r][c]
+ *                k[r] = k[r] + delta[r];  q = q + h*G;  y[r] = y[r] + h*k[r];  J = q
+ *                kbar[r] = h*w[r] + ((theta h) h)*gy[r];  A'[r][c] = (r == c ? 1.0 : 0.0) - (theta h)*fy[c][r]
+ *                xbar[m] = xbar[m] + (((fu[0][m]*mu[0] + fu[1][m]*mu[1]) + ...) + h*gu[m])
+ *                w[c] = w[c] + (((fy[0][c]*mu[0] + fy[1][c]*mu[1]) + ...) + h*gy[c]);  df[m, i] = xbar[m] / tau
+ *   scratch    with d_df the stage state Y of every substep is stored, the same K * nt * m * ny doubles as above; a
+ *              value-only call stores nothing.
+ *
  * mioc_ode_program_create needs no context and no GPU: it compiles for gfx950 and keeps the code object.  Limits:
  *   1 <= ny <= 8, 1 <= nx <= 8, 0 <= nparams <= 32, source text of at most 1 MiB (else MIOC_EINVAL).  A compile
  *   failure returns MIOC_ECOMPILE; the compiler's log (also the warnings of a successful compile) is copied into
@@ -361,6 +403,10 @@ int32_t mioc_ode_program_create(const char *hooks, int32_t ny, int32_t nx, int32
 #define MIOC_ODE_INT_EULER 0
 #define MIOC_ODE_INT_HEUN 1
 #define MIOC_ODE_INT_RK4 2
+#define MIOC_ODE_INT_BEULER 16   /* implicit schemes start at 16 (see "Implicit integrators" above) */
+#define MIOC_ODE_INT_MIDPOINT 17
+#define MIOC_ODE_NEWTON_MAX 12   /* fixed: the Newton updates per substep, and the relative size of the last one */
+#define MIOC_ODE_NEWTON_TOL 1e-10
 int32_t mioc_ode_program_create_ex(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t integrator,
                                    int32_t substeps, mioc_ode_program **out, char *log, int64_t log_cap);
 int32_t mioc_ode_program_destroy(mioc_ode_program *prog);

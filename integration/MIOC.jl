@@ -235,7 +235,8 @@ end
 # ---- user-defined ODE objectives: the six hooks of an AbstractODEObjective (ODEObjective.jl:243-248) as HIP source
 # text, compiled at run time for gfx950 (mioc_ode_program_*; the hook contract is in include/mioc.h) ----------------
 
-const ODE_INTEGRATORS = Dict(:euler => Int32(0), :heun => Int32(1), :rk4 => Int32(2))  # MIOC_ODE_INT_*
+const ODE_INTEGRATORS = Dict(:euler => Int32(0), :heun => Int32(1), :rk4 => Int32(2), :beuler => Int32(16),
+                             :midpoint => Int32(17))  # MIOC_ODE_INT_*
 
 """
     ode_program_create(hooks, ny, nx, nparams; integrator = :euler, substeps = 1) -> Ptr{Cvoid}
@@ -244,11 +245,15 @@ Compile the hook text (needs no context and no GPU).  A compile failure raises a
 whose diagnostics name the text's own lines (`hooks:3:…`).  mioc_ode_program_create_ex: `:euler` is the reference's
 scheme, what mioc_ode_program_create compiles (substeps must be 1); `:heun` and `:rk4` take `substeps` (1..64) steps inside every control interval and return the exact gradient of their
 discrete objective, so the control grid nt (and with it the DP) can be much coarser (include/mioc.h, "Integrators").
+`:beuler` (backward Euler) and `:midpoint` (the implicit midpoint rule) are the implicit schemes for stiff dynamics,
+with `substeps` likewise: Newton's method per substep on the device (at most 12 updates, relative size 1e-10), the
+gradient by the implicit function theorem; a restart whose iteration fails has NaN for J and its df row
+(include/mioc.h, "Implicit integrators").
 The program carries both; `ode_program_eval_device!` is unchanged.
 """
 function ode_program_create(hooks::String, ny::Integer, nx::Integer, nparams::Integer; integrator::Symbol = :euler,
                             substeps::Integer = 1)
-    haskey(ODE_INTEGRATORS, integrator) || error("integrator must be :euler, :heun or :rk4")
+    haskey(ODE_INTEGRATORS, integrator) || error("integrator must be :euler, :heun, :rk4, :beuler or :midpoint")
     r = Ref{Ptr{Cvoid}}(C_NULL)
     log = zeros(UInt8, 1 << 16)
     rc = ccall((:mioc_ode_program_create_ex, libmioc), Int32,

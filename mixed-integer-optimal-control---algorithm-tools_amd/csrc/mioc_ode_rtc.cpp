@@ -15,6 +15,8 @@
 // mioc_ode_program_create_ex also takes an integrator: Heun or classical RK4 with substeps inside each control
 // interval, a quadrature cost and the scheme's discrete adjoint (kSkeletonRK; the scheme is defined in include/mioc.h).
 // The program carries integrator and substeps; the Euler skeleton and what it compiles to are untouched.
+// MIOC_ODE_INT_BEULER / _MIDPOINT are the one-stage implicit schemes (kSkeletonTheta): Newton with an in-register
+// Gaussian elimination forward, one transposed solve per substep backward.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -270,6 +272,188 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
 }
 )SKEL";
 
+// The backward Euler / implicit midpoint skeleton (one stage, Y = y_n + (theta h) k, k = F(Y); the scheme, its Newton
+// rule and the rounding order are written out in include/mioc.h).  TH, theta as a double literal, is #defined in front
+// with NY / NX / NP.  The kernel signature is kSkeletonRK's.  The stage equation is solved by Newton's method with a
+// dense Gaussian elimination in registers: every loop over NY is fully unrolled and the pivoting is conditional row
+// swaps, so no array is indexed by a run-time value.  ST holds the stage state Y of every substep, [n][r][k]: the
+// backward sweep solves one transposed system per substep and calls neither F nor Newton.
+const char *const kSkeletonTheta = R"SKEL(
+#define MIOC_ODE_NEWTON_MAX 12
+#define MIOC_ODE_NEWTON_TOL 1e-10
+namespace mioc_skeleton {
+struct Par {
+  double y0[NY];
+  double p[NP > 0 ? NP : 1];
+};
+
+// A d = b by Gaussian elimination with partial pivoting; A and b are overwritten.  For column c and each r > c in
+// turn, rows r and c change places if |A[r][c]| > |A[c][c]|; then f = A[r][c] / A[c][c] and row r = row r - f * row c
+// (the entries left of the diagonal are never read again and stay as they are).  Back substitution, left to right:
+// d[r] = ((b[r] - A[r][r+1]*d[r+1]) - ...) / A[r][r].  A singular A gives non-finite d.
+__device__ __forceinline__ void solve(double (*A)[NY], double *b, double *d) {
+#pragma unroll
+  for (int c = 0; c < NY; ++c) {
+#pragma unroll
+    for (int r = c + 1; r < NY; ++r) {
+      const bool sw = fabs(A[r][c]) > fabs(A[c][c]);
+#pragma unroll
+      for (int e = c; e < NY; ++e) {
+        const double u = A[c][e], v = A[r][e];
+        A[c][e] = sw ? v : u;
+        A[r][e] = sw ? u : v;
+      }
+      const double u = b[c], v = b[r];
+      b[c] = sw ? v : u;
+      b[r] = sw ? u : v;
+    }
+#pragma unroll
+    for (int r = c + 1; r < NY; ++r) {
+      const double f = A[r][c] / A[c][c];
+#pragma unroll
+      for (int e = c + 1; e < NY; ++e) A[r][e] = A[r][e] - f * A[c][e];
+      b[r] = b[r] - f * b[c];
+    }
+  }
+#pragma unroll
+  for (int r = NY - 1; r >= 0; --r) {
+    double s = b[r];
+#pragma unroll
+    for (int e = r + 1; e < NY; ++e) s = s - A[r][e] * d[e];
+    d[r] = s / A[r][r];
+  }
+}
+}  // namespace mioc_skeleton
+
+extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
+    int K, int nt, int ms, double T0, double tau, double h, mioc_skeleton::Par P, const double *X, double *J,
+    double *DF, double *ST, const int *gate) {
+  if (gate && *gate == 0) return;  // device TRM control: no restart is inside its inner loop
+  const unsigned ku = blockIdx.x * 64u + threadIdx.x;
+  if (ku >= (unsigned)K) return;
+  const size_t k = ku, KK = (size_t)K;
+  const double *p = P.p;
+  const double *x = X + k * (size_t)nt * NX;
+  const double th = TH * h, thh = th * h;  // theta h and (theta h) h, each rounded once
+  // ---- forward: Newton on k = F(y_n + th k) from k = F(y_n); y_{n+1} = y_n + h k, q_{n+1} = q_n + h G(Y) ----
+  double y[NY], Y[NY], kv[NY], f[NY], d[NY], xc[NX], fy[NY][NY], A[NY][NY];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) {
+    y[r] = P.y0[r];
+#pragma unroll
+    for (int c = 0; c < NY; ++c) fy[r][c] = 0.0;  // zeroed once per evaluation, as in the other skeletons
+  }
+  double q = 0.0;
+  bool failed = false;
+  for (int i = 0; i < nt && !failed; ++i) {
+#pragma unroll
+    for (int m = 0; m < NX; ++m) xc[m] = x[(size_t)i * NX + m];
+    for (int j = 0; j < ms && !failed; ++j) {
+      const long long n = (long long)i * ms + j;
+      const double ts = (T0 + (double)n * h) + th;
+      F(p, i, ts, y, xc, kv);
+      bool conv = false;
+#pragma nounroll
+      for (int it = 0; it < MIOC_ODE_NEWTON_MAX && !conv; ++it) {
+#pragma unroll
+        for (int r = 0; r < NY; ++r) Y[r] = y[r] + th * kv[r];
+        F(p, i, ts, Y, xc, f);
+        Fy(p, i, ts, Y, xc, fy);
+#pragma unroll
+        for (int r = 0; r < NY; ++r) {
+          f[r] = f[r] - kv[r];
+#pragma unroll
+          for (int c = 0; c < NY; ++c) A[r][c] = (r == c ? 1.0 : 0.0) - th * fy[r][c];
+        }
+        mioc_skeleton::solve(A, f, d);
+        double kmax = 1.0;
+#pragma unroll
+        for (int r = 0; r < NY; ++r) {
+          kv[r] = kv[r] + d[r];
+          kmax = fmax(kmax, fabs(kv[r]));
+        }
+        // component by component: a NaN in d or kv fails the comparison, an infinite kv its own
+        const double tol = MIOC_ODE_NEWTON_TOL * kmax;
+        conv = true;
+#pragma unroll
+        for (int r = 0; r < NY; ++r) conv = conv && fabs(d[r]) <= tol && fabs(kv[r]) <= 1.7976931348623157e308;
+      }
+      failed = !conv;
+#pragma unroll
+      for (int r = 0; r < NY; ++r) Y[r] = y[r] + th * kv[r];
+      if (DF) {
+#pragma unroll
+        for (int r = 0; r < NY; ++r) ST[((size_t)n * NY + r) * KK + k] = Y[r];
+      }
+      q = q + h * G(p, i, ts, Y, xc);
+#pragma unroll
+      for (int r = 0; r < NY; ++r) y[r] = y[r] + h * kv[r];
+    }
+  }
+  if (failed) {  // a substep's Newton iteration did not converge: this restart's J and df row are NaN
+    const double nan = __builtin_nan("");
+    if (J) J[k] = nan;
+    if (DF)
+      for (size_t e = 0; e < (size_t)nt * NX; ++e) DF[k * (size_t)nt * NX + e] = nan;
+    return;
+  }
+  if (J) J[k] = q;
+  if (!DF) return;
+  // ---- backward: (I - th Fy)' mu = h w + (th h) Gy at the stored Y; df[:, i] = xbar_i / tau ----
+  double *df = DF + k * (size_t)nt * NX;
+  double gy[NY], gu[NX], fu[NY][NX], w[NY], kb[NY], mu[NY], xbar[NX];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) {
+    gy[r] = 0.0;
+    w[r] = 0.0;
+#pragma unroll
+    for (int m = 0; m < NX; ++m) fu[r][m] = 0.0;
+  }
+#pragma unroll
+  for (int m = 0; m < NX; ++m) gu[m] = 0.0;
+  for (int i = nt - 1; i >= 0; --i) {
+#pragma unroll
+    for (int m = 0; m < NX; ++m) {
+      xc[m] = x[(size_t)i * NX + m];
+      xbar[m] = 0.0;
+    }
+    for (int j = ms - 1; j >= 0; --j) {
+      const long long n = (long long)i * ms + j;
+      const double ts = (T0 + (double)n * h) + th;
+#pragma unroll
+      for (int r = 0; r < NY; ++r) Y[r] = ST[((size_t)n * NY + r) * KK + k];
+      Fy(p, i, ts, Y, xc, fy);
+      Gy(p, i, ts, Y, xc, gy);
+#pragma unroll
+      for (int r = 0; r < NY; ++r) {
+        kb[r] = h * w[r] + thh * gy[r];
+#pragma unroll
+        for (int c = 0; c < NY; ++c) A[r][c] = (r == c ? 1.0 : 0.0) - th * fy[c][r];
+      }
+      mioc_skeleton::solve(A, kb, mu);
+      Fu(p, i, ts, Y, xc, fu);
+      Gu(p, i, ts, Y, xc, gu);
+#pragma unroll
+      for (int m = 0; m < NX; ++m) {
+        double t = fu[0][m] * mu[0];
+#pragma unroll
+        for (int r = 1; r < NY; ++r) t = t + fu[r][m] * mu[r];
+        xbar[m] = xbar[m] + (t + h * gu[m]);
+      }
+#pragma unroll
+      for (int c = 0; c < NY; ++c) {
+        double t = fy[0][c] * mu[0];
+#pragma unroll
+        for (int r = 1; r < NY; ++r) t = t + fy[r][c] * mu[r];
+        w[c] = w[c] + (t + h * gy[c]);
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < NX; ++m) df[(size_t)i * NX + m] = xbar[m] / tau;
+  }
+}
+)SKEL";
+
 // ---- hiprtc, loaded at the first mioc_ode_program_create -------------------------------------------------------
 struct Rtc {
   bool ok = false;
@@ -349,11 +533,12 @@ int32_t mioc_ode_program_create_ex(const char *hooks, int32_t ny, int32_t nx, in
   if (!out) return MIOC_EINVAL;
   *out = nullptr;
   if (!hooks || ny < 1 || ny > kMaxNY || nx < 1 || nx > kMaxNX || nparams < 0 || nparams > kMaxNP) return MIOC_EINVAL;
-  if (integrator != MIOC_ODE_INT_EULER && integrator != MIOC_ODE_INT_HEUN && integrator != MIOC_ODE_INT_RK4)
+  const bool implicit = integrator == MIOC_ODE_INT_BEULER || integrator == MIOC_ODE_INT_MIDPOINT;
+  if (integrator != MIOC_ODE_INT_EULER && integrator != MIOC_ODE_INT_HEUN && integrator != MIOC_ODE_INT_RK4 && !implicit)
     return MIOC_EINVAL;
   if (substeps < 1 || substeps > kMaxSubsteps || (integrator == MIOC_ODE_INT_EULER && substeps != 1)) return MIOC_EINVAL;
   // the reference scheme keeps its own skeleton and its head, so its source text is what it was
-  const char *const skeleton = integrator == MIOC_ODE_INT_EULER ? kSkeleton : kSkeletonRK;
+  const char *const skeleton = integrator == MIOC_ODE_INT_EULER ? kSkeleton : implicit ? kSkeletonTheta : kSkeletonRK;
   const size_t len = strnlen(hooks, kMaxSource + 1);
   if (len > kMaxSource) return MIOC_EINVAL;
   const Rtc &R = rtc();
@@ -367,6 +552,9 @@ int32_t mioc_ode_program_create_ex(const char *hooks, int32_t ny, int32_t nx, in
     if (integrator == MIOC_ODE_INT_EULER)
       std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n#line 1 \"hooks\"\n", (int)ny,
                     (int)nx, (int)nparams);
+    else if (implicit)  // TH: theta, 1 for backward Euler and 1/2 for the implicit midpoint rule
+      std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n#define TH %s\n#line 1 \"hooks\"\n",
+                    (int)ny, (int)nx, (int)nparams, integrator == MIOC_ODE_INT_BEULER ? "1.0" : "0.5");
     else  // NS: the stage count, which selects the tableau
       std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n#define NS %d\n#line 1 \"hooks\"\n",
                     (int)ny, (int)nx, (int)nparams, integrator == MIOC_ODE_INT_HEUN ? 2 : 4);
@@ -469,7 +657,8 @@ int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int6
   if (euler) {  // forward states [nt][ny][K]
     const int rc = ctx->d_ode_state.grow(ctx, (size_t)K * (size_t)nt * (size_t)prog->ny * sizeof(double), "ODE states");
     if (rc) return rc;
-  } else if (d_df) {  // the state at every substep start [nt * substeps][ny][K]; a value-only call stores nothing
+  } else if (d_df) {  // the state of every substep (Heun / RK4: at its start, implicit: its stage state)
+    // [nt * substeps][ny][K]; a value-only call stores nothing
     // K * nt < 2^62 and per <= 64 * 8 * 8: the product is taken only once it is known to stay below 2^46
     const uint64_t cells = (uint64_t)K * (uint64_t)nt, per = (uint64_t)(prog->substeps * prog->ny) * sizeof(double);
     if (cells > ((uint64_t)1 << 46) / per) return fail(ctx, MIOC_ENOMEM, "the ODE states of all substeps exceed 64 TiB");
@@ -478,7 +667,7 @@ int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int6
   }
   int Ki = (int)K, nti = (int)nt, ms = prog->substeps;
   double t0 = T0, tau = (T1 - T0) / (double)nt;  // ODEObjective.jl: tau = (T1 - T0) / nt
-  double h = tau / (double)ms;                   // the substep of the Heun / RK4 schemes
+  double h = tau / (double)ms;                   // the substep of every scheme but Euler
   double par[kMaxNY + kMaxNP] = {};              // the skeleton's Par: y0[NY], then p[max(NP, 1)]
   for (int r = 0; r < prog->ny; ++r) par[r] = state0[r];
   for (int q = 0; q < prog->np; ++q) par[prog->ny + q] = params[q];

@@ -6,7 +6,9 @@ sweep for gfx950 at run time (mioc_ode_program_create) and ``Context.ode_program
 hook contract (signatures, the step index each hook sees, zeroing, rounding order) is in ``include/mioc.h``.
 ``ODEProgram(..., integrator="heun" | "rk4", substeps=m)`` compiles the hooks into a Heun / classical RK4 sweep with m
 substeps per control interval instead (mioc_ode_program_create_ex): the states are integrated as accurately as needed
-while nt, and with it the DP, follows how finely the control should switch.
+while nt, and with it the DP, follows how finely the control should switch.  ``integrator="beuler" | "midpoint"`` are
+backward Euler and the implicit midpoint rule for stiff dynamics: Newton's method per substep on the device, the
+gradient by the implicit function theorem; a restart whose Newton iteration fails returns NaN for J and its df row.
 
 ``EXAMPLE_SOURCES`` restates the three built-in problems as hook text, term for term as ``Hooks<...>`` of
 csrc/mioc_ode.hip has them, so each reproduces mioc_ode_eval_device bit for bit; they double as templates.  Parameter
@@ -20,8 +22,8 @@ import ctypes
 import sys
 import weakref
 
-from .native import (MIOC_ECOMPILE, MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_RK4, MIOC_OK, MiocNativeError,
-                     load_library)
+from .native import (MIOC_ECOMPILE, MIOC_ODE_INT_BEULER, MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_MIDPOINT,
+                     MIOC_ODE_INT_RK4, MIOC_OK, MiocNativeError, load_library)
 
 
 class MiocCompileError(MiocNativeError):
@@ -46,7 +48,8 @@ def _close_live_programs():
             pass
 
 
-INTEGRATORS = {"euler": MIOC_ODE_INT_EULER, "heun": MIOC_ODE_INT_HEUN, "rk4": MIOC_ODE_INT_RK4}
+INTEGRATORS = {"euler": MIOC_ODE_INT_EULER, "heun": MIOC_ODE_INT_HEUN, "rk4": MIOC_ODE_INT_RK4,
+               "beuler": MIOC_ODE_INT_BEULER, "midpoint": MIOC_ODE_INT_MIDPOINT}
 MAX_SUBSTEPS = 64
 
 
@@ -54,9 +57,10 @@ class ODEProgram:
     """Six hooks (HIP source text) compiled for gfx950: ny states, nx controls, nparams parameters.  Needs no GPU to
     compile; one program serves any number of contexts.  ``close()`` destroys it (also ``with ODEProgram(...) as p``).
 
-    ``integrator``: "euler" (the reference's explicit Euler / trapezoid scheme, the default), "heun" or "rk4", the
-    latter two with ``substeps`` steps inside every control interval and the exact gradient of their discrete J
-    (include/mioc.h, "Integrators"); the program carries both, every evaluation uses them."""
+    ``integrator``: "euler" (the reference's explicit Euler / trapezoid scheme, the default), "heun", "rk4", or the
+    implicit "beuler" (backward Euler) and "midpoint" (implicit midpoint rule) for stiff dynamics; all but "euler"
+    with ``substeps`` steps inside every control interval and the exact gradient of their discrete J (include/mioc.h,
+    "Integrators" and "Implicit integrators"); the program carries both, every evaluation uses them."""
 
     LOG_CAP = 1 << 16
 
@@ -67,7 +71,7 @@ class ODEProgram:
         if int(substeps) != substeps or not 1 <= substeps <= MAX_SUBSTEPS:
             raise ValueError(f"substeps must be an integer in 1..{MAX_SUBSTEPS}, not {substeps!r}")
         if integrator == "euler" and substeps != 1:
-            raise ValueError("the reference's Euler scheme defines no substeps: use heun or rk4")
+            raise ValueError("the reference's Euler scheme defines no substeps: use heun, rk4, beuler or midpoint")
         self.integrator, self.substeps = integrator, int(substeps)
         self.lib = load_library()
         self.ny, self.nx, self.nparams = int(ny), int(nx), int(nparams)
@@ -238,7 +242,8 @@ def example_program(name, integrator="euler", substeps=1):
 
 def example_problem(name, program=None, nt=None, integrator="euler", substeps=1):
     """DeviceODEProblem of a built-in example (SOS1 over three binary controls, the example's horizon; nt: the
-    example's unless given -- with heun / rk4 and substeps the control grid can be much coarser than the example's).
+    example's unless given -- with heun / rk4 / beuler / midpoint and substeps the control grid can be much coarser
+    than the example's).
     Without ``program``, one is compiled with ``integrator`` and ``substeps``."""
     from .iterators import bounded_sum_iterator
     from .trm_batch import PROBLEMS
