@@ -85,6 +85,10 @@ extern "C" {
                                 over many workgroups -- for batches of at most 64 subproblems with >= 512 steps,
                                 else one serial walk per subproblem; 1: segmented walk forced; -1: serial walk */
 /* option 9 (a two-workgroups-per-row separable driver, opt-in and slower) was removed in round 6: MIOC_EINVAL */
+#define MIOC_OPT_SDT_ROW_OWNER 10 /* persistent separable transform: 1 (default) runs the one-row driver
+                                     (k_sdt_run1) when the plan gives every workgroup exactly one row (K·B
+                                     rows on at least as many CUs); 0: always the general driver (k_sdt_run).
+                                     Results and diagnostics are the same either way */
 
 typedef struct mioc_ctx mioc_ctx;
 
@@ -476,6 +480,9 @@ int32_t mioc_reset_stats(mioc_ctx *ctx);
 
 /* Which algorithm served the last mioc_bellman* call (MIOC_ALGO_GENERIC / _PINF / _PYRAMID). */
 int32_t mioc_last_algo(mioc_ctx *ctx);
+/* Which driver ran the last separable-transform DP (before any per-step redo): 0 one launch per step,
+ * 1 the general persistent driver (k_sdt_run), 2 the one-row persistent driver (k_sdt_run1). */
+int32_t mioc_last_sdt_driver(mioc_ctx *ctx);
 
 /*
  * Diagnostics of the last bellman/backtrack: counters[0] pyramid / separable-transform targets resolved by

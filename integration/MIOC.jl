@@ -15,6 +15,8 @@ const libmioc = get(ENV, "MIOC_LIB",
 const MIOC_OK = Int32(0)
 const MIOC_EINEXACT = Int32(-2)
 const P_INF, P_ONE, P_INTLUT, P_TABLE = Int32(0), Int32(1), Int32(2), Int32(3)
+# mioc_set_option: 0 keeps the separable DP on the general persistent driver (default 1: the one-row driver where it fits)
+const MIOC_OPT_SDT_ROW_OWNER = Int32(10)
 
 mutable struct Context
     ptr::Ptr{Cvoid}

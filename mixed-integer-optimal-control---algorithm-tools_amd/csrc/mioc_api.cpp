@@ -363,13 +363,17 @@ int run_staged(mioc_ctx *ctx, int bmax) {
     ev_begin(ctx, 0, "k_sdt_run");
     // (the grid is nwg <= CUs x resident workgroups per CU by construction of the plan; a wait that never ends
     // anyway -- another process holding CUs -- is caught by the spin limit and redone per step by check_run)
+    // (every workgroup owns one row for the whole launch: the one-row driver k_sdt_run1, under the same label)
+    const bool one_row = ctx->opt_row_owner && plan.one_row;
     HIP_TRY(ctx, launch_sdt_run(ctx->stream, P, Lv, ctx->pyr, perm, ctx->d_same2.get(), ctx->d_strad.get(), stage, ks,
                                 plan.nbuf, UU, Y.uu_stride_k, counters, ctx->d_runflags.get(), plan.nwg,
-                                ctx->spin_limit, run_lds));
+                                ctx->spin_limit, run_lds, one_row));
+    ctx->last_sdt_driver = one_row ? 2 : 1;
     ev_end(ctx, 0, 1);
     Y.err_buf = &ctx->d_runflags, Y.err_off = nflag;
     return queue_timeout_read(ctx);
   }
+  if (!ctx->force_steps) ctx->last_sdt_driver = 0;  // (a redo keeps the driver of the launch it replaces)
   ev_begin(ctx, 0, sdt ? "k_sdt_step" : "k_pyr_step");
   for (int i = ctx->nt - 2; i >= 0; --i)
     HIP_TRY(ctx, (sdt ? launch_sdt_step : launch_pyr_step)(ctx->stream, P, Lv, ctx->pyr, i, perm, st[(i + 1) & 1],
@@ -769,6 +773,7 @@ int32_t mioc_set_option(mioc_ctx *ctx, int32_t option, int64_t value) {
       if (value < 4 || value > kSdtMaxBuffers) return fail(ctx, MIOC_EINVAL, "staging buffers must be in [4, 256]");
       ctx->opt_nb = (int)value;
       return MIOC_OK;
+    case MIOC_OPT_SDT_ROW_OWNER: ctx->opt_row_owner = value != 0; return MIOC_OK;
     case MIOC_OPT_PINF_WALK:
       if (value < -1 || value > 1) return fail(ctx, MIOC_EINVAL, "p=Inf walk option must be -1, 0 or 1");
       ctx->opt_pinf_walk = (int)value;
@@ -1341,6 +1346,8 @@ int32_t mioc_reset_stats(mioc_ctx *ctx) {
 }
 
 int32_t mioc_last_algo(mioc_ctx *ctx) { return ctx ? ctx->lay.algo : MIOC_EINVAL; }
+
+int32_t mioc_last_sdt_driver(mioc_ctx *ctx) { return ctx ? ctx->last_sdt_driver : MIOC_EINVAL; }
 
 int32_t mioc_diagnostics(mioc_ctx *ctx, int64_t *counters, int32_t n) {
   if (!ctx || !counters || n < 0) return MIOC_EINVAL;

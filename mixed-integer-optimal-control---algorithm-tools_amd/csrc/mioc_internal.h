@@ -223,7 +223,7 @@ hipError_t launch_sdt_run(hipStream_t s, const ProblemDev &P, const LevelsDev &L
                           const uint32_t *perm, const int32_t *same2, const uint16_t *strad, double *S, size_t kstride,
                           int NB, uint16_t *UU,
                           size_t uu_stride_k, int32_t *counters, int32_t *flags, int nwg, unsigned spin_limit,
-                          size_t lds);
+                          size_t lds, bool one_row);  // one_row: nwg = K·B, every workgroup owns one row (k_sdt_run1)
 int sdt_run_blocks_per_cu(const PyrGeom &G, size_t lds);
 hipError_t launch_stage_argmin0(hipStream_t s, const ProblemDev &P, const LevelsDev &Lv, const uint32_t *perm,
                                 const double *S0, size_t s_stride, int Bu, Start *start);
@@ -416,6 +416,8 @@ struct mioc_ctx {
   Buf<int32_t> d_same2;            // [K][nt] u_old(i) == u_old(i+2) (the persistent separable driver's order reuse)
   Buf<uint16_t> d_strad;           // [K][nt][8][32] seam-straddling pairs per wave (k_sdt_run's 8-wave layout)
   bool opt_persist = true;         // separable transform: one persistent launch (MIOC_OPT_PERSIST)
+  bool opt_row_owner = true;       // ... with one row per workgroup where the plan allows (MIOC_OPT_SDT_ROW_OWNER)
+  int last_sdt_driver = 0;         // the last separable DP: 0 per-step launches, 1 k_sdt_run, 2 k_sdt_run1
   bool force_steps = false;        // redo of a persistent DP whose waits timed out: per-step launches
   int64_t n_persist_fallbacks = 0; // persistent DPs redone with per-step launches (mioc_diagnostics slot 6 after a separable DP)
   Buf<int32_t> d_runflags;         // persistent DP: [K][B+1] done, [K][B+1] loaded, err; p = Inf: segment flags, err

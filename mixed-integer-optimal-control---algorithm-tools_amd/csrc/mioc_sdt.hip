@@ -950,9 +950,16 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
     const unsigned long long cell = ~(0xFFFFull << sft) | ((unsigned long long)bj << sft);
     ut = make_ulonglong2(mine && !(l0 & 4) ? cell : ~0ull, mine && (l0 & 4) ? cell : ~0ull);
   } else {
+    // this thread's entries of the output order: from the LDS slot, or (one-row driver) the registers that go() left
+    // them in -- the next item's input order is this item's output order
     uint2 eo[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) eo[q] = *reinterpret_cast<const uint2 *>(pout + sd_p2<M>(tid, q));
+    for (int q = 0; q < 4; ++q) {
+      if constexpr (Hooks::kOutOrderRegs)
+        eo[q] = h.raw.e[q];
+      else
+        eo[q] = *reinterpret_cast<const uint2 *>(pout + sd_p2<M>(tid, q));
+    }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       go[2 * q] = outv[eo[q].x & 0xFFFFu];
@@ -1170,6 +1177,7 @@ __device__ __forceinline__ void sdt_rowB(const ProblemDev &P, const LevelsDev &L
 
 // per-step driver: no pipeline hooks
 struct SdHooksNone {
+  static constexpr bool kOutOrderRegs = false;  // (see SdPipe1)
   __device__ __forceinline__ void early() {}
   __device__ __forceinline__ void go() {}
   __device__ __forceinline__ void late_drain() {}
@@ -1562,6 +1570,7 @@ __device__ __forceinline__ int sd_flag_poll(const int32_t *p) {
 template <int M>
 struct SdPipe {
   static constexpr int L = 1 << (3 * M);
+  static constexpr bool kOutOrderRegs = false;  // (see SdPipe1)
   // the current row (cp, step i) and the next one (ncp, step ni)
   int cp, i, ncp, ni;
   bool has_next;
@@ -1850,6 +1859,261 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P_ar
   SD_TL_FLUSH(h.g0);
 }
 
+// ---- the one-row driver ----------------------------------------------------------------------------------
+// The persistent driver for W = B: every workgroup owns one row c' for the whole launch (the headline shape, B rows on
+// at least B CUs).  The hand-off is k_sdt_run's, instruction for instruction (sc1 loads and stores, the late drain, the
+// barrier, one lane's flag store, the polling wave, the counted row start); what differs is what k_sdt_run re-derives
+// per item from "which row is this": with c' fixed the next item is always (c', i - 1), so
+//   * each lane's poll address is fixed and its token steps by one per item (early() is "step the token, poll");
+//     diagnostics [4] -- items whose write-after-read wait was armed -- is arithmetic in nt and NB, formed at exit;
+//   * the next item's input order is this item's output order, so the entries go() reads for the next item's loads are
+//     the ones the gather after barrier 3 needs: it takes them from the registers (kOutOrderRegs);
+//   * the row's byte offsets, its flags and its U row step with i.
+template <int M>
+struct SdPipe1 {
+  static constexpr int L = 1 << (3 * M);
+  static constexpr bool kOutOrderRegs = true;
+  int cp, i;  // the row (fixed) and the current step; the next item is (cp, i - 1)
+  bool has_next;
+  int nt, k, g0;
+  unsigned spin_limit, rowb, r0b;
+  int32_t *lflag, *dflag, *err;  // loaded[k][cp], done[k][cp], the launch's error word
+  const uint32_t *pk;
+  uint32_t *slot;
+  __amdgpu_buffer_rsrc_t rs;
+  const char *dfuo0;
+  unsigned dfuo_st;
+  const uint16_t *sk;
+  uint16_t *sslot;
+  unsigned char *sds;
+  unsigned ldsb;
+  __device__ __forceinline__ unsigned lds_slot(int step) const {
+    return ldsb + (unsigned)sd_slot_offset<M>() + (unsigned)(step & 1) * (unsigned)(L * sizeof(uint32_t));
+  }
+  __device__ __forceinline__ unsigned lds_sslot(int step) const {
+    return ldsb + (unsigned)sd_strad_offset<M>() + (unsigned)(step & 1) * (unsigned)(8 * SD_STRAD_N * sizeof(uint16_t));
+  }
+  SdtShared<(1 << (3 * M - 3)) / 64> *sh;
+  // this lane's poll, set up once (lanes 0-31: done[cp - s], token(i) = nt - 1 - i, armed while there is a next item;
+  // lanes 32-63: loaded[cp + s], token(i + NB - 1) -- not positive until the ring wraps, and every flag is >= 0, so it
+  // needs no arming; a lane without a neighbour polls the row's own `loaded` against INT32_MIN, which a step per item
+  // leaves far below zero)
+  int32_t *fp;
+  int need, val;
+  SdRaw raw;
+  SdNext nx;
+  const ProblemDev *Pp;
+  const PyrGeom *Gp;
+  unsigned valid_next;
+  unsigned nbo;  // byte offset of buffer i % NB: this item's output buffer and the next item's input buffer
+  unsigned sob;  // byte offset of this row's output row in the region
+  bool stop_seen;
+  double *reg;
+
+  // step the token, poll
+  __device__ __forceinline__ void early() {
+    SD_TL_AT(g0, i, nt, 1);
+    ++need;
+    if (!has_next && (sd_tid() & 63) < 32) need = INT32_MIN;  // the last item: no next row to wait for
+    val = sd_flag_poll(fp);
+  }
+  __device__ __forceinline__ void go() {
+    SD_TL_AT(g0, i, nt, 2);
+    const int tid = sd_tid();
+    // evaluated before the flag store below: the compiler's wait for `val` would otherwise cover that store
+    bool ready = __all(val >= need);
+    if (tid == 0) __hip_atomic_store(lflag, nt - 1 - i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned spins = 0;
+    while (!ready) {
+      if (sd_flag_poll(err) || ++spins > spin_limit) {
+        if ((tid & 63) == 0) {
+          __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          sh->stop = 1;
+        }
+        break;
+      }
+      __builtin_amdgcn_s_sleep(1);
+      val = sd_flag_poll(fp);
+      ready = __all(val >= need);
+    }
+    SD_TL_AT(g0, i, nt, 3);
+    // this lane's entries of slot(i): the next item's input order and this item's output order (the gather reads them
+    // from raw.e), so they are read on the last item too
+    sd_read_next<M>(nx, slot + (i & 1) * L, sslot + (i & 1) * 8 * SD_STRAD_N);
+    if (has_next) {
+      const int ni = i - 1;
+      const int same = *(const volatile __attribute__((address_space(3))) int32_t *)(
+          sds + sd_dfuo_offset<M>() + (threadIdx.x >> 6) * sd_dfuo_stride<M>() + 16 * M);
+      sd_issue_pipe<M>(raw, rs, nx, cp, nbo, r0b + (unsigned)i * rowb, rowb);
+      if (!same) {
+        sd_perm_dma_asm<M>(pk + (size_t)ni * L, lds_slot(ni));
+        if constexpr (sd_strad<M>()) sd_strad_dma(sk + (size_t)ni * 8 * SD_STRAD_N, lds_sslot(ni));
+      }
+      sd_dfuo_dma<M>(dfuo0 + (size_t)((unsigned)ni * dfuo_st), ni >= 1, ldsb);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) raw.e[q] = nx.e[q];
+    }
+    SD_TL_AT(g0, i, nt, 4);
+  }
+  __device__ __forceinline__ void late_drain() {
+#ifdef SD_TL_DRAIN
+    SD_TL_AT(g0, i, nt, 7);
+#endif
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    SD_TL_AT(g0, i, nt, 5);
+  }
+  // the previous item (cp, i + 1) is done: token(i + 1)
+  __device__ __forceinline__ void publish() {
+    if (sd_tid() == 0 && i != nt - 2)
+      __hip_atomic_store(dflag, nt - 2 - i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    stop_seen = sh->stop != 0;
+  }
+  __device__ __forceinline__ void store16(double *, int e, unsigned long long lo, unsigned long long hi) {
+    sd_store16<true>(reg + sob / 8, L * 8, e, lo, hi);
+  }
+  // as SdPipe::tail for a one-row workgroup
+  __device__ __forceinline__ void tail(bool empty, const double *outv) {
+    if (!has_next) return;
+    double v[8];
+    sd_take<M>(v, raw);
+    if ((sd_tid() & 63) == 0 && (raw.e[0].x >> 16) == 0) v[0] = empty ? INFINITY : outv[raw.e[0].x & 0xFFFFu];
+    const double xs = __hiloint2double((int)raw.sv.y, (int)raw.sv.x);
+    valid_next = sdt_stats<M, true>(*Pp, *Gp, k, cp, i - 1, v, raw.e, *sh, sds, nullptr, nullptr, raw.srank, xs);
+  }
+};
+
+// (the parameters are k_sdt_run's; nwg = K·B)
+template <int M>
+__global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run1(ProblemDev P_arg, LevelsDev Lv_arg, PyrGeom G,
+                                                               const uint32_t *__restrict__ perm_all, double *S_all,
+                                                               size_t kstride, int NB, uint16_t *__restrict__ UU_all,
+                                                               size_t uu_stride_k, int32_t *__restrict__ counters,
+                                                               int32_t *flags, int nwg, unsigned spin_limit,
+                                                               const double *__restrict__ df_all,
+                                                               const double *__restrict__ uo_all,
+                                                               const int32_t *__restrict__ same2,
+                                                               const uint16_t *__restrict__ strad) {
+  constexpr int L = 1 << (3 * M);
+  extern __shared__ __attribute__((aligned(16))) unsigned char sds[];
+  __shared__ SdtShared<(1 << (3 * M - 3)) / 64> sh;
+  // (vector registers for what only meets per-lane or double-precision operands: as k_sdt_run)
+  ProblemDev P = P_arg;
+  LevelsDev Lv = Lv_arg;
+  asm volatile("" : "+v"(P.dt), "+v"(Lv.beta), "+v"(Lv.inv_beta));
+  asm volatile("" : "+v"(counters), "+v"(spin_limit));
+  const int B = P.B, R = B + 1, nt = P.nt, tid = threadIdx.x;
+  const int FR = R * SDT_FLAG_STRIDE;
+  int32_t *done = flags, *loaded = flags + P.K * FR, *err = flags + 2 * P.K * FR;
+  const int k = (int)blockIdx.x / B, cp = 1 + (int)blockIdx.x - k * B;  // nwg = K·B: one row per workgroup
+  if (k >= P.K) return;
+  (void)nwg;
+  uint32_t *slot = reinterpret_cast<uint32_t *>(sds + sd_slot_offset<M>());
+  auto pslot = [&](int step) { return slot + (step & 1) * L; };
+  double *reg = S_all + (size_t)k * kstride;
+  SdPipe1<M> h;
+  h.cp = cp, h.nt = nt, h.k = k, h.g0 = k * R + cp;
+  h.spin_limit = spin_limit, h.rowb = (unsigned)L * 8u;
+  const unsigned bufb = (unsigned)R * h.rowb;
+  h.r0b = (unsigned)NB * bufb;
+  asm volatile("" : "+v"(err));
+  h.err = err;
+  h.pk = perm_all + (size_t)k * nt * L, h.slot = slot;
+  h.rs = __builtin_amdgcn_make_buffer_rsrc(reg, 0, (int)(h.r0b + (unsigned)nt * h.rowb), 0x00020000);
+  h.dfuo0 = sd_dfuo_src<M>(df_all + (size_t)k * nt * M, uo_all + (size_t)k * nt * M, same2 + (size_t)k * nt - 1);
+  h.dfuo_st = sd_dfuo_step<M>();
+  h.sds = sds, h.ldsb = sd_lds_addr(sds), h.sh = &sh;
+  h.sk = strad ? strad + (size_t)k * nt * 8 * SD_STRAD_N : nullptr;
+  h.sslot = reinterpret_cast<uint16_t *>(sds + sd_strad_offset<M>());
+  {  // the polls, once: this lane's flag and its token before the first item (early() steps it)
+    int32_t *dk = done + (size_t)k * FR, *lk = loaded + (size_t)k * FR;
+    h.lflag = lk + cp * SDT_FLAG_STRIDE, h.dflag = dk + cp * SDT_FLAG_STRIDE;
+    const int lane = tid & 63, s = lane < 32 ? lane + 1 : lane - 31;
+    h.fp = h.lflag;
+    h.need = INT32_MIN;
+    if (lane < 32) {
+      if (s <= 7 * M && cp - s >= 1) h.fp = dk + (cp - s) * SDT_FLAG_STRIDE, h.need = 0;  // token(nt - 2) - 1
+    } else {
+      if (s <= 7 * M && cp + s <= B) h.fp = lk + (cp + s) * SDT_FLAG_STRIDE, h.need = 1 - NB;  // token(nt + NB - 3) - 1
+    }
+    asm volatile("" : "+v"(h.lflag), "+v"(h.dflag));
+  }
+  asm volatile("" : "+v"(h.pk), "+v"(h.sk));
+  asm volatile("" : "+v"(h.r0b));
+  h.reg = reg;
+  if (tid == 0) {
+    sh.stop = 0;
+    sh.cnt[0] = sh.cnt[1] = sh.cnt[2] = sh.cnt[3] = 0;
+    sh.nlist[0] = sh.nlist[1] = sh.redo[0] = sh.redo[1] = 0;
+  }
+  // prologue (as k_sdt_run): both sphere orders of the first step, df / u_old, the first item's loads
+  sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 1) * L, h.lds_slot(nt - 1));
+  sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 2) * L, h.lds_slot(nt - 2));
+  if constexpr (sd_strad<M>()) {
+    sd_strad_dma(h.sk + (size_t)(nt - 1) * 8 * SD_STRAD_N, h.lds_sslot(nt - 1));
+    sd_strad_dma(h.sk + (size_t)(nt - 2) * 8 * SD_STRAD_N, h.lds_sslot(nt - 2));
+  }
+  sd_dfuo_dma<M>(h.dfuo0 + (size_t)((unsigned)(nt - 2) * h.dfuo_st), nt >= 3, h.ldsb);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  sd_bar();
+  sd_read_next<M>(h.nx, pslot(nt - 1), h.sslot + ((nt - 1) & 1) * 8 * SD_STRAD_N);
+  sd_issue_pipe<M>(h.raw, h.rs, h.nx, cp, (unsigned)((nt - 1) % NB) * bufb, h.r0b + (unsigned)(nt - 1) * h.rowb,
+                   h.rowb);
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // (vmcnt(0), seen by the compiler: see k_sdt_run)
+  h.Pp = &P, h.Gp = &G;
+  {
+    double v[8];
+    sd_take<M>(v, h.raw);
+    const double xs = __hiloint2double((int)h.raw.sv.y, (int)h.raw.sv.x);
+    h.valid_next = sdt_stats<M, true>(P, G, k, cp, nt - 2, v, h.raw.e, sh, sds, df_all, uo_all, h.raw.srank, xs);
+  }
+  // buffer i % NB's byte offset and the row's U row of step i, stepped down with i
+  const unsigned cprow = (unsigned)cp * h.rowb, wrapb = (unsigned)(NB - 1) * bufb;
+  h.nbo = (unsigned)((nt - 2) % NB) * bufb;
+  uint16_t *uu_i = UU_all + (size_t)k * uu_stride_k + (size_t)(nt - 2) * ((size_t)R * L) + (size_t)cp * L;
+  asm volatile("" : "+v"(uu_i));
+  int par = 0;
+  bool stop = false;
+  const int g = h.g0;  // timeline stamps
+  (void)g;
+  int i = nt - 2;
+#pragma nounroll
+  for (; i >= 0 && !stop; --i) {
+    h.i = i;
+    h.has_next = i >= 1;
+    h.sob = h.nbo + cprow;
+    SD_TL(0);
+    // everything but the previous item's five stores has landed (see k_sdt_run)
+    asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+#ifndef SD_TL_DRAIN
+    SD_TL(7);
+#endif
+    uint2 ein[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) ein[q] = h.raw.e[q];
+    sdt_body<M, true>(P, Lv, G, k, cp, i, h.valid_next, ein, pslot(i + 1), pslot(i), nullptr, uu_i, sh, sds, h, df_all,
+                      uo_all, par, h.raw.mask, h.raw.srank);
+    par ^= 1;
+    SD_TL(6);
+    stop = h.stop_seen;
+    h.nbo = h.nbo == 0 ? wrapb : h.nbo - bufb;
+    unsigned rows = (unsigned)R;
+    asm volatile("" : "+s"(rows));
+    uu_i = reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(uu_i) - rows * (unsigned)(L * sizeof(uint16_t)));
+  }
+  if (sd_tid() == 0) {
+    if (sh.cnt[0]) atomicAdd(&counters[0], sh.cnt[0]);
+    if (sh.cnt[1]) atomicAdd(&counters[1], sh.cnt[1]);
+    // diagnostics [4]: the items run (steps above i) whose write-after-read wait was armed: token(i' + NB - 1) > 0, i.e.
+    // i' < nt - NB, on a row with a row above it
+    const int armed = cp < B ? max(nt - NB - 1 - i, 0) : 0;
+    if (armed) atomicAdd(&counters[4], armed);
+    if (sh.cnt[3]) atomicAdd(&counters[5], sh.cnt[3]);
+  }
+  SD_FLUSH();
+  SD_TL_FLUSH(h.g0);
+}
+
 bool sdt_seam_lists(const PyrGeom &G) { return G.M == 4 && sd_strad<4>(); }
 
 bool sdt_supported(const PyrGeom &G) {
@@ -1879,8 +2143,9 @@ hipError_t launch_sdt_run(hipStream_t s, const ProblemDev &P, const LevelsDev &L
                           const uint32_t *perm, const int32_t *same2, const uint16_t *strad, double *S, size_t kstride,
                           int NB, uint16_t *UU,
                           size_t uu_stride_k, int32_t *counters, int32_t *flags, int nwg, unsigned spin_limit,
-                          size_t lds) {
+                          size_t lds, bool one_row) {
   if (!sdt_supported(G)) return hipErrorInvalidValue;
+  if (one_row && nwg != P.K * P.B) return hipErrorInvalidValue;  // k_sdt_run1: every workgroup owns one row
   // every workgroup must be resident at once (the row hand-off spins on other workgroups): the caller sizes the grid
   // to the CUs x resident workgroups per CU (sdt_run_blocks_per_cu); a dependency wait that times out anyway (another
   // process's kernels holding CUs) sets the error word and the host redoes the DP per step.  An ordinary launch, not a
@@ -1890,6 +2155,10 @@ hipError_t launch_sdt_run(hipStream_t s, const ProblemDev &P, const LevelsDev &L
                   (void *)&S,     (void *)&kstride,  (void *)&NB,        (void *)&UU,
                   (void *)&uu_stride_k, (void *)&counters, (void *)&flags, (void *)&nwg, (void *)&spin_limit,
                   (void *)&P.df,  (void *)&P.uold, (void *)&same2, (void *)&strad};
+  if (one_row) {
+    if (G.M == 4) return hipLaunchKernel((const void *)k_sdt_run1<4>, dim3(nwg), dim3(512), args, lds, s);
+    return hipLaunchKernel((const void *)k_sdt_run1<3>, dim3(nwg), dim3(64), args, lds, s);
+  }
   if (G.M == 4) return hipLaunchKernel((const void *)k_sdt_run<4>, dim3(nwg), dim3(512), args, lds, s);
   return hipLaunchKernel((const void *)k_sdt_run<3>, dim3(nwg), dim3(64), args, lds, s);
 }

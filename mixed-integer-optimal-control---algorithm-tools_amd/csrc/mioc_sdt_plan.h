@@ -10,6 +10,7 @@ namespace mioc {
 struct SdtPlan {
   bool persist = false;  // one persistent launch (k_sdt_run); else one launch per step over two staging buffers
   int nwg = 0;           // persistent: resident row workgroups, nwg / K per subproblem
+  bool one_row = false;  // persistent: nwg = K·B, every workgroup owns one row for the whole launch (k_sdt_run1)
   int nbuf = 2;          // staging buffers per subproblem
   size_t s_stride = 0;   // doubles of one staging buffer: (B + 1)·L
   size_t kstride = 0;    // doubles between two subproblems' staging blocks
@@ -52,6 +53,7 @@ inline SdtPlan sdt_stage_plan(size_t K, size_t nt, int B, size_t L, int M, int b
   }
   p.kstride = p.persist ? (size_t)p.nbuf * p.s_stride + nt * L : p.s_stride;
   if (p.persist && p.kstride * sizeof(double) >= (1ull << 32)) p.persist = false, p.kstride = p.s_stride;
+  p.one_row = p.persist && (size_t)p.nwg == K * (size_t)B;
   return p;
 }
 

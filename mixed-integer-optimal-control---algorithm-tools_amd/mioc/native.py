@@ -32,6 +32,7 @@ MIOC_ECOMPILE = -8
 MIOC_P_INF, MIOC_P_ONE, MIOC_P_INTLUT, MIOC_P_TABLE = 0, 1, 2, 3
 MIOC_OPT_ALGO, MIOC_OPT_TIMING, MIOC_OPT_PERSIST, MIOC_OPT_PRED_FMA = 1, 2, 3, 4
 MIOC_OPT_SPIN_LIMIT, MIOC_OPT_SDT_BUFFERS, MIOC_OPT_FSEP_SEGMENTS, MIOC_OPT_PINF_WALK = 5, 6, 7, 8
+MIOC_OPT_SDT_ROW_OWNER = 10
 MIOC_ALGO_AUTO, MIOC_ALGO_GENERIC, MIOC_ALGO_PINF, MIOC_ALGO_PYRAMID, MIOC_ALGO_SEPARABLE = 0, 1, 2, 3, 4
 MIOC_ALGO_FUSED, MIOC_ALGO_FUSED_SEPARABLE = 5, 6
 MIOC_ODE_FISHING, MIOC_ODE_DOUBLETANK, MIOC_ODE_VANDERPOL = 1, 2, 3
@@ -43,7 +44,8 @@ EXPORTED = [
     "mioc_version", "mioc_create", "mioc_destroy", "mioc_last_error", "mioc_set_option", "mioc_set_levels",
     "mioc_set_cost", "mioc_bellman", "mioc_backtrack", "mioc_bellman_batch_device",
     "mioc_backtrack_batch_device", "mioc_synchronize", "mioc_stream", "mioc_kernel_stats",
-    "mioc_reset_stats", "mioc_last_algo", "mioc_diagnostics", "mioc_get_argmin_table", "mioc_get_ranks_device",
+    "mioc_reset_stats", "mioc_last_algo", "mioc_last_sdt_driver", "mioc_diagnostics", "mioc_get_argmin_table",
+    "mioc_get_ranks_device",
     "mioc_pred", "mioc_pred_batch_device", "mioc_tv_device", "mioc_trm_decide_device", "mioc_batch_multi",
     "mioc_ode_eval_device", "mioc_rand_start_device", "mioc_backtrack_batch_budgets_device",
     "mioc_heat_setup", "mioc_heat_eval_device", "mioc_heat_eval",
@@ -103,6 +105,7 @@ def load_library(path=None):
                                     ctypes.POINTER(ctypes.c_char_p)]),
         "mioc_reset_stats": (i32, [vp]),
         "mioc_last_algo": (i32, [vp]),
+        "mioc_last_sdt_driver": (i32, [vp]),
         "mioc_diagnostics": (i32, [vp, vp, i32]),
         "mioc_get_argmin_table": (i32, [vp, i64, i64, vp]),
         "mioc_get_ranks_device": (i32, [vp, vp]),
@@ -577,6 +580,10 @@ class Context:
 
     def last_algo(self):
         return self.lib.mioc_last_algo(self.h)
+
+    def last_sdt_driver(self):
+        """The driver of the last separable DP: 0 per-step launches, 1 k_sdt_run, 2 the one-row k_sdt_run1."""
+        return self.lib.mioc_last_sdt_driver(self.h)
 
     def argmin_table(self, step, k=0):
         """U of step `step` in the reference layout: int32 (B+1, Lgrid), rank of the minimising source
