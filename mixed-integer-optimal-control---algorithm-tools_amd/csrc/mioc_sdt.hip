@@ -649,8 +649,9 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
     }
   };
   // the certified winners of the transform in o[] (FLAG: the counting transform, near ties listed for the exact scan)
-  auto winners = [&](auto flag_tag) {
+  auto winners = [&](auto flag_tag, auto all_tag) {
     constexpr bool FLAG = decltype(flag_tag)::value;
+    constexpr bool ALL = decltype(all_tag)::value;  // every target is inside the trust region (!highc: valid = 0xFF)
     unsigned listed = 0;
     int jx[8];
     double pv[8];
@@ -663,7 +664,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
       const int r = tid | (x << (3 * (M - 1))), j = jx[x];
       // the winners run only in a row that is not `empty`: it has a finite source, which reaches every target at a
       // finite distance, so every o[x] is finite here -- only the trust region decides
-      const bool fin = (valid >> x & 1) != 0;
+      const bool fin = ALL || (valid >> x & 1) != 0;
       const bool flg = FLAG && (__double2loint(o[x]) & SD_CNT) != 0;
       // d(l, j*) exactly: an unflagged finite o[x] is V_j* + d with V_j* = the stamp of Ψ_j* (the same expression
       // as the stamping above, payload j*), every term exact in the binade (garbage, unused, otherwise)
@@ -698,7 +699,12 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
   // order of step i (e0h: its entry) -- row B of every step: the one-target item below
   // (held in a vector register and read back as a scalar at each use: the row loop has no scalar register to spare)
   int onev = 0;
-  auto is_one = [&]() { return PERSIST && __builtin_amdgcn_readfirstlane(onev) != 0; };  // uniform
+  // highc: a target may lie outside the trust region.  A driver that fixes the row for the launch (Hooks::kRowClass)
+  // knows it from a scalar compare, B - c' < 7·M: at or above that every target is inside (b̃ <= 7·M in the persistent
+  // drivers' window), so the row has all L targets, is never a one-target row, reads nothing of the output order for
+  // the test, and its winners need no `valid`.  Any other driver does not know: today's code, as for highc.
+  const bool highc = !Hooks::kRowClass || P.B - cp < Smax;  // uniform
+  auto is_one = [&]() { return PERSIST && highc && __builtin_amdgcn_readfirstlane(onev) != 0; };  // uniform
   [[maybe_unused]] uint32_t e0h = 0;
   {
     double pmn, pmx;
@@ -720,7 +726,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
       // SD_FEW, more): the sphere order of step i ascends in b̃, so at most q levels have b̃ <= B - c' iff entry q has
       // b̃ > B - c' -- two broadcast reads in the same batch instead of eight ballots per wave (sdt_stats)
       [[maybe_unused]] uint32_t e0 = 0, e1 = 0, ef = 0;
-      if constexpr (PERSIST) {
+      if (PERSIST && highc) {
         static_assert(SD_FEW < L, "entry SD_FEW of the sphere order");
         e0 = pout[0];
         e1 = pout[1];  // exactly one target iff entry 0 is inside and entry 1 is not
@@ -739,7 +745,8 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
       pmx = mx[0];
       nf = cn[0] >> 16;
       nv = cn[0] & 0xFFFF;
-      if constexpr (PERSIST) {
+      if (PERSIST && !highc) nv = SD_FEW + 1;
+      if (PERSIST && highc) {
         nv = (int)(e0 >> 16) > P.B - cp ? 0 : (int)(ef >> 16) > P.B - cp ? SD_FEW : SD_FEW + 1;
         // (a row with at most SD_SPARSE finite sources stays with the sparse path, as before)
         onev = nv != 0 && (int)(e1 >> 16) > P.B - cp && pmn < INFINITY && nf > SD_SPARSE;
@@ -832,7 +839,10 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
         sh.redj[tid >> 6] = bj;
       }
     } else if (!direct && !sparse) {
-      winners(std::false_type{});
+      if (Hooks::kRowClass && !highc)
+        winners(std::false_type{}, std::true_type{});
+      else
+        winners(std::false_type{}, std::false_type{});
       if (__any(dmin <= tol) && lane == 0) sh.redo[par] = 1;
     } else {
 #pragma unroll
@@ -898,7 +908,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
     SD_STAMP(7);
     if (transform && sh.redo[par]) {  // uniform, rare: a near tie somewhere in the row -- the certified transform
       passes(std::true_type{});
-      list_targets(winners(std::true_type{}));
+      list_targets(winners(std::true_type{}, std::false_type{}));
       sd_bar();
       if (tid == 0) ++sh.cnt[3];
     }
@@ -1178,6 +1188,7 @@ __device__ __forceinline__ void sdt_rowB(const ProblemDev &P, const LevelsDev &L
 // per-step driver: no pipeline hooks
 struct SdHooksNone {
   static constexpr bool kOutOrderRegs = false;  // (see SdPipe1)
+  static constexpr bool kRowClass = false;      // (see SdPipe1)
   __device__ __forceinline__ void early() {}
   __device__ __forceinline__ void go() {}
   __device__ __forceinline__ void late_drain() {}
@@ -1469,9 +1480,14 @@ __device__ __forceinline__ void sd_read_next(SdNext &n, const uint32_t *pin, con
     n.se = pin[sd_seam_pos<M>(wv, (int)(n.sp & (L / NW - 1)))];
   }
 }
-template <int M>
+// lowc (workgroup-uniform): some source row c' - b̃ may be below 0.  The one-row driver passes c' <= 7·M, which it
+// decides once per launch: above it every source row is >= 1 (b̃ <= 7·M inside the driver's dependency window), so the
+// offsets are the row's own minus b̃ rows, with no three-way select, no row-0 array and only the straddle bit of the mask.
+// (CLS: the caller knows the class; without it lowc is the constant true and the code is the general form alone.)
+template <int M, bool CLS = false>
 __device__ __forceinline__ void sd_issue_pipe(SdRaw &w, __amdgpu_buffer_rsrc_t rs, const SdNext &n, int cp,
-                                              unsigned boff, unsigned r0, const unsigned rowb) {
+                                              unsigned boff, unsigned r0, const unsigned rowb, bool lowc_known = true) {
+  const bool lowc = !CLS || lowc_known;
   constexpr int L = 1 << (3 * M), T = L / 8, NW = T / 64;
   const int tid = threadIdx.x;
   uint2 e[4];
@@ -1486,16 +1502,28 @@ __device__ __forceinline__ void sd_issue_pipe(SdRaw &w, __amdgpu_buffer_rsrc_t r
   // below 0, and the second element wherever the pair does not straddle (it came with the first)
   constexpr unsigned OOB = 0xFFFFFFF0u;
   unsigned oa[4], ob[4], mask = 0;
+  if (!CLS || lowc) {
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int p2 = sd_p2<M>(tid, q);
-    const int ra = cp - (int)(e[q].x >> 16), rb = cp - (int)(e[q].y >> 16);
-    oa[q] = ra >= 1 ? boff + (unsigned)ra * rowb + (unsigned)p2 * 8u : ra == 0 ? r0 + (unsigned)p2 * 8u : OOB;
-    ob[q] = rb == ra ? OOB
-            : rb >= 1 ? boff + (unsigned)rb * rowb + (unsigned)(p2 + 1) * 8u
-            : rb == 0 ? r0 + (unsigned)(p2 + 1) * 8u
-                      : OOB;
-    mask |= ((unsigned)(ra < 0) | (unsigned)(rb < 0) << 1 | (unsigned)(ra != rb) << 2) << (3 * q);
+    for (int q = 0; q < 4; ++q) {
+      const int p2 = sd_p2<M>(tid, q);
+      const int ra = cp - (int)(e[q].x >> 16), rb = cp - (int)(e[q].y >> 16);
+      oa[q] = ra >= 1 ? boff + (unsigned)ra * rowb + (unsigned)p2 * 8u : ra == 0 ? r0 + (unsigned)p2 * 8u : OOB;
+      ob[q] = rb == ra ? OOB
+              : rb >= 1 ? boff + (unsigned)rb * rowb + (unsigned)(p2 + 1) * 8u
+              : rb == 0 ? r0 + (unsigned)(p2 + 1) * 8u
+                        : OOB;
+      mask |= ((unsigned)(ra < 0) | (unsigned)(rb < 0) << 1 | (unsigned)(ra != rb) << 2) << (3 * q);
+    }
+  } else {
+    const unsigned row = boff + (unsigned)cp * rowb;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int p2 = sd_p2<M>(tid, q);
+      const unsigned ba = e[q].x >> 16, bb = e[q].y >> 16;
+      oa[q] = row + (unsigned)p2 * 8u - ba * rowb;
+      ob[q] = bb == ba ? OOB : row + (unsigned)(p2 + 1) * 8u - bb * rowb;
+      mask |= (unsigned)(ba != bb) << (3 * q + 2);
+    }
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -1506,17 +1534,39 @@ __device__ __forceinline__ void sd_issue_pipe(SdRaw &w, __amdgpu_buffer_rsrc_t r
     const int P = sd_seam_pos<M>(tid >> 6, (int)(sp & (L / NW - 1)));
     const int rsr = cp - (int)(se >> 16);
     const bool has = sp != 0xFFFFu;
-    const unsigned osv =
-        !has || rsr < 0 ? OOB : rsr >= 1 ? boff + (unsigned)rsr * rowb + (unsigned)P * 8u : r0 + (unsigned)P * 8u;
+    // (the offset and the rank are chosen under the class branch, the load itself sits behind it: one load on every path)
+    unsigned osv;
+    int sr;
+    if (!CLS || lowc) {
+      osv = !has || rsr < 0 ? OOB : rsr >= 1 ? boff + (unsigned)rsr * rowb + (unsigned)P * 8u : r0 + (unsigned)P * 8u;
+      sr = has ? (int)(se & 0xFFFFu) | (rsr < 0 ? 0x10000 : 0) : -1;
+    } else {
+      osv = has ? boff + (unsigned)rsr * rowb + (unsigned)P * 8u : OOB;
+      sr = has ? (int)(se & 0xFFFFu) : -1;
+    }
     w.sv = __builtin_amdgcn_raw_buffer_load_b64(rs, osv, 0, 16);
-    w.srank = has ? (int)(se & 0xFFFFu) | (rsr < 0 ? 0x10000 : 0) : -1;
+    w.srank = sr;
   }
   w.mask = mask;
 }
 // this lane's eight values; (sd_strad) the second element of a straddling pair is a NaN here -- its value comes with
 // the lane that loaded it as a straddle element, which writes it after this lane (in-wave LDS order)
-template <int M>
-__device__ __forceinline__ void sd_take(double (&v)[8], const SdRaw &w) {
+// (lowc as in sd_issue_pipe: without it no source row is below 0 and mask bits 3q, 3q+1 are clear)
+template <int M, bool CLS = false>
+__device__ __forceinline__ void sd_take(double (&v)[8], const SdRaw &w, bool lowc = true) {
+  if (CLS && !lowc) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool str = (w.mask >> (3 * q + 2) & 1) != 0;
+      v[2 * q] = __hiloint2double((int)w.a[q].y, (int)w.a[q].x);
+      const double a1 = __hiloint2double((int)w.a[q].w, (int)w.a[q].z);
+      if constexpr (sd_strad<M>())
+        v[2 * q + 1] = str ? __longlong_as_double(0x7FF8000000000000ll) : a1;
+      else
+        v[2 * q + 1] = str ? __hiloint2double((int)w.b[q].y, (int)w.b[q].x) : a1;
+    }
+    return;
+  }
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const unsigned m = w.mask >> (3 * q);
@@ -1571,6 +1621,7 @@ template <int M>
 struct SdPipe {
   static constexpr int L = 1 << (3 * M);
   static constexpr bool kOutOrderRegs = false;  // (see SdPipe1)
+  static constexpr bool kRowClass = false;      // (see SdPipe1)
   // the current row (cp, step i) and the next one (ncp, step ni)
   int cp, i, ncp, ni;
   bool has_next;
@@ -1868,11 +1919,19 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P_ar
 //     diagnostics [4] -- items whose write-after-read wait was armed -- is arithmetic in nt and NB, formed at exit;
 //   * the next item's input order is this item's output order, so the entries go() reads for the next item's loads are
 //     the ones the gather after barrier 3 needs: it takes them from the registers (kOutOrderRegs);
-//   * the row's byte offsets, its flags and its U row step with i.
+//   * the row's byte offsets, its flags and its U row step with i;
+//   * the row's class is fixed: lowc (c' <= 7·M, a source row may be below 0) and highc (B - c' < 7·M, a target may lie
+//     outside the trust region) are scalar compares, and the one item loop branches on them where the general driver
+//     derives the same per item from per-lane data: the load offsets and sd_take (lowc), the one-target test and the
+//     winners' `valid` (highc).  One loop, one row start; the loads and stores sit behind the branches, not in them.
 template <int M>
 struct SdPipe1 {
   static constexpr int L = 1 << (3 * M);
   static constexpr bool kOutOrderRegs = true;
+  // the row's class is fixed for the launch: the row body and the loads branch on it (workgroup-uniform scalar compares
+  // on c' and B) instead of deriving it per item from per-lane data
+  static constexpr bool kRowClass = true;
+  __device__ __forceinline__ bool lowc() const { return cp <= 7 * M; }  // a source row c' - b̃ may be below 0
   int cp, i;  // the row (fixed) and the current step; the next item is (cp, i - 1)
   bool has_next;
   int nt, k, g0;
@@ -1944,7 +2003,7 @@ struct SdPipe1 {
       const int ni = i - 1;
       const int same = *(const volatile __attribute__((address_space(3))) int32_t *)(
           sds + sd_dfuo_offset<M>() + (threadIdx.x >> 6) * sd_dfuo_stride<M>() + 16 * M);
-      sd_issue_pipe<M>(raw, rs, nx, cp, nbo, r0b + (unsigned)i * rowb, rowb);
+      sd_issue_pipe<M, true>(raw, rs, nx, cp, nbo, r0b + (unsigned)i * rowb, rowb, lowc());
       if (!same) {
         sd_perm_dma_asm<M>(pk + (size_t)ni * L, lds_slot(ni));
         if constexpr (sd_strad<M>()) sd_strad_dma(sk + (size_t)ni * 8 * SD_STRAD_N, lds_sslot(ni));
@@ -1976,7 +2035,7 @@ struct SdPipe1 {
   __device__ __forceinline__ void tail(bool empty, const double *outv) {
     if (!has_next) return;
     double v[8];
-    sd_take<M>(v, raw);
+    sd_take<M, true>(v, raw, lowc());
     if ((sd_tid() & 63) == 0 && (raw.e[0].x >> 16) == 0) v[0] = empty ? INFINITY : outv[raw.e[0].x & 0xFFFFu];
     const double xs = __hiloint2double((int)raw.sv.y, (int)raw.sv.x);
     valid_next = sdt_stats<M, true>(*Pp, *Gp, k, cp, i - 1, v, raw.e, *sh, sds, nullptr, nullptr, raw.srank, xs);
@@ -2057,13 +2116,13 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run1(ProblemDev P_a
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   sd_bar();
   sd_read_next<M>(h.nx, pslot(nt - 1), h.sslot + ((nt - 1) & 1) * 8 * SD_STRAD_N);
-  sd_issue_pipe<M>(h.raw, h.rs, h.nx, cp, (unsigned)((nt - 1) % NB) * bufb, h.r0b + (unsigned)(nt - 1) * h.rowb,
-                   h.rowb);
+  sd_issue_pipe<M, true>(h.raw, h.rs, h.nx, cp, (unsigned)((nt - 1) % NB) * bufb,
+                         h.r0b + (unsigned)(nt - 1) * h.rowb, h.rowb, h.lowc());
   __builtin_amdgcn_s_waitcnt(0x0F70);  // (vmcnt(0), seen by the compiler: see k_sdt_run)
   h.Pp = &P, h.Gp = &G;
   {
     double v[8];
-    sd_take<M>(v, h.raw);
+    sd_take<M, true>(v, h.raw, h.lowc());
     const double xs = __hiloint2double((int)h.raw.sv.y, (int)h.raw.sv.x);
     h.valid_next = sdt_stats<M, true>(P, G, k, cp, nt - 2, v, h.raw.e, sh, sds, df_all, uo_all, h.raw.srank, xs);
   }
