@@ -384,6 +384,62 @@ int32_t mioc_ode_eval_device(mioc_ctx *ctx, int32_t problem, int64_t K, const do
  *   scratch    with d_df the stage state Y of every substep is stored, the same K * nt * m * ny doubles as above; a
  *              value-only call stores nothing.
  *
+ * Derived hooks.  mioc_ode_program_create_ad(..., derive, ...) generates the hooks named by the bits of `derive`
+ * (MIOC_ODE_DERIVE_FY / _FU / _GY / _GU) from F and G by forward-mode automatic differentiation, for every
+ * integrator; derive == 0 is mioc_ode_program_create_ex, the assembled source byte for byte.  With derive != 0 the
+ * text defines F and G as templates over the scalar type,
+ *   template <class T> __device__ void F(const double *p, int i, double t, const T *y, const T *x, T *f);
+ *   template <class T> __device__ T    G(const double *p, int i, double t, const T *y, const T *x);
+ * and so every helper that takes y or x.  The skeletons call them with T = double as before: the same expressions,
+ * so J is what the non-template text gives, bit for bit.  A generated hook is an ordinary __device__ function with
+ * the signature above, placed between the caller's text and the skeleton; it calls F or G once with
+ * T = mioc_ad::Dual<N> (a value v and N tangents d[0..N-1], all in registers):
+ *   Fy, Gy  N = ny; y[r] = (y_r, e_r), the r-th unit tangent; x[m] = (x_m, 0).  fy[r][c] = f[r].d[c], gy[r] = G.d[r]
+ *   Fu, Gu  N = nx; x[m] = (x_m, e_m); y[r] = (y_r, 0).                        fu[r][m] = f[r].d[m], gu[m] = G.d[m]
+ * and writes every entry of its output (a structural zero too).  The hooks not in `derive` are the caller's, their
+ * contract unchanged.  For every derived hook the head #defines MIOC_DERIVE_FY / _FU / _GY / _GU as 1 (none with
+ * derive == 0), so one text may carry hand-written hooks under `#ifndef MIOC_DERIVE_FY ... #endif` and serve any
+ * mask.  A hook both defined by hand and named in `derive` is a redefinition, a non-template F or G cannot be called
+ * with a Dual: both return MIOC_ECOMPILE with the compiler's message in the log.  The assembled text is the head with
+ * the MIOC_DERIVE_* macros, the dual type under `#line 1 "mioc_ad"`, the caller's text under `#line 1 "hooks"` (its
+ * diagnostics keep its own line numbers; the 1 MiB limit is the caller's text alone), the generated hooks under
+ * `#line 1 "mioc_ad_hooks"`, the skeleton.  The namespace mioc_ad exists only with derive != 0.
+ *   A generated hook is inlined at each of its call sites like a hand-written one (Heun / RK4: one per stage).  If
+ *   the kernel then needs more than the 256 architectural VGPRs (the compiler reports AGPRs in use or vector spills),
+ *   the text is compiled a second time with the generated hooks as functions that are called (the head then also
+ *   #defines MIOC_AD_NOINLINE): one body each, the same operations in the same order, so J and df do not change;
+ *   the log then starts with a line "mioc_ad: ... compiled as functions".
+ *   Dual<N> supports: implicit construction and assignment from double (all tangents 0.0); unary + and -;
+ *   + - * / and += -= *= /= for Dual o Dual, Dual o double, double o Dual (op= with a Dual on the left); the six
+ *   comparisons in the same three forms, on the values; sqrt exp log sin cos tan tanh atan fabs; pow(Dual, double),
+ *   pow(Dual, Dual); fmin, fmax (Dual, Dual), (Dual, double), (double, Dual); mioc_ad::value(a), the value of a
+ *   double or a Dual.  An integer literal converts like a double.
+ *   Tangent rules, for every k = 0..N-1 (v: the result's value, c: a double operand, which is never promoted to a
+ *   Dual -- its rule has no term for it; every sum left to right, no contraction, each line as written):
+ *     +a          d[k] = a.d[k]                        -a        v = -a.v; d[k] = -a.d[k]
+ *     a + b       d[k] = a.d[k] + b.d[k]               a + c, c + a   d[k] = a.d[k]
+ *     a - b       d[k] = a.d[k] - b.d[k]               a - c     d[k] = a.d[k];      c - a   d[k] = -a.d[k]
+ *     a * b       d[k] = a.d[k]*b.v + a.v*b.d[k]       a * c     d[k] = a.d[k]*c;    c * a   d[k] = c*a.d[k]
+ *     a / b       v = a.v/b.v; d[k] = (a.d[k] - v*b.d[k])/b.v
+ *     a / c       d[k] = a.d[k]/c                      c / a     v = c/a.v; d[k] = (-(v*a.d[k]))/a.v
+ *     a op= b     a = a op b
+ *     sqrt(a)     v = sqrt(a.v); d[k] = a.d[k]/(2.0*v)
+ *     exp(a)      v = exp(a.v);  d[k] = a.d[k]*v       log(a)    d[k] = a.d[k]/a.v
+ *     sin(a)      d[k] = a.d[k]*cos(a.v)               cos(a)    d[k] = a.d[k]*(-sin(a.v))
+ *     tan(a)      v = tan(a.v);  d[k] = a.d[k]*(1.0 + v*v)
+ *     tanh(a)     v = tanh(a.v); d[k] = a.d[k]*(1.0 - v*v)
+ *     atan(a)     d[k] = a.d[k]/(1.0 + a.v*a.v)
+ *     fabs(a)     d[k] = a.v < 0.0 ? -a.d[k] : a.d[k]
+ *     pow(a, c)   v = pow(a.v, c); d[k] = (c*pow(a.v, c - 1.0))*a.d[k]
+ *     pow(a, b)   v = pow(a.v, b.v); d[k] = (b.v*pow(a.v, b.v - 1.0))*a.d[k] + (v*log(a.v))*b.d[k]
+ *     fmin(a, b)  b.v < a.v ? b : a;   fmax(a, b)  b.v > a.v ? b : a   (a tie, and a NaN, take the first argument;
+ *                 a double that is taken has the tangents 0.0)
+ *   No product is ever folded because a tangent is zero: the build has no fast-math, and 0.0*v is not 0.0 for a
+ *   negative or non-finite v, so the constant argument's zero tangents are multiplied and added like any other.
+ *   Singular points propagate Inf or NaN as the hand-written -1/(2*sqrt(y)) does: sqrt at 0, log at 0, a / b at
+ *   b.v = 0, pow of a negative base with a Dual exponent (log of the base), pow(a, c) at a.v = 0 with c < 1; with
+ *   a.v = 0 and a.d[k] = 0 such a rule gives 0.0/0.0 or 0.0*Inf = NaN where the derivative's limit may exist.
+ *
  * mioc_ode_program_create needs no context and no GPU: it compiles for gfx950 and keeps the code object.  Limits:
  *   1 <= ny <= 8, 1 <= nx <= 8, 0 <= nparams <= 32, source text of at most 1 MiB (else MIOC_EINVAL).  A compile
  *   failure returns MIOC_ECOMPILE; the compiler's log (also the warnings of a successful compile) is copied into
@@ -413,6 +469,15 @@ int32_t mioc_ode_program_create(const char *hooks, int32_t ny, int32_t nx, int32
 #define MIOC_ODE_NEWTON_TOL 1e-10
 int32_t mioc_ode_program_create_ex(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t integrator,
                                    int32_t substeps, mioc_ode_program **out, char *log, int64_t log_cap);
+/* The same with the hooks named in `derive` generated from templated F and G (see "Derived hooks" above).  MIOC_EINVAL
+ * also for bits outside MIOC_ODE_DERIVE_ALL.  mioc_ode_program_create_ex(...) is _ad(..., derive = 0, ...). */
+#define MIOC_ODE_DERIVE_FY 1
+#define MIOC_ODE_DERIVE_FU 2
+#define MIOC_ODE_DERIVE_GY 4
+#define MIOC_ODE_DERIVE_GU 8
+#define MIOC_ODE_DERIVE_ALL 15
+int32_t mioc_ode_program_create_ad(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t integrator,
+                                   int32_t substeps, int32_t derive, mioc_ode_program **out, char *log, int64_t log_cap);
 int32_t mioc_ode_program_destroy(mioc_ode_program *prog);
 int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t K, const double *d_x, int64_t nt,
                                      double T0, double T1, const double *state0, const double *params, double *d_J,

@@ -239,9 +239,10 @@ end
 
 const ODE_INTEGRATORS = Dict(:euler => Int32(0), :heun => Int32(1), :rk4 => Int32(2), :beuler => Int32(16),
                              :midpoint => Int32(17))  # MIOC_ODE_INT_*
+const ODE_DERIVE = Dict(:Fy => Int32(1), :Fu => Int32(2), :Gy => Int32(4), :Gu => Int32(8))  # MIOC_ODE_DERIVE_*
 
 """
-    ode_program_create(hooks, ny, nx, nparams; integrator = :euler, substeps = 1) -> Ptr{Cvoid}
+    ode_program_create(hooks, ny, nx, nparams; integrator = :euler, substeps = 1, derive = Symbol[]) -> Ptr{Cvoid}
 
 Compile the hook text (needs no context and no GPU).  A compile failure raises an error carrying the compiler's log,
 whose diagnostics name the text's own lines (`hooks:3:…`).  mioc_ode_program_create_ex: `:euler` is the reference's
@@ -252,16 +253,22 @@ with `substeps` likewise: Newton's method per substep on the device (at most 12 
 gradient by the implicit function theorem; a restart whose iteration fails has NaN for J and its df row
 (include/mioc.h, "Implicit integrators").
 The program carries both; `ode_program_eval_device!` is unchanged.
+`derive` (mioc_ode_program_create_ad): `:all` or a collection of `:Fy`, `:Fu`, `:Gy`, `:Gu`, the hooks that the library
+generates from F and G by forward-mode AD; the text then defines F and G as templates over the scalar type and only
+the other hooks by hand (include/mioc.h, "Derived hooks").  Empty: all six hooks are the text's, as before.
 """
 function ode_program_create(hooks::String, ny::Integer, nx::Integer, nparams::Integer; integrator::Symbol = :euler,
-                            substeps::Integer = 1)
+                            substeps::Integer = 1, derive = Symbol[])
     haskey(ODE_INTEGRATORS, integrator) || error("integrator must be :euler, :heun, :rk4, :beuler or :midpoint")
+    names = derive === :all ? collect(keys(ODE_DERIVE)) : collect(derive)
+    all(n -> haskey(ODE_DERIVE, n), names) || error("derive must be :all or a collection of :Fy, :Fu, :Gy, :Gu")
+    mask = reduce(|, (ODE_DERIVE[n] for n in names); init = Int32(0))
     r = Ref{Ptr{Cvoid}}(C_NULL)
     log = zeros(UInt8, 1 << 16)
-    rc = ccall((:mioc_ode_program_create_ex, libmioc), Int32,
-               (Cstring, Int32, Int32, Int32, Int32, Int32, Ptr{Ptr{Cvoid}}, Ptr{UInt8}, Int64), hooks, ny, nx, nparams,
-               ODE_INTEGRATORS[integrator], substeps, r, log, length(log))
-    rc == MIOC_OK || error("mioc_ode_program_create_ex failed with $rc:\n" * unsafe_string(pointer(log)))
+    rc = ccall((:mioc_ode_program_create_ad, libmioc), Int32,
+               (Cstring, Int32, Int32, Int32, Int32, Int32, Int32, Ptr{Ptr{Cvoid}}, Ptr{UInt8}, Int64), hooks, ny, nx,
+               nparams, ODE_INTEGRATORS[integrator], substeps, mask, r, log, length(log))
+    rc == MIOC_OK || error("mioc_ode_program_create_ad failed with $rc:\n" * unsafe_string(pointer(log)))
     r[]
 end
 

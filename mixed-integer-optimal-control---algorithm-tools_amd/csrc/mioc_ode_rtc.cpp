@@ -17,11 +17,16 @@
 // The program carries integrator and substeps; the Euler skeleton and what it compiles to are untouched.
 // MIOC_ODE_INT_BEULER / _MIDPOINT are the one-stage implicit schemes (kSkeletonTheta): Newton with an in-register
 // Gaussian elimination forward, one transposed solve per substep backward.
+//
+// mioc_ode_program_create_ad generates Fy / Fu / Gy / Gu from templated F and G with a dual-number type (kAdPrelude,
+// kAdHooks) that is compiled into the same kernel; the skeletons and the launch are the same, and with derive == 0 so
+// is the source text.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -35,6 +40,8 @@ namespace {
 constexpr int kMaxNY = 8, kMaxNX = 8, kMaxNP = 32, kMaxSubsteps = 64;
 constexpr size_t kMaxSource = 1u << 20;
 const char *const kKernelName = "mioc_ode_program_kernel";
+const char *const kNoinlineNote =
+    "mioc_ad: with the generated hooks inlined the kernel needs more than 256 VGPRs; they are compiled as functions\n";
 
 // The skeleton follows the user text.  NY, NX, NP are #defined in front of both.
 const char *const kSkeleton = R"SKEL(
@@ -454,6 +461,298 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
 }
 )SKEL";
 
+// The forward-mode AD prelude of mioc_ode_program_create_ad (derive != 0): mioc_ad::Dual<N>, a value and N tangents,
+// all members indexed by constants under full unrolling, so a Dual lives in registers.  It stands in front of the
+// caller's text, which defines F and G as templates over the scalar type; argument-dependent lookup resolves
+// sqrt(T), fmin(T, T), ... to ::sqrt for T = double and to the overloads below for a Dual.  Every tangent rule and its
+// rounding order is written out in include/mioc.h ("Derived hooks"); a double operand is never promoted to a Dual, and
+// no product with a zero tangent is folded (no fast-math: 0.0 * v is not 0.0 for a non-finite or negative v).
+const char *const kAdPrelude = R"SKEL(
+namespace mioc_ad {
+template <int N>
+struct Dual {
+  double v;
+  double d[N];
+  Dual() = default;
+  __device__ __forceinline__ Dual(double c) : v(c) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) d[k] = 0.0;
+  }
+};
+__device__ __forceinline__ double value(double a) { return a; }
+template <int N> __device__ __forceinline__ double value(const Dual<N> &a) { return a.v; }
+
+#define MIOC_AD_FN template <int N> __device__ __forceinline__ Dual<N>
+#define MIOC_AD_EACH _Pragma("unroll") for (int k = 0; k < N; ++k)
+MIOC_AD_FN operator+(const Dual<N> &a) { return a; }
+MIOC_AD_FN operator-(const Dual<N> &a) {
+  Dual<N> r;
+  r.v = -a.v;
+  MIOC_AD_EACH r.d[k] = -a.d[k];
+  return r;
+}
+MIOC_AD_FN operator+(const Dual<N> &a, const Dual<N> &b) {
+  Dual<N> r;
+  r.v = a.v + b.v;
+  MIOC_AD_EACH r.d[k] = a.d[k] + b.d[k];
+  return r;
+}
+MIOC_AD_FN operator+(const Dual<N> &a, double b) {
+  Dual<N> r;
+  r.v = a.v + b;
+  MIOC_AD_EACH r.d[k] = a.d[k];
+  return r;
+}
+MIOC_AD_FN operator+(double a, const Dual<N> &b) {
+  Dual<N> r;
+  r.v = a + b.v;
+  MIOC_AD_EACH r.d[k] = b.d[k];
+  return r;
+}
+MIOC_AD_FN operator-(const Dual<N> &a, const Dual<N> &b) {
+  Dual<N> r;
+  r.v = a.v - b.v;
+  MIOC_AD_EACH r.d[k] = a.d[k] - b.d[k];
+  return r;
+}
+MIOC_AD_FN operator-(const Dual<N> &a, double b) {
+  Dual<N> r;
+  r.v = a.v - b;
+  MIOC_AD_EACH r.d[k] = a.d[k];
+  return r;
+}
+MIOC_AD_FN operator-(double a, const Dual<N> &b) {
+  Dual<N> r;
+  r.v = a - b.v;
+  MIOC_AD_EACH r.d[k] = -b.d[k];
+  return r;
+}
+MIOC_AD_FN operator*(const Dual<N> &a, const Dual<N> &b) {
+  Dual<N> r;
+  r.v = a.v * b.v;
+  MIOC_AD_EACH r.d[k] = a.d[k] * b.v + a.v * b.d[k];
+  return r;
+}
+MIOC_AD_FN operator*(const Dual<N> &a, double b) {
+  Dual<N> r;
+  r.v = a.v * b;
+  MIOC_AD_EACH r.d[k] = a.d[k] * b;
+  return r;
+}
+MIOC_AD_FN operator*(double a, const Dual<N> &b) {
+  Dual<N> r;
+  r.v = a * b.v;
+  MIOC_AD_EACH r.d[k] = a * b.d[k];
+  return r;
+}
+MIOC_AD_FN operator/(const Dual<N> &a, const Dual<N> &b) {
+  Dual<N> r;
+  r.v = a.v / b.v;
+  MIOC_AD_EACH r.d[k] = (a.d[k] - r.v * b.d[k]) / b.v;
+  return r;
+}
+MIOC_AD_FN operator/(const Dual<N> &a, double b) {
+  Dual<N> r;
+  r.v = a.v / b;
+  MIOC_AD_EACH r.d[k] = a.d[k] / b;
+  return r;
+}
+MIOC_AD_FN operator/(double a, const Dual<N> &b) {
+  Dual<N> r;
+  r.v = a / b.v;
+  MIOC_AD_EACH r.d[k] = (-(r.v * b.d[k])) / b.v;
+  return r;
+}
+#define MIOC_AD_ASSIGN(op)                                                                                   \
+  template <int N> __device__ __forceinline__ Dual<N> &operator op##=(Dual<N> &a, const Dual<N> &b) {        \
+    a = a op b;                                                                                              \
+    return a;                                                                                                \
+  }                                                                                                          \
+  template <int N> __device__ __forceinline__ Dual<N> &operator op##=(Dual<N> &a, double b) {                \
+    a = a op b;                                                                                              \
+    return a;                                                                                                \
+  }
+MIOC_AD_ASSIGN(+)
+MIOC_AD_ASSIGN(-)
+MIOC_AD_ASSIGN(*)
+MIOC_AD_ASSIGN(/)
+#undef MIOC_AD_ASSIGN
+#define MIOC_AD_COMPARE(op)                                                                                  \
+  template <int N> __device__ __forceinline__ bool operator op(const Dual<N> &a, const Dual<N> &b) {         \
+    return a.v op b.v;                                                                                       \
+  }                                                                                                          \
+  template <int N> __device__ __forceinline__ bool operator op(const Dual<N> &a, double b) { return a.v op b; } \
+  template <int N> __device__ __forceinline__ bool operator op(double a, const Dual<N> &b) { return a op b.v; }
+MIOC_AD_COMPARE(<)
+MIOC_AD_COMPARE(<=)
+MIOC_AD_COMPARE(>)
+MIOC_AD_COMPARE(>=)
+MIOC_AD_COMPARE(==)
+MIOC_AD_COMPARE(!=)
+#undef MIOC_AD_COMPARE
+MIOC_AD_FN sqrt(const Dual<N> &a) {
+  Dual<N> r;
+  r.v = ::sqrt(a.v);
+  const double g = 2.0 * r.v;
+  MIOC_AD_EACH r.d[k] = a.d[k] / g;
+  return r;
+}
+MIOC_AD_FN exp(const Dual<N> &a) {
+  Dual<N> r;
+  r.v = ::exp(a.v);
+  MIOC_AD_EACH r.d[k] = a.d[k] * r.v;
+  return r;
+}
+MIOC_AD_FN log(const Dual<N> &a) {
+  Dual<N> r;
+  r.v = ::log(a.v);
+  MIOC_AD_EACH r.d[k] = a.d[k] / a.v;
+  return r;
+}
+MIOC_AD_FN sin(const Dual<N> &a) {
+  Dual<N> r;
+  r.v = ::sin(a.v);
+  const double g = ::cos(a.v);
+  MIOC_AD_EACH r.d[k] = a.d[k] * g;
+  return r;
+}
+MIOC_AD_FN cos(const Dual<N> &a) {
+  Dual<N> r;
+  r.v = ::cos(a.v);
+  const double g = -::sin(a.v);
+  MIOC_AD_EACH r.d[k] = a.d[k] * g;
+  return r;
+}
+MIOC_AD_FN tan(const Dual<N> &a) {
+  Dual<N> r;
+  r.v = ::tan(a.v);
+  const double g = 1.0 + r.v * r.v;
+  MIOC_AD_EACH r.d[k] = a.d[k] * g;
+  return r;
+}
+MIOC_AD_FN tanh(const Dual<N> &a) {
+  Dual<N> r;
+  r.v = ::tanh(a.v);
+  const double g = 1.0 - r.v * r.v;
+  MIOC_AD_EACH r.d[k] = a.d[k] * g;
+  return r;
+}
+MIOC_AD_FN atan(const Dual<N> &a) {
+  Dual<N> r;
+  r.v = ::atan(a.v);
+  const double g = 1.0 + a.v * a.v;
+  MIOC_AD_EACH r.d[k] = a.d[k] / g;
+  return r;
+}
+MIOC_AD_FN fabs(const Dual<N> &a) {
+  Dual<N> r;
+  r.v = ::fabs(a.v);
+  MIOC_AD_EACH r.d[k] = a.v < 0.0 ? -a.d[k] : a.d[k];
+  return r;
+}
+MIOC_AD_FN pow(const Dual<N> &a, double b) {
+  Dual<N> r;
+  r.v = ::pow(a.v, b);
+  const double g = b * ::pow(a.v, b - 1.0);
+  MIOC_AD_EACH r.d[k] = g * a.d[k];
+  return r;
+}
+MIOC_AD_FN pow(const Dual<N> &a, const Dual<N> &b) {
+  Dual<N> r;
+  r.v = ::pow(a.v, b.v);
+  const double g = b.v * ::pow(a.v, b.v - 1.0), e = r.v * ::log(a.v);
+  MIOC_AD_EACH r.d[k] = g * a.d[k] + e * b.d[k];
+  return r;
+}
+MIOC_AD_FN fmin(const Dual<N> &a, const Dual<N> &b) { return b.v < a.v ? b : a; }
+MIOC_AD_FN fmin(const Dual<N> &a, double b) { return b < a.v ? Dual<N>(b) : a; }
+MIOC_AD_FN fmin(double a, const Dual<N> &b) { return b.v < a ? b : Dual<N>(a); }
+MIOC_AD_FN fmax(const Dual<N> &a, const Dual<N> &b) { return b.v > a.v ? b : a; }
+MIOC_AD_FN fmax(const Dual<N> &a, double b) { return b > a.v ? Dual<N>(b) : a; }
+MIOC_AD_FN fmax(double a, const Dual<N> &b) { return b.v > a ? b : Dual<N>(a); }
+#undef MIOC_AD_EACH
+#undef MIOC_AD_FN
+}  // namespace mioc_ad
+)SKEL";
+
+// The generated hooks: F or G once with T = mioc_ad::Dual<N>, the unit tangents on y (Fy, Gy: N = NY) or on x (Fu,
+// Gu: N = NX), the other argument constant.  Every entry of the output is written.  Each stands under the guard macro
+// that the head defines for a derived hook.  MIOC_AD_NOINLINE (the second compile of mioc_ode_program_create_ad) makes
+// them functions that are called: one body each, where the Heun / RK4 skeleton would inline one per stage.
+const char *const kAdHooks = R"SKEL(
+#ifdef MIOC_AD_NOINLINE
+#define MIOC_AD_HOOK __device__ __attribute__((noinline))
+#else
+#define MIOC_AD_HOOK __device__
+#endif
+#ifdef MIOC_DERIVE_FY
+MIOC_AD_HOOK void Fy(const double *p, int i, double t, const double *y, const double *x, double (*fy)[NY]) {
+  mioc_ad::Dual<NY> yd[NY], xd[NX], fd[NY];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) {
+    yd[r] = y[r];
+    yd[r].d[r] = 1.0;
+  }
+#pragma unroll
+  for (int m = 0; m < NX; ++m) xd[m] = x[m];
+  F(p, i, t, (const mioc_ad::Dual<NY> *)yd, (const mioc_ad::Dual<NY> *)xd, fd);
+#pragma unroll
+  for (int r = 0; r < NY; ++r) {
+#pragma unroll
+    for (int c = 0; c < NY; ++c) fy[r][c] = fd[r].d[c];
+  }
+}
+#endif
+#ifdef MIOC_DERIVE_FU
+MIOC_AD_HOOK void Fu(const double *p, int i, double t, const double *y, const double *x, double (*fu)[NX]) {
+  mioc_ad::Dual<NX> yd[NY], xd[NX], fd[NY];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) yd[r] = y[r];
+#pragma unroll
+  for (int m = 0; m < NX; ++m) {
+    xd[m] = x[m];
+    xd[m].d[m] = 1.0;
+  }
+  F(p, i, t, (const mioc_ad::Dual<NX> *)yd, (const mioc_ad::Dual<NX> *)xd, fd);
+#pragma unroll
+  for (int r = 0; r < NY; ++r) {
+#pragma unroll
+    for (int m = 0; m < NX; ++m) fu[r][m] = fd[r].d[m];
+  }
+}
+#endif
+#ifdef MIOC_DERIVE_GY
+MIOC_AD_HOOK void Gy(const double *p, int i, double t, const double *y, const double *x, double *gy) {
+  mioc_ad::Dual<NY> yd[NY], xd[NX];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) {
+    yd[r] = y[r];
+    yd[r].d[r] = 1.0;
+  }
+#pragma unroll
+  for (int m = 0; m < NX; ++m) xd[m] = x[m];
+  const mioc_ad::Dual<NY> g = G(p, i, t, (const mioc_ad::Dual<NY> *)yd, (const mioc_ad::Dual<NY> *)xd);
+#pragma unroll
+  for (int r = 0; r < NY; ++r) gy[r] = g.d[r];
+}
+#endif
+#ifdef MIOC_DERIVE_GU
+MIOC_AD_HOOK void Gu(const double *p, int i, double t, const double *y, const double *x, double *gu) {
+  mioc_ad::Dual<NX> yd[NY], xd[NX];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) yd[r] = y[r];
+#pragma unroll
+  for (int m = 0; m < NX; ++m) {
+    xd[m] = x[m];
+    xd[m].d[m] = 1.0;
+  }
+  const mioc_ad::Dual<NX> g = G(p, i, t, (const mioc_ad::Dual<NX> *)yd, (const mioc_ad::Dual<NX> *)xd);
+#pragma unroll
+  for (int m = 0; m < NX; ++m) gu[m] = g.d[m];
+}
+#endif
+)SKEL";
+
 // ---- hiprtc, loaded at the first mioc_ode_program_create -------------------------------------------------------
 struct Rtc {
   bool ok = false;
@@ -505,6 +804,38 @@ int fail(mioc_ctx *ctx, int code, const std::string &msg) {
   return code;
 }
 
+// The number after `key` in the compiler's resource remarks of the kernel (-Rpass-analysis=kernel-resource-usage), -1
+// if there is none.
+long remark_value(const std::string &log, const char *key) {
+  size_t at = log.find(std::string("Function Name: ") + kKernelName);
+  if (at == std::string::npos) return -1;
+  at = log.find(key, at);
+  if (at == std::string::npos) return -1;
+  return std::strtol(log.c_str() + at + std::strlen(key), nullptr, 10);
+}
+
+// Does the kernel need more than the 256 architectural VGPRs (AGPRs as spill space, or vector spills to scratch)?
+bool over_vgpr_file(const std::string &log) {
+  return remark_value(log, " AGPRs: ") > 0 || remark_value(log, " VGPRs Spill: ") > 0;
+}
+
+// The log without the remarks.  A diagnostic is its head line ("file:line:col: kind: ...") and the indented source lines
+// under it; a note belongs to the diagnostic before it.  So a clean compile leaves an empty log as before.
+std::string without_remarks(const std::string &log) {
+  std::string out;
+  bool drop = false;
+  for (size_t at = 0; at < log.size();) {
+    size_t end = log.find('\n', at);
+    end = end == std::string::npos ? log.size() : end + 1;
+    const std::string line = log.substr(at, end - at);
+    if (line[0] != ' ' && line[0] != '\n' && line.find(": note: ") == std::string::npos)
+      drop = line.find(": remark: ") != std::string::npos;
+    if (!drop) out += line;
+    at = end;
+  }
+  return out;
+}
+
 }  // namespace
 
 struct mioc_ode_program {
@@ -529,6 +860,12 @@ int32_t mioc_ode_program_create(const char *hooks, int32_t ny, int32_t nx, int32
 
 int32_t mioc_ode_program_create_ex(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t integrator,
                                    int32_t substeps, mioc_ode_program **out, char *log, int64_t log_cap) {
+  return mioc_ode_program_create_ad(hooks, ny, nx, nparams, integrator, substeps, 0, out, log, log_cap);
+}
+
+int32_t mioc_ode_program_create_ad(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t integrator,
+                                   int32_t substeps, int32_t derive, mioc_ode_program **out, char *log,
+                                   int64_t log_cap) {
   put_log(log, log_cap, "", 0);
   if (!out) return MIOC_EINVAL;
   *out = nullptr;
@@ -537,6 +874,7 @@ int32_t mioc_ode_program_create_ex(const char *hooks, int32_t ny, int32_t nx, in
   if (integrator != MIOC_ODE_INT_EULER && integrator != MIOC_ODE_INT_HEUN && integrator != MIOC_ODE_INT_RK4 && !implicit)
     return MIOC_EINVAL;
   if (substeps < 1 || substeps > kMaxSubsteps || (integrator == MIOC_ODE_INT_EULER && substeps != 1)) return MIOC_EINVAL;
+  if (derive & ~MIOC_ODE_DERIVE_ALL) return MIOC_EINVAL;
   // the reference scheme keeps its own skeleton and its head, so its source text is what it was
   const char *const skeleton = integrator == MIOC_ODE_INT_EULER ? kSkeleton : implicit ? kSkeletonTheta : kSkeletonRK;
   const size_t len = strnlen(hooks, kMaxSource + 1);
@@ -550,60 +888,92 @@ int32_t mioc_ode_program_create_ex(const char *hooks, int32_t ny, int32_t nx, in
   try {
     char head[128];
     if (integrator == MIOC_ODE_INT_EULER)
-      std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n#line 1 \"hooks\"\n", (int)ny,
-                    (int)nx, (int)nparams);
+      std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n", (int)ny, (int)nx, (int)nparams);
     else if (implicit)  // TH: theta, 1 for backward Euler and 1/2 for the implicit midpoint rule
-      std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n#define TH %s\n#line 1 \"hooks\"\n",
-                    (int)ny, (int)nx, (int)nparams, integrator == MIOC_ODE_INT_BEULER ? "1.0" : "0.5");
+      std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n#define TH %s\n", (int)ny, (int)nx,
+                    (int)nparams, integrator == MIOC_ODE_INT_BEULER ? "1.0" : "0.5");
     else  // NS: the stage count, which selects the tableau
-      std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n#define NS %d\n#line 1 \"hooks\"\n",
-                    (int)ny, (int)nx, (int)nparams, integrator == MIOC_ODE_INT_HEUN ? 2 : 4);
-    src.reserve(len + std::strlen(skeleton) + 256);
+      std::snprintf(head, sizeof head, "#define NY %d\n#define NX %d\n#define NP %d\n#define NS %d\n", (int)ny, (int)nx,
+                    (int)nparams, integrator == MIOC_ODE_INT_HEUN ? 2 : 4);
+    src.reserve(len + std::strlen(skeleton) + (derive ? std::strlen(kAdPrelude) + std::strlen(kAdHooks) : 0) + 512);
     src = head;
+    if (derive) {  // the guard macros and the dual type in front of the caller's text; derive == 0 adds no byte
+      if (derive & MIOC_ODE_DERIVE_FY) src += "#define MIOC_DERIVE_FY 1\n";
+      if (derive & MIOC_ODE_DERIVE_FU) src += "#define MIOC_DERIVE_FU 1\n";
+      if (derive & MIOC_ODE_DERIVE_GY) src += "#define MIOC_DERIVE_GY 1\n";
+      if (derive & MIOC_ODE_DERIVE_GU) src += "#define MIOC_DERIVE_GU 1\n";
+      src += "#line 1 \"mioc_ad\"";
+      src += kAdPrelude;
+    }
+    src += "#line 1 \"hooks\"\n";
     src.append(hooks, len);
+    if (derive) {  // the generated hooks between the caller's text and the skeleton
+      src += "\n#line 1 \"mioc_ad_hooks\"";
+      src += kAdHooks;
+    }
     src += "\n#line 1 \"mioc_ode_program_skeleton\"";
     src += skeleton;
   } catch (const std::bad_alloc &) {
     return MIOC_ENOMEM;
   }
-  hiprtcProgram prog = nullptr;
-  if (R.create(&prog, src.c_str(), "mioc_ode_program.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
-    const char msg[] = "hiprtcCreateProgram failed";
-    put_log(log, log_cap, msg, sizeof msg - 1);
-    return MIOC_ECOMPILE;
-  }
-  // the flags of csrc/Makefile that bear on the arithmetic: no FMA contraction, no fast-math
-  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math"};
-  const hiprtcResult rc = R.compile(prog, (int)(sizeof opts / sizeof opts[0]), opts);
+  // the flags of csrc/Makefile that bear on the arithmetic: no FMA contraction, no fast-math.  With derived hooks the
+  // compiler also reports the kernel's registers (remarks, taken out of the log again): a kernel that needs more than
+  // the 256 architectural VGPRs with every generated hook inlined at each of its call sites is compiled a second time
+  // with the generated hooks as functions (MIOC_AD_NOINLINE), one body each however many stages call it.
+  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math",
+                        "-Rpass-analysis=kernel-resource-usage"};
+  const int nopts = derive ? 5 : 4;
   int ret = MIOC_OK;
-  try {
-    size_t ln = 0;
-    if (log && log_cap > 0 && R.log_size(prog, &ln) == HIPRTC_SUCCESS && ln > 1) {
-      std::vector<char> buf(ln + 1, '\0');
-      if (R.log(prog, buf.data()) == HIPRTC_SUCCESS) put_log(log, log_cap, buf.data(), strnlen(buf.data(), ln));
+  for (int pass = 0; pass < 2; ++pass) {
+    hiprtcProgram prog = nullptr;
+    if (R.create(&prog, src.c_str(), "mioc_ode_program.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
+      const char msg[] = "hiprtcCreateProgram failed";
+      put_log(log, log_cap, msg, sizeof msg - 1);
+      return MIOC_ECOMPILE;
     }
-    if (rc != HIPRTC_SUCCESS) {
-      ret = MIOC_ECOMPILE;
-    } else {
-      size_t cn = 0;
-      mioc_ode_program *p = new mioc_ode_program;
-      p->ny = ny, p->nx = nx, p->np = nparams;
-      p->integrator = integrator, p->substeps = substeps;
-      if (R.code_size(prog, &cn) != HIPRTC_SUCCESS || cn == 0) {
-        ret = MIOC_ECOMPILE;
-      } else {
-        p->code.resize(cn);
-        if (R.code(prog, p->code.data()) != HIPRTC_SUCCESS) ret = MIOC_ECOMPILE;
+    const hiprtcResult rc = R.compile(prog, nopts, opts);
+    bool again = false;
+    ret = MIOC_OK;
+    try {
+      size_t ln = 0;
+      std::string text;
+      if (R.log_size(prog, &ln) == HIPRTC_SUCCESS && ln > 1) {
+        std::vector<char> buf(ln + 1, '\0');
+        if (R.log(prog, buf.data()) == HIPRTC_SUCCESS) text.assign(buf.data(), strnlen(buf.data(), ln));
       }
-      if (ret == MIOC_OK)
-        *out = p;
-      else
-        delete p;
+      if (derive) {
+        again = pass == 0 && rc == HIPRTC_SUCCESS && over_vgpr_file(text);
+        text = without_remarks(text);
+        if (pass == 1) text.insert(0, kNoinlineNote);
+      }
+      put_log(log, log_cap, text.c_str(), text.size());
+      if (rc != HIPRTC_SUCCESS) {
+        ret = MIOC_ECOMPILE;
+      } else if (again) {
+        src.insert(0, "#define MIOC_AD_NOINLINE 1\n");
+      } else {
+        size_t cn = 0;
+        mioc_ode_program *p = new mioc_ode_program;
+        p->ny = ny, p->nx = nx, p->np = nparams;
+        p->integrator = integrator, p->substeps = substeps;
+        if (R.code_size(prog, &cn) != HIPRTC_SUCCESS || cn == 0) {
+          ret = MIOC_ECOMPILE;
+        } else {
+          p->code.resize(cn);
+          if (R.code(prog, p->code.data()) != HIPRTC_SUCCESS) ret = MIOC_ECOMPILE;
+        }
+        if (ret == MIOC_OK)
+          *out = p;
+        else
+          delete p;
+      }
+    } catch (const std::bad_alloc &) {
+      ret = MIOC_ENOMEM;
+      again = false;
     }
-  } catch (const std::bad_alloc &) {
-    ret = MIOC_ENOMEM;
+    R.destroy(&prog);
+    if (!again) break;
   }
-  R.destroy(&prog);
   return ret;
 }
 

@@ -39,6 +39,7 @@ MIOC_ODE_FISHING, MIOC_ODE_DOUBLETANK, MIOC_ODE_VANDERPOL = 1, 2, 3
 MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_RK4 = 0, 1, 2
 MIOC_ODE_INT_BEULER, MIOC_ODE_INT_MIDPOINT = 16, 17  # the implicit schemes start at 16
 MIOC_ODE_NEWTON_MAX, MIOC_ODE_NEWTON_TOL = 12, 1e-10
+MIOC_ODE_DERIVE_FY, MIOC_ODE_DERIVE_FU, MIOC_ODE_DERIVE_GY, MIOC_ODE_DERIVE_GU, MIOC_ODE_DERIVE_ALL = 1, 2, 4, 8, 15
 
 EXPORTED = [
     "mioc_version", "mioc_create", "mioc_destroy", "mioc_last_error", "mioc_set_option", "mioc_set_levels",
@@ -53,7 +54,7 @@ EXPORTED = [
     "mioc_trm_state_bytes", "mioc_trm_attach", "mioc_trm_outer_begin_device", "mioc_trm_inner_end_device",
     "mioc_trm_poll",
     "mioc_ode_program_create", "mioc_ode_program_destroy", "mioc_ode_program_eval_device",
-    "mioc_ode_program_create_ex",
+    "mioc_ode_program_create_ex", "mioc_ode_program_create_ad",
 ]
 
 
@@ -132,6 +133,8 @@ def load_library(path=None):
         "mioc_trm_poll": (i32, [vp, vp, vp]),
         "mioc_ode_program_create": (i32, [ctypes.c_char_p, i32, i32, i32, ctypes.POINTER(vp), ctypes.c_char_p, i64]),
         "mioc_ode_program_create_ex": (i32, [ctypes.c_char_p, i32, i32, i32, i32, i32, ctypes.POINTER(vp),
+                                             ctypes.c_char_p, i64]),
+        "mioc_ode_program_create_ad": (i32, [ctypes.c_char_p, i32, i32, i32, i32, i32, i32, ctypes.POINTER(vp),
                                              ctypes.c_char_p, i64]),
         "mioc_ode_program_destroy": (i32, [vp]),
         "mioc_ode_program_eval_device": (i32, [vp, vp, i64, vp, i64, dbl, dbl, vp, vp, vp, vp]),

@@ -9,6 +9,9 @@ substeps per control interval instead (mioc_ode_program_create_ex): the states a
 while nt, and with it the DP, follows how finely the control should switch.  ``integrator="beuler" | "midpoint"`` are
 backward Euler and the implicit midpoint rule for stiff dynamics: Newton's method per substep on the device, the
 gradient by the implicit function theorem; a restart whose Newton iteration fails returns NaN for J and its df row.
+``ODEProgram(..., derive="all" | ("Fy", "Gy", ...))`` takes F and G as templates over the scalar type and has the
+library generate the named derivative hooks by forward-mode AD (mioc_ode_program_create_ad; include/mioc.h, "Derived
+hooks"); ``check_hooks`` uses that to tell which hand-written derivative hook is wrong.
 
 ``EXAMPLE_SOURCES`` restates the three built-in problems as hook text, term for term as ``Hooks<...>`` of
 csrc/mioc_ode.hip has them, so each reproduces mioc_ode_eval_device bit for bit; they double as templates.  Parameter
@@ -22,7 +25,8 @@ import ctypes
 import sys
 import weakref
 
-from .native import (MIOC_ECOMPILE, MIOC_ODE_INT_BEULER, MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_MIDPOINT,
+from .native import (MIOC_ECOMPILE, MIOC_ODE_DERIVE_FU, MIOC_ODE_DERIVE_FY, MIOC_ODE_DERIVE_GU, MIOC_ODE_DERIVE_GY,
+                     MIOC_ODE_INT_BEULER, MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_MIDPOINT,
                      MIOC_ODE_INT_RK4, MIOC_OK, MiocNativeError, load_library)
 
 
@@ -51,6 +55,20 @@ def _close_live_programs():
 INTEGRATORS = {"euler": MIOC_ODE_INT_EULER, "heun": MIOC_ODE_INT_HEUN, "rk4": MIOC_ODE_INT_RK4,
                "beuler": MIOC_ODE_INT_BEULER, "midpoint": MIOC_ODE_INT_MIDPOINT}
 MAX_SUBSTEPS = 64
+DERIVE_BITS = {"Fy": MIOC_ODE_DERIVE_FY, "Fu": MIOC_ODE_DERIVE_FU, "Gy": MIOC_ODE_DERIVE_GY, "Gu": MIOC_ODE_DERIVE_GU}
+
+
+def derive_names(derive):
+    """``derive`` ("all" or an iterable of hook names) as a tuple of names in the order Fy, Fu, Gy, Gu."""
+    if isinstance(derive, str):
+        if derive != "all":
+            raise ValueError(f'derive must be "all" or an iterable of {list(DERIVE_BITS)}, not {derive!r}')
+        return tuple(DERIVE_BITS)
+    names = set(derive)
+    unknown = sorted(str(n) for n in names if n not in DERIVE_BITS)
+    if unknown:
+        raise ValueError(f"derive names must be among {list(DERIVE_BITS)}, not {unknown}")
+    return tuple(n for n in DERIVE_BITS if n in names)
 
 
 class ODEProgram:
@@ -60,12 +78,17 @@ class ODEProgram:
     ``integrator``: "euler" (the reference's explicit Euler / trapezoid scheme, the default), "heun", "rk4", or the
     implicit "beuler" (backward Euler) and "midpoint" (implicit midpoint rule) for stiff dynamics; all but "euler"
     with ``substeps`` steps inside every control interval and the exact gradient of their discrete J (include/mioc.h,
-    "Integrators" and "Implicit integrators"); the program carries both, every evaluation uses them."""
+    "Integrators" and "Implicit integrators"); the program carries both, every evaluation uses them.
+
+    ``derive``: "all" or an iterable of "Fy", "Fu", "Gy", "Gu" -- the hooks the library generates by forward-mode AD
+    from F and G, which the text then defines as templates over the scalar type (include/mioc.h, "Derived hooks");
+    the text defines the others.  ``ODEProgram.derive`` is the tuple of names; empty: all six hooks are the text's."""
 
     LOG_CAP = 1 << 16
 
-    def __init__(self, source, ny, nx, nparams, integrator="euler", substeps=1):
+    def __init__(self, source, ny, nx, nparams, integrator="euler", substeps=1, derive=()):
         self.h = None
+        self.derive = derive_names(derive)
         if integrator not in INTEGRATORS:
             raise ValueError(f"integrator must be one of {sorted(INTEGRATORS)}, not {integrator!r}")
         if int(substeps) != substeps or not 1 <= substeps <= MAX_SUBSTEPS:
@@ -78,7 +101,11 @@ class ODEProgram:
         h = ctypes.c_void_p()
         log = ctypes.create_string_buffer(self.LOG_CAP)
         text = source.encode() if isinstance(source, str) else source
-        if integrator == "euler":
+        if self.derive:
+            mask = sum(DERIVE_BITS[n] for n in self.derive)
+            rc = self.lib.mioc_ode_program_create_ad(text, self.ny, self.nx, self.nparams, INTEGRATORS[integrator],
+                                                     self.substeps, mask, ctypes.byref(h), log, self.LOG_CAP)
+        elif integrator == "euler":
             rc = self.lib.mioc_ode_program_create(text, self.ny, self.nx, self.nparams, ctypes.byref(h), log,
                                                   self.LOG_CAP)
         else:
@@ -228,6 +255,45 @@ __device__ void Gu@SIG@, double *gu) {}
 }
 EXAMPLE_SOURCES = {k: v.replace("@SIG@", _SIG) for k, v in EXAMPLE_SOURCES.items()}
 
+# The same three problems for derive="all": F and G as templates over the scalar type, their helpers, and nothing
+# else.  F and G keep the parenthesisation above, so with T = double they are the same expressions (the same J bits).
+_TSIG = "(const double *p, int i, double t, const T *y, const T *x"
+
+EXAMPLE_SOURCES_AD = {
+    "fishing": """
+template <class T> __device__ T fish_s1(const double *p, const T *x) { return ((0.0 + x[0] * p[6]) + x[1] * p[7]) + x[2] * p[8]; }
+template <class T> __device__ T fish_s2(const double *p, const T *x) { return ((0.0 + x[0] * p[9]) + x[1] * p[10]) + x[2] * p[11]; }
+template <class T> __device__ void F@SIG@, T *f) {
+  f[0] = y[0] * ((p[0] - p[1] * y[1]) - p[4] * fish_s1(p, x));
+  f[1] = y[1] * ((-p[2] + p[3] * y[0]) - p[5] * fish_s2(p, x));
+}
+template <class T> __device__ T G@SIG@) {
+  const T a = y[0] - 1.0, b = y[1] - 1.0;
+  return 0.5 * (a * a) + 0.5 * (b * b);
+}
+""",
+    "doubletank": """
+template <class T> __device__ T tank_cx(const double *p, const T *x) { return ((0.0 + p[2] * x[0]) + p[3] * x[1]) + p[4] * x[2]; }
+template <class T> __device__ void F@SIG@, T *f) {
+  f[0] = tank_cx(p, x) - sqrt(y[0]);
+  f[1] = sqrt(y[0]) - sqrt(y[1]);
+}
+template <class T> __device__ T G@SIG@) {
+  const T d = y[1] - p[1];
+  return p[0] * (d * d);
+}
+""",
+    "vanderpol": """
+template <class T> __device__ T vdp_cx(const double *p, const T *x) { return ((0.0 + p[0] * x[0]) + p[1] * x[1]) + p[2] * x[2]; }
+template <class T> __device__ void F@SIG@, T *f) {
+  f[0] = y[1];
+  f[1] = ((1.0 - y[0] * y[0]) * y[1]) * vdp_cx(p, x) - y[0];
+}
+template <class T> __device__ T G@SIG@) { return y[0] * y[0] + y[1] * y[1]; }
+""",
+}
+EXAMPLE_SOURCES_AD = {k: v.replace("@SIG@", _TSIG) for k, v in EXAMPLE_SOURCES_AD.items()}
+
 # the examples' constants (example_fishing.jl, example_doubletank.jl, example_vanderpol.jl) and shapes
 EXAMPLE_PARAMS = {"fishing": [1, 1, 1, 1, 1, 1, 0.2, 0.4, 0.01, 0.1, 0.2, 0.1], "doubletank": [2, 3, 1, 0.5, 2],
                   "vanderpol": [-1, 0.75, -2]}
@@ -235,19 +301,54 @@ EXAMPLE_STATE0 = {"fishing": [0.5, 0.7], "doubletank": [2, 2], "vanderpol": [1, 
 EXAMPLE_SHAPES = {k: (2, 3, len(v)) for k, v in EXAMPLE_PARAMS.items()}  # (ny, nx, nparams)
 
 
-def example_program(name, integrator="euler", substeps=1):
-    """ODEProgram of a built-in example's hook text."""
+def example_program(name, integrator="euler", substeps=1, ad=False):
+    """ODEProgram of a built-in example's hook text; ``ad``: of its F and G alone (EXAMPLE_SOURCES_AD), the four
+    derivative hooks generated (derive="all")."""
+    if ad:
+        return ODEProgram(EXAMPLE_SOURCES_AD[name], *EXAMPLE_SHAPES[name], integrator=integrator, substeps=substeps,
+                          derive="all")
     return ODEProgram(EXAMPLE_SOURCES[name], *EXAMPLE_SHAPES[name], integrator=integrator, substeps=substeps)
 
 
-def example_problem(name, program=None, nt=None, integrator="euler", substeps=1):
+def check_hooks(ctx, source, ny, nx, nparams, x, T0, T1, state0, params, integrator="euler", substeps=1):
+    """Which hand-written derivative hook is wrong?  The program-level counterpart of the reference's test_Fy! /
+    test_Fu! (ODEObjective.jl:186-241), without finite differences.
+
+    ``source`` defines F and G as templates over the scalar type and each of Fy, Fu, Gy, Gu by hand under its guard
+    (``#ifndef MIOC_DERIVE_FY`` ... ``#endif``, include/mioc.h "Derived hooks").  It is compiled six times: all hooks
+    by hand (derive = 0), all four derived, and each one derived with the other three by hand; J and df are evaluated
+    at the controls ``x``, a (K, nt, nx) float64 CUDA tensor, on ``ctx``.  Returns a dict:
+      "J_equal"   J is bit-equal across the six programs (F and G are the same in all);
+      "Fy", "Fu", "Gy", "Gu"   max|df(that hook derived) - df(all by hand)| / max|df(all derived)|: replacing a correct
+                  hand-written hook by the derived one changes df by rounding only, a wrong one by its error;
+      "all"       the same for all four derived against all by hand.
+    A wrong hook shows in its own entry and in "all" alone.  The programs are closed before returning."""
+    import torch
+    masks = [("hand", ()), ("all", "all")] + [(n, (n,)) for n in DERIVE_BITS]
+    res = {}
+    for key, derive in masks:
+        with ODEProgram(source, ny, nx, nparams, integrator=integrator, substeps=substeps, derive=derive) as prog:
+            J = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
+            df = torch.empty_like(x)
+            ctx.ode_program_eval_tensors(prog, x, T0, T1, state0, params, J, df)
+            ctx.synchronize()
+            res[key] = (J, df)
+    J0, df0 = res["hand"]
+    scale = float(res["all"][1].abs().max())
+    out = {"J_equal": all(bool(torch.equal(J, J0)) for J, _ in res.values())}
+    for key, _ in masks[1:]:
+        out[key] = float((res[key][1] - df0).abs().max()) / scale
+    return out
+
+
+def example_problem(name, program=None, nt=None, integrator="euler", substeps=1, ad=False):
     """DeviceODEProblem of a built-in example (SOS1 over three binary controls, the example's horizon; nt: the
     example's unless given -- with heun / rk4 / beuler / midpoint and substeps the control grid can be much coarser
     than the example's).
-    Without ``program``, one is compiled with ``integrator`` and ``substeps``."""
+    Without ``program``, one is compiled with ``integrator`` and ``substeps``, with ``ad`` from F and G alone."""
     from .iterators import bounded_sum_iterator
     from .trm_batch import PROBLEMS
     _, nt_def, T0, T1 = PROBLEMS[name]
     V = [[0, 1], [0, 1], [0, 1]]
-    return DeviceODEProblem(program or example_program(name, integrator, substeps), V, bounded_sum_iterator(V, 1, 1),
+    return DeviceODEProblem(program or example_program(name, integrator, substeps, ad), V, bounded_sum_iterator(V, 1, 1),
                             T0, T1, nt_def if nt is None else nt, EXAMPLE_STATE0[name], EXAMPLE_PARAMS[name])
