@@ -216,7 +216,8 @@ int32_t mioc_tv_device(mioc_ctx *ctx, int64_t K, const double *d_u, int64_t nx, 
  *     (offset 0: gate word, 4: any-active word, 8: copy word; then K doubles Δᵏ, K doubles TV_old, K int32 k,
  *     K int32 flags (1 inner, 2 halved, 4 stopped), K int32 outer iterations per restart).
  *   mioc_trm_attach(ctx, d_state): while the gate word is 0, the kernels of mioc_backtrack_batch*_device,
- *     mioc_pred_batch_device, mioc_ode_eval_device, mioc_ode_program_eval_device, mioc_heat_eval_device and mioc_conv_eval_device return at once;
+ *     mioc_pred_batch_device, mioc_ode_eval_device, mioc_ode_program_eval_device (and _eval_mixed_device),
+ *     mioc_rows_copy_device, mioc_heat_eval_device and mioc_conv_eval_device return at once;
  *     NULL detaches.
  *   mioc_trm_outer_begin_device: multi-trust.jl:99-107 (TV_old = TV_p(u), Δᵏ = Δ⁰, k = 1, budgets = B, every
  *     restart not stopped enters its inner loop; the gate opens if any did).
@@ -273,7 +274,8 @@ int32_t mioc_ode_eval_device(mioc_ctx *ctx, int32_t problem, int64_t K, const do
  * F!, Fy!, Fu!, G, Gy!, Gu!, julia_opt/ODEObjective.jl:243-248) for problems other than the three above.  The caller
  * hands the six hooks over as HIP source text; the library compiles them into its explicit-Euler / adjoint sweep for
  * gfx950 at run time (hiprtc) and launches that kernel: min ∫ G(t, y, u) dt  s.t.  y' = F(t, y, u), y(T0) = state0,
- * with ny states, nx controls (discrete controls only, the DP's) and nparams parameters.
+ * with ny states, nx controls (the DP's discrete ones; with "Mixed controls" below, nu continuous ones in front of
+ * them) and nparams parameters.
  *
  * Hook contract.  The text is compiled as HIP C++ in front of the kernel; NY, NX and NP (= ny, nx, nparams) are
  * defined as macros before it.  It may define helper __device__ functions, and it defines exactly these six:
@@ -482,6 +484,62 @@ int32_t mioc_ode_program_destroy(mioc_ode_program *prog);
 int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t K, const double *d_x, int64_t nt,
                                      double T0, double T1, const double *state0, const double *params, double *d_J,
                                      double *d_df);
+
+/*
+ * Mixed controls: continuous controls beside the DP's integer ones, for ODE programs.  A mixed
+ * control x has nx = nu + nv rows per time step: rows 0..nu-1 are continuous (c), rows nu..nx-1 integer (v), as the
+ * reference's rand_func lays them out (HelpFunctions.jl:136-148: x0[1:nu,:], x0[nu+1:nx,:]).  Device layout
+ * K x nx x nt as everywhere ((K, nt, nx) row-major).  The bounds are pointwise, d_lo and d_hi of nt x nu doubles
+ * ([i][m], the reference's umin[m, i] / umax[m, i]), lo <= hi.  The context's levels describe the nv integer rows
+ * only (M = nv): the DP, the backtrack, pred and TV_p see compact K x nv x nt arrays.  The reference announces this
+ * algorithm but has no code for it; the continuous step is defined here.
+ *
+ * mioc_ode_program_eval_mixed_device is mioc_ode_program_eval_device (the same kernel, launch, scratch and gate) with
+ *   one different check: 1 <= nu < the program's nx, and once levels are set nx == nu + M (MIOC_EINVAL otherwise).
+ *   K may be the K*R candidates of a fan.
+ * mioc_rows_copy_device: dst[k][i][dst_row0 + r] = src[k][i][src_row0 + r] for r < nrows, k < K, i < nt, with dst of
+ *   dst_nx and src of src_nx rows per step: the split (df -> df_v, x -> v_old) and the join (c, trial_v -> x_trial)
+ *   around the DP.  dst == src is allowed with one nx and disjoint rows.  Enqueued on the context's stream; gated by
+ *   mioc_trm_attach like mioc_pred_batch_device.  MIOC_EINVAL for a row range outside dst_nx / src_nx (and K > 65535,
+ *   nx > 1024, nt >= 2^21).
+ * mioc_mixed_state_bytes(K): bytes of the device state block of the continuous step, 1 <= K <= 4096 (else -1):
+ *   offset 0 an int32 any-live word; offset 16 K doubles, the step size s; then K int32 flags (1 final, 2 moved),
+ *   K int32 jsel (the candidate accepted last, -1 none), K int32 csteps (accepted continuous steps).  The caller
+ *   zero-initialises it and writes the first step size s0 into s.
+ * mioc_mixed_fan_device: the R candidates of a backtracking line search along the projected gradient, for all K
+ *   restarts in one launch (1 <= R <= 16, 1 <= nu <= nx <= 1024).  For restart k and candidate j, with g = d_df:
+ *     s_j = s[k] * 2^-j (exact);  for m < nu: t = x - s_j*g (one product, one difference),
+ *     c_j = t < lo ? lo : (t > hi ? hi : t)  (a NaN stays a NaN);  rows m >= nu are copied from x.
+ *   d_xfan is R x K x nx x nt, candidate-major: a batch of R*K controls for the eval entry.
+ *     slope[j*K + k] = tau * sum g*(c - c_j): each term one difference, then one product; the sum starts at 0.0 and
+ *     runs over i ascending, m ascending within i, sequentially (one lane folds the terms of an LDS chunk, as for
+ *     int_val), so a host loop reproduces every bit.  Not gated.
+ * mioc_mixed_select_device: per restart, with STOP = flag 4 of the TRM state block d_trm_state, in this order:
+ *     1. a final restart is left alone;
+ *     2. STOP and not moved (the flag of the previous call) -> final, left alone;
+ *     3. otherwise the smallest j with slope_j > 0 and Jfan_j <= J_old - c1*slope_j (comparisons as written: a NaN
+ *        never passes).  Found: rows < nu of xfan[j][k] are copied into x[k]; moved = (J_old - Jfan_j) >
+ *        ctol*max(1, |J_old|); J_old = Jfan_j; s = min(2*s_j, smax); jsel = j; csteps += 1.  None: moved = false;
+ *        s = s * 2^-R; jsel = -1;
+ *     4. if STOP: it is cleared when moved (the DP runs again), else the restart is final.
+ *   0 < c1 < 1, smax > 0, ctol >= 0.  Not gated.
+ * mioc_mixed_poll: reduces the flags, synchronises the stream once (as mioc_trm_poll) and returns out[0] = the TRM
+ *   gate word, out[1] = any restart that is not final and (not STOP or moved).  It takes K from the last
+ *   mioc_mixed_select_device on d_mstate (MIOC_ESTATE if there was none).
+ */
+int32_t mioc_ode_program_eval_mixed_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K,
+                                           const double *d_x, int64_t nt, double T0, double T1, const double *state0,
+                                           const double *params, double *d_J, double *d_df);
+int32_t mioc_rows_copy_device(mioc_ctx *ctx, int64_t K, int64_t nt, double *d_dst, int64_t dst_nx, int64_t dst_row0,
+                              const double *d_src, int64_t src_nx, int64_t src_row0, int64_t nrows);
+int64_t mioc_mixed_state_bytes(int64_t K);
+int32_t mioc_mixed_fan_device(mioc_ctx *ctx, int64_t K, int64_t R, int64_t nu, int64_t nx, int64_t nt, double tau,
+                              const double *d_x, const double *d_df, const double *d_lo, const double *d_hi,
+                              void *d_mstate, double *d_xfan, double *d_slope);
+int32_t mioc_mixed_select_device(mioc_ctx *ctx, int64_t K, int64_t R, int64_t nu, int64_t nx, int64_t nt, double c1,
+                                 double smax, double ctol, void *d_mstate, void *d_trm_state, const double *d_xfan,
+                                 const double *d_slope, const double *d_Jfan, double *d_J_old, double *d_x);
+int32_t mioc_mixed_poll(mioc_ctx *ctx, void *d_mstate, void *d_trm_state, int32_t *out);
 
 /*
  * Random admissible starts, rand_func_int (HelpFunctions.jl:204-225) on the device: K piecewise-constant controls

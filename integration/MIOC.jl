@@ -294,4 +294,89 @@ function ode_program_eval_device!(ctx::Context, prog::Ptr{Cvoid}, K::Integer, d_
     nothing
 end
 
+# ---- mixed controls: nu continuous controls in front of the DP's integer ones (include/mioc.h, "Mixed controls").
+# Thin wrappers of the six entries; they have not been run under Julia (none is installed where this was written).
+
+"""
+    ode_program_eval_mixed_device!(ctx, prog, nu, K, d_x, nt, T0, T1, state0, params, d_J, d_df)
+
+`ode_program_eval_device!` for a mixed control: the first `nu` of the program's nx controls are continuous and the
+context's levels describe the other nx - nu (mioc_ode_program_eval_mixed_device).  K may be the K·R candidates of a fan.
+"""
+function ode_program_eval_mixed_device!(ctx::Context, prog::Ptr{Cvoid}, nu::Integer, K::Integer, d_x::Ptr{Float64},
+                                        nt::Integer, T0::Float64, T1::Float64, state0::Vector{Float64},
+                                        params::Vector{Float64}, d_J::Ptr{Float64}, d_df::Ptr{Float64})
+    check(ctx, ccall((:mioc_ode_program_eval_mixed_device, libmioc), Int32,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Float64, Float64, Ptr{Float64},
+                      Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ctx.ptr, prog, nu, K, d_x, nt, T0, T1, state0, params,
+                     d_J, d_df))
+    nothing
+end
+
+"""
+    rows_copy_device!(ctx, K, nt, d_dst, dst_nx, dst_row0, d_src, src_nx, src_row0, nrows)
+
+dst[k][i][dst_row0 + r] = src[k][i][src_row0 + r] (0-based rows, r < nrows): the split and the join around the DP
+(mioc_rows_copy_device); enqueued, gated by the TRM state's gate word.
+"""
+function rows_copy_device!(ctx::Context, K::Integer, nt::Integer, d_dst::Ptr{Float64}, dst_nx::Integer,
+                           dst_row0::Integer, d_src::Ptr{Float64}, src_nx::Integer, src_row0::Integer, nrows::Integer)
+    check(ctx, ccall((:mioc_rows_copy_device, libmioc), Int32,
+                     (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Int64), ctx.ptr,
+                     K, nt, d_dst, dst_nx, dst_row0, d_src, src_nx, src_row0, nrows))
+    nothing
+end
+
+"""
+    mixed_state_bytes(K)
+
+Bytes of the device state block of the continuous step for K restarts (mioc_mixed_state_bytes): zero it and write the
+first step size into its K doubles at offset 16.
+"""
+mixed_state_bytes(K::Integer) = ccall((:mioc_mixed_state_bytes, libmioc), Int64, (Int64,), K)
+
+"""
+    mixed_fan_device!(ctx, K, R, nu, nx, nt, tau, d_x, d_df, d_lo, d_hi, d_mstate, d_xfan, d_slope)
+
+The R line-search candidates of every restart and their Armijo slopes (mioc_mixed_fan_device); d_xfan is R × K × nx × nt.
+"""
+function mixed_fan_device!(ctx::Context, K::Integer, R::Integer, nu::Integer, nx::Integer, nt::Integer, tau::Float64,
+                           d_x::Ptr{Float64}, d_df::Ptr{Float64}, d_lo::Ptr{Float64}, d_hi::Ptr{Float64},
+                           d_mstate::Ptr{Cvoid}, d_xfan::Ptr{Float64}, d_slope::Ptr{Float64})
+    check(ctx, ccall((:mioc_mixed_fan_device, libmioc), Int32,
+                     (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                      Ptr{Float64}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ctx.ptr, K, R, nu, nx, nt, tau, d_x, d_df,
+                     d_lo, d_hi, d_mstate, d_xfan, d_slope))
+    nothing
+end
+
+"""
+    mixed_select_device!(ctx, K, R, nu, nx, nt, c1, smax, ctol, d_mstate, d_trm_state, d_xfan, d_slope, d_Jfan, d_J_old, d_x)
+
+Per restart the first candidate that passes the Armijo test, the step-size update and the finality rule
+(mioc_mixed_select_device).
+"""
+function mixed_select_device!(ctx::Context, K::Integer, R::Integer, nu::Integer, nx::Integer, nt::Integer, c1::Float64,
+                              smax::Float64, ctol::Float64, d_mstate::Ptr{Cvoid}, d_trm_state::Ptr{Cvoid},
+                              d_xfan::Ptr{Float64}, d_slope::Ptr{Float64}, d_Jfan::Ptr{Float64}, d_J_old::Ptr{Float64},
+                              d_x::Ptr{Float64})
+    check(ctx, ccall((:mioc_mixed_select_device, libmioc), Int32,
+                     (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int64, Float64, Float64, Float64, Ptr{Cvoid}, Ptr{Cvoid},
+                      Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ctx.ptr, K, R, nu, nx, nt,
+                     c1, smax, ctol, d_mstate, d_trm_state, d_xfan, d_slope, d_Jfan, d_J_old, d_x))
+    nothing
+end
+
+"""
+    mixed_poll(ctx, d_mstate, d_trm_state) -> (inner, live)
+
+One stream synchronisation: any restart inside its inner loop, any restart that can still move (mioc_mixed_poll).
+"""
+function mixed_poll(ctx::Context, d_mstate::Ptr{Cvoid}, d_trm_state::Ptr{Cvoid})
+    out = zeros(Int32, 2)
+    check(ctx, ccall((:mioc_mixed_poll, libmioc), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}), ctx.ptr,
+                     d_mstate, d_trm_state, out))
+    (out[1] != 0, out[2] != 0)
+end
+
 end # module

@@ -1329,6 +1329,79 @@ int32_t mioc_trm_poll(mioc_ctx *ctx, const void *d_state, int32_t *out) {
   return MIOC_OK;
 }
 
+// ---- mixed controls: the continuous step beside the DP (mioc_mixed.hip) ------------------------------------
+int32_t mioc_rows_copy_device(mioc_ctx *ctx, int64_t K, int64_t nt, double *d_dst, int64_t dst_nx, int64_t dst_row0,
+                              const double *d_src, int64_t src_nx, int64_t src_row0, int64_t nrows) {
+  if (!ctx) return MIOC_EINVAL;
+  MIOC_JOIN_BT(ctx);
+  if (!d_dst || !d_src) return fail(ctx, MIOC_EINVAL, "null pointer");
+  if (K < 1 || K > 65535 || nt < 1 || dst_nx < 1 || src_nx < 1 || dst_nx > 1024 || src_nx > 1024 ||
+      nt > INT32_MAX / 1024)
+    return fail(ctx, MIOC_EINVAL, "bad K / nt / nx");
+  if (nrows < 1 || dst_row0 < 0 || src_row0 < 0 || dst_row0 + nrows > dst_nx || src_row0 + nrows > src_nx)
+    return fail(ctx, MIOC_EINVAL, "row range outside dst_nx / src_nx");
+  if (d_dst == d_src && (dst_nx != src_nx || (dst_row0 < src_row0 + nrows && src_row0 < dst_row0 + nrows)))
+    return fail(ctx, MIOC_EINVAL, "in-place row copy needs one nx and disjoint rows");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, launch_rows_copy(ctx->stream, ctx->gate, (int)K, (int)nt, d_dst, (int)dst_nx, (int)dst_row0, d_src,
+                                (int)src_nx, (int)src_row0, (int)nrows));
+  return MIOC_OK;
+}
+
+int64_t mioc_mixed_state_bytes(int64_t K) { return K < 1 || K > 4096 ? -1 : (int64_t)mixed_state_bytes((int)K); }
+
+int32_t mioc_mixed_fan_device(mioc_ctx *ctx, int64_t K, int64_t R, int64_t nu, int64_t nx, int64_t nt, double tau,
+                              const double *d_x, const double *d_df, const double *d_lo, const double *d_hi,
+                              void *d_mstate, double *d_xfan, double *d_slope) {
+  if (!ctx) return MIOC_EINVAL;
+  MIOC_JOIN_BT(ctx);
+  if (!d_x || !d_df || !d_lo || !d_hi || !d_mstate || !d_xfan || !d_slope) return fail(ctx, MIOC_EINVAL, "null pointer");
+  if (K < 1 || K > 4096 || R < 1 || R > 16) return fail(ctx, MIOC_EINVAL, "need 1 <= K <= 4096 and 1 <= R <= 16");
+  if (nu < 1 || nu > nx || nx > 1024 || nt < 1 || nt > INT32_MAX / 1024)
+    return fail(ctx, MIOC_EINVAL, "need 1 <= nu <= nx <= 1024 and 1 <= nt < 2^21");
+  if (!std::isfinite(tau)) return fail(ctx, MIOC_EINVAL, "tau must be finite");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, launch_mixed_fan(ctx->stream, (int)K, (int)R, (int)nu, (int)nx, (int)nt, tau, d_x, d_df, d_lo, d_hi,
+                                d_mstate, d_xfan, d_slope));
+  return MIOC_OK;
+}
+
+int32_t mioc_mixed_select_device(mioc_ctx *ctx, int64_t K, int64_t R, int64_t nu, int64_t nx, int64_t nt, double c1,
+                                 double smax, double ctol, void *d_mstate, void *d_trm_state, const double *d_xfan,
+                                 const double *d_slope, const double *d_Jfan, double *d_J_old, double *d_x) {
+  if (!ctx) return MIOC_EINVAL;
+  MIOC_JOIN_BT(ctx);
+  if (!d_mstate || !d_trm_state || !d_xfan || !d_slope || !d_Jfan || !d_J_old || !d_x)
+    return fail(ctx, MIOC_EINVAL, "null pointer");
+  if (K < 1 || K > 4096 || R < 1 || R > 16) return fail(ctx, MIOC_EINVAL, "need 1 <= K <= 4096 and 1 <= R <= 16");
+  if (nu < 1 || nu > nx || nx > 1024 || nt < 1 || nt > INT32_MAX / 1024)
+    return fail(ctx, MIOC_EINVAL, "need 1 <= nu <= nx <= 1024 and 1 <= nt < 2^21");
+  if (!(c1 > 0.0) || !(c1 < 1.0) || !(smax > 0.0) || !(ctol >= 0.0))
+    return fail(ctx, MIOC_EINVAL, "need 0 < c1 < 1, smax > 0 and ctol >= 0");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, launch_mixed_select(ctx->stream, (int)K, (int)R, (int)nu, (int)nx, (int)nt, c1, smax, ctol, d_mstate,
+                                   d_trm_state, d_xfan, d_slope, d_Jfan, d_J_old, d_x));
+  ctx->mixed_state = d_mstate;
+  ctx->mixed_K = (int)K;
+  return MIOC_OK;
+}
+
+int32_t mioc_mixed_poll(mioc_ctx *ctx, void *d_mstate, void *d_trm_state, int32_t *out) {
+  if (!ctx || !d_mstate || !d_trm_state || !out) return MIOC_EINVAL;
+  MIOC_JOIN_BT(ctx);
+  if (d_mstate != ctx->mixed_state)
+    return fail(ctx, MIOC_ESTATE, "mioc_mixed_poll: no mioc_mixed_select_device has run on this state block");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, launch_mixed_live(ctx->stream, ctx->mixed_K, d_mstate, d_trm_state));
+  int32_t *h = ctx->h_trm_poll.get();
+  HIP_TRY(ctx, hipMemcpyAsync(h, d_trm_state, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(h + 1, d_mstate, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  out[0] = h[0];
+  out[1] = h[1];
+  return MIOC_OK;
+}
+
 int32_t mioc_kernel_stats(mioc_ctx *ctx, int32_t which, double *total_ms, int64_t *launches, const char **name) {
   if (!ctx || which < 0 || which >= kStats) return MIOC_EINVAL;
   ev_collect(ctx);

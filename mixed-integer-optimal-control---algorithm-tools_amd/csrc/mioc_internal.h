@@ -316,7 +316,66 @@ hipError_t launch_trm_decide(hipStream_t s, int K, const double *J_old, const do
                              int32_t *decision);
 
 hipError_t launch_rand_start(hipStream_t s, int K, int nt, int jumps, uint64_t seed, const LevelsDev &Lv, double *U);
-// device-resident TRM control (mioc_trm.hip)
+// device-resident TRM control (mioc_trm.hip): the state block's layout and flag bits, shared with the mixed control
+// (mioc_mixed.hip), which reads and clears the stop flag
+constexpr int TRM_INNER = 1, TRM_HALVED = 2, TRM_STOP = 4, TRM_COPY_U = 8, TRM_COPY_UOLD = 16;
+
+struct TrmState {
+  int32_t *gate, *any_active, *any_copy;
+  double *Dk, *tv_old;
+  int32_t *k, *flags, *iters;
+};
+__host__ __device__ inline TrmState trm_state_layout(void *base, int K) {
+  TrmState S;
+  char *b = static_cast<char *>(base);
+  S.gate = reinterpret_cast<int32_t *>(b);
+  S.any_active = S.gate + 1;
+  S.any_copy = S.gate + 2;
+  S.Dk = reinterpret_cast<double *>(b + 16);
+  S.tv_old = S.Dk + K;
+  S.k = reinterpret_cast<int32_t *>(S.tv_old + K);
+  S.flags = S.k + K;
+  S.iters = S.flags + K;
+  return S;
+}
+
+// block-wide OR of one flag per thread into *out (one workgroup)
+__device__ __forceinline__ void trm_block_or(int v, int32_t *out) {
+  __shared__ int s_or;
+  if (threadIdx.x == 0) s_or = 0;
+  __syncthreads();
+  if (__ballot(v) && (threadIdx.x & 63) == 0) atomicOr(&s_or, 1);
+  __syncthreads();
+  if (threadIdx.x == 0) *out = s_or;
+}
+
+// acc + x[0] + x[1] + ... in this order, by one lane (the sequential sums of k_trm_pred and k_mixed_fan)
+__device__ __forceinline__ double fold(const double *x, int n, double acc) {
+  int j = 0;
+  for (; j + 8 <= n; j += 8) {
+    double v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = x[j + q];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc = acc + v[q];
+  }
+  for (; j < n; ++j) acc = acc + x[j];
+  return acc;
+}
+
+// ---- mixed control: the continuous step beside the DP (mioc_mixed.hip) -----------------------------------------
+constexpr int kMixedChunk = 2048;  // per-element slope terms folded per LDS chunk of k_mixed_fan
+size_t mixed_state_bytes(int K);
+hipError_t launch_rows_copy(hipStream_t s, const int32_t *gate, int K, int nt, double *dst, int dst_nx, int dst_row0,
+                            const double *src, int src_nx, int src_row0, int nrows);
+hipError_t launch_mixed_fan(hipStream_t s, int K, int R, int nu, int nx, int nt, double tau, const double *x,
+                            const double *df, const double *lo, const double *hi, void *mstate, double *xfan,
+                            double *slope);
+hipError_t launch_mixed_select(hipStream_t s, int K, int R, int nu, int nx, int nt, double c1, double smax, double ctol,
+                               void *mstate, void *trm_state, const double *xfan, const double *slope,
+                               const double *Jfan, double *J_old, double *x);
+hipError_t launch_mixed_live(hipStream_t s, int K, void *mstate, void *trm_state);
+
 size_t trm_state_bytes(int K);
 hipError_t launch_trm_outer_begin(hipStream_t s, int K, void *state, const double *tv_u, double D0, int B,
                                   int32_t *budgets);
@@ -425,7 +484,9 @@ struct mioc_ctx {
   unsigned spin_limit = 1u << 24;  // persistent DP: polls before a dependency wait gives up (MIOC_OPT_SPIN_LIMIT)
   int opt_nb = mioc::kSdtDefaultBuffers;  // staging buffers of a persistent separable DP (MIOC_OPT_SDT_BUFFERS)
   const int32_t *gate = nullptr;   // device TRM control (mioc_trm_attach): the state block's gate word
-  mioc::PinnedWord h_trm_poll;     // pinned: the gate and any-active words (mioc_trm_poll)
+  mioc::PinnedWord h_trm_poll;     // pinned: the gate and any-active words (mioc_trm_poll, mioc_mixed_poll)
+  const void *mixed_state = nullptr;  // the mixed state block of the last mioc_mixed_select_device and its K: what
+  int mixed_K = 0;                    // mioc_mixed_poll may reduce
   int opt_fsep_seg = 0;            // fused separable DP: row segments (MIOC_OPT_FSEP_SEGMENTS)
   Buf<double> d_ring;              // fused separable DP, S > 1: the segments' outbox rings
   Buf<int32_t> d_segflags;         // ... and their flags (+ err)

@@ -994,17 +994,21 @@ int32_t mioc_ode_program_destroy(mioc_ode_program *prog) {
   return rc;
 }
 
-int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t K, const double *d_x, int64_t nt,
-                                     double T0, double T1, const double *state0, const double *params, double *d_J,
-                                     double *d_df) {
+// The body of both eval entries.  nu = 0: every control is the DP's (mioc_ode_program_eval_device); nu >= 1: the first
+// nu controls are continuous and the levels describe the other nx - nu (mioc_ode_program_eval_mixed_device).
+static int32_t program_eval(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K, const double *d_x, int64_t nt,
+                            double T0, double T1, const double *state0, const double *params, double *d_J,
+                            double *d_df) {
   if (!ctx) return MIOC_EINVAL;
   MIOC_JOIN_BT(ctx);
   if (!prog) return fail(ctx, MIOC_EINVAL, "no ODE program");
   if (K < 1 || nt < 1 || K > INT32_MAX || nt > INT32_MAX || !d_x) return fail(ctx, MIOC_EINVAL, "bad K / nt / x");
   if (!state0 || (prog->np > 0 && !params)) return fail(ctx, MIOC_EINVAL, "state0 / params missing");
   if (!(T1 > T0)) return fail(ctx, MIOC_EINVAL, "need T1 > T0");
-  if (ctx->have_levels && ctx->M != prog->nx)
-    return fail(ctx, MIOC_EINVAL, "the program's nx differs from the levels' number of controls");
+  if (nu < 0 || nu >= prog->nx) return fail(ctx, MIOC_EINVAL, "need 1 <= nu < the program's nx");
+  if (ctx->have_levels && ctx->M != prog->nx - nu)
+    return fail(ctx, MIOC_EINVAL, nu ? "the program's nx differs from nu + the levels' number of controls"
+                                     : "the program's nx differs from the levels' number of controls");
   if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, MIOC_EHIP, "hipSetDevice failed");
   hipFunction_t fn = nullptr;
   {
@@ -1050,6 +1054,19 @@ int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int6
   const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)((K + 63) / 64), 1, 1, 64, 1, 1, 0, ctx->stream, args, nullptr);
   if (e != hipSuccess) return fail(ctx, MIOC_EHIP, std::string("launching the ODE program: ") + hipGetErrorString(e));
   return MIOC_OK;
+}
+
+int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t K, const double *d_x, int64_t nt,
+                                     double T0, double T1, const double *state0, const double *params, double *d_J,
+                                     double *d_df) {
+  return program_eval(ctx, prog, 0, K, d_x, nt, T0, T1, state0, params, d_J, d_df);
+}
+
+int32_t mioc_ode_program_eval_mixed_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K,
+                                           const double *d_x, int64_t nt, double T0, double T1, const double *state0,
+                                           const double *params, double *d_J, double *d_df) {
+  if (ctx && nu < 1) return fail(ctx, MIOC_EINVAL, "need 1 <= nu < the program's nx");
+  return program_eval(ctx, prog, nu, K, d_x, nt, T0, T1, state0, params, d_J, d_df);
 }
 
 }  // extern "C"

@@ -91,19 +91,6 @@ __device__ double tv_term(const TrmDev &T, const double *a, const double *b, int
   return T.tvw[key];
 }
 
-__device__ __forceinline__ double fold(const double *x, int n, double acc) {
-  int j = 0;
-  for (; j + 8 <= n; j += 8) {
-    double v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = x[j + q];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) acc = acc + v[q];
-  }
-  for (; j < n; ++j) acc = acc + x[j];
-  return acc;
-}
-
 __global__ __launch_bounds__(kTrmThreads) void k_trm_pred(TrmDev T) {
   if (gate_closed(T.gate)) return;
   __shared__ double s_int[kTrmChunk], s_told[kTrmChunk], s_tnew[kTrmChunk];
@@ -189,36 +176,7 @@ __global__ void k_trm_decide(int K, const double *J_old, const double *J_new, co
 // State block (TrmState, laid out by trm_state_layout): the gate word (any restart inside its inner loop: the
 // gated kernels of an inner iteration return at once while it is 0), the any-active word (any restart not
 // stopped), the copy word (any trial to copy), then per restart Δᵏ, TV_old, k, flags, outer iterations.
-constexpr int TRM_INNER = 1, TRM_HALVED = 2, TRM_STOP = 4, TRM_COPY_U = 8, TRM_COPY_UOLD = 16;
-
-struct TrmState {
-  int32_t *gate, *any_active, *any_copy;
-  double *Dk, *tv_old;
-  int32_t *k, *flags, *iters;
-};
-__host__ __device__ inline TrmState trm_state_layout(void *base, int K) {
-  TrmState S;
-  char *b = static_cast<char *>(base);
-  S.gate = reinterpret_cast<int32_t *>(b);
-  S.any_active = S.gate + 1;
-  S.any_copy = S.gate + 2;
-  S.Dk = reinterpret_cast<double *>(b + 16);
-  S.tv_old = S.Dk + K;
-  S.k = reinterpret_cast<int32_t *>(S.tv_old + K);
-  S.flags = S.k + K;
-  S.iters = S.flags + K;
-  return S;
-}
-
-// block-wide OR of one flag per thread into *out (one workgroup)
-__device__ __forceinline__ void trm_block_or(int v, int32_t *out) {
-  __shared__ int s_or;
-  if (threadIdx.x == 0) s_or = 0;
-  __syncthreads();
-  if (__ballot(v) && (threadIdx.x & 63) == 0) atomicOr(&s_or, 1);
-  __syncthreads();
-  if (threadIdx.x == 0) *out = s_or;
-}
+// (TrmState, the flag bits and trm_block_or are in mioc_internal.h: mioc_mixed.hip reads and clears the stop flag.)
 
 // start of an outer iteration, multi-trust.jl:99-107: TV_old = TV_p(u), Δᵏ = Δ⁰, k = 1, every restart that has not
 // stopped enters its inner loop with the full budget B; the gate opens if any did

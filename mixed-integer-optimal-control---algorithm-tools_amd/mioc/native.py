@@ -55,7 +55,17 @@ EXPORTED = [
     "mioc_trm_poll",
     "mioc_ode_program_create", "mioc_ode_program_destroy", "mioc_ode_program_eval_device",
     "mioc_ode_program_create_ex", "mioc_ode_program_create_ad",
+    "mioc_ode_program_eval_mixed_device", "mioc_rows_copy_device", "mioc_mixed_state_bytes", "mioc_mixed_fan_device",
+    "mioc_mixed_select_device", "mioc_mixed_poll",
 ]
+
+MIXED_FAN_TERMS = 2048  # slope terms per LDS chunk of mioc_mixed_fan_device (kMixedChunk)
+
+
+def mixed_fan_chunk(nu):
+    """Slope terms (elements of the continuous rows) that mioc_mixed_fan_device folds per LDS chunk: an even number of
+    time steps of nu terms each, at most MIXED_FAN_TERMS."""
+    return ((MIXED_FAN_TERMS // int(nu)) & ~1) * int(nu)
 
 
 class MiocNativeError(RuntimeError):
@@ -138,6 +148,12 @@ def load_library(path=None):
                                              ctypes.c_char_p, i64]),
         "mioc_ode_program_destroy": (i32, [vp]),
         "mioc_ode_program_eval_device": (i32, [vp, vp, i64, vp, i64, dbl, dbl, vp, vp, vp, vp]),
+        "mioc_ode_program_eval_mixed_device": (i32, [vp, vp, i64, i64, vp, i64, dbl, dbl, vp, vp, vp, vp]),
+        "mioc_rows_copy_device": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, i64]),
+        "mioc_mixed_state_bytes": (i64, [i64]),
+        "mioc_mixed_fan_device": (i32, [vp, i64, i64, i64, i64, i64, dbl, vp, vp, vp, vp, vp, vp, vp]),
+        "mioc_mixed_select_device": (i32, [vp, i64, i64, i64, i64, i64, dbl, dbl, dbl, vp, vp, vp, vp, vp, vp, vp]),
+        "mioc_mixed_poll": (i32, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -469,6 +485,122 @@ class Context:
             _p(par) if par.size else None,
             ctypes.c_void_p(J.data_ptr()) if J is not None else None,
             ctypes.c_void_p(df.data_ptr()) if df is not None else None))
+
+    # ---- mixed controls: the continuous step beside the DP (include/mioc.h, "Mixed controls") -----------------
+    def ode_program_eval_mixed_tensors(self, prog, nu, x, T0, T1, state0, params, J=None, df=None):
+        """ode_program_eval_tensors for a mixed control: the first nu of the program's nx controls are continuous, the
+        levels describe the other nx - nu; x may hold the K*R candidates of a fan
+        (mioc_ode_program_eval_mixed_device)."""
+        if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
+            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
+        K, nt, nx = x.shape
+        if nx != prog.nx:
+            raise ValueError(f"x has {nx} controls, the program {prog.nx}")
+        if int(nu) != nu or not 1 <= nu < nx:
+            raise ValueError(f"nu must be an integer in 1..{nx - 1}, not {nu!r}")
+        for name, t, n in (("J", J, K), ("df", df, x.numel())):
+            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or
+                                  t.numel() != n):
+                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries")
+        y0 = np.ascontiguousarray(state0, dtype=np.float64).reshape(-1)
+        par = np.ascontiguousarray(() if params is None else params, dtype=np.float64).reshape(-1)
+        if y0.size != prog.ny or par.size != prog.nparams:
+            raise ValueError(f"the program takes {prog.ny} initial states and {prog.nparams} parameters")
+        if not prog.h:
+            raise ValueError("the ODE program is closed")
+        self._check(self.lib.mioc_ode_program_eval_mixed_device(
+            self.h, prog.h, int(nu), K, ctypes.c_void_p(x.data_ptr()), nt, float(T0), float(T1), _p(y0),
+            _p(par) if par.size else None,
+            ctypes.c_void_p(J.data_ptr()) if J is not None else None,
+            ctypes.c_void_p(df.data_ptr()) if df is not None else None))
+
+    def rows_copy_tensors(self, dst, dst_row0, src, src_row0, nrows):
+        """dst[:, :, dst_row0:dst_row0 + nrows] = src[:, :, src_row0:src_row0 + nrows] for float64 CUDA tensors
+        (K, nt, dst_nx) and (K, nt, src_nx); dst may be src with disjoint rows.  Enqueued, gated by trm_attach
+        (mioc_rows_copy_device); the row ranges are checked by the library."""
+        for name, t in (("dst", dst), ("src", src)):
+            if t.dim() != 3 or not t.is_contiguous() or not t.is_cuda or str(t.dtype) != "torch.float64":
+                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
+        if tuple(dst.shape[:2]) != tuple(src.shape[:2]):
+            raise ValueError("dst and src must agree in K and nt")
+        K, nt, dnx = dst.shape
+        self._check(self.lib.mioc_rows_copy_device(self.h, K, nt, ctypes.c_void_p(dst.data_ptr()), dnx, int(dst_row0),
+                                                   ctypes.c_void_p(src.data_ptr()), src.shape[2], int(src_row0),
+                                                   int(nrows)))
+
+    def mixed_state_tensor(self, K, s0):
+        """A device state block of the continuous step for K restarts (uint8 CUDA tensor): zeroed, the step sizes s0."""
+        import torch
+        n = int(self.lib.mioc_mixed_state_bytes(int(K)))
+        if n < 0:
+            raise ValueError("K must be in [1, 4096]")
+        if not (s0 > 0 and math.isfinite(s0)):
+            raise ValueError("s0 must be positive and finite")
+        b = np.zeros(n, dtype=np.uint8)
+        b[16:16 + 8 * int(K)].view(np.float64)[:] = float(s0)
+        return torch.from_numpy(b).to(f"cuda:{self.device}")
+
+    def _mixed_check(self, K, R, nu, nx, nt, mstate, f64, what):
+        if not 1 <= int(R) <= 16:
+            raise ValueError("R must be in 1..16")
+        if not 1 <= int(nu) <= nx:
+            raise ValueError(f"nu must be in 1..{nx}")
+        if not mstate.is_cuda or str(mstate.dtype) != "torch.uint8" or not mstate.is_contiguous() or \
+                mstate.numel() != int(self.lib.mioc_mixed_state_bytes(K)):
+            raise ValueError("mstate must be the uint8 CUDA tensor of mixed_state_tensor(K, s0)")
+        for name, t, n in f64:
+            if not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or t.numel() != n:
+                raise ValueError(f"{what}: {name} must be a contiguous float64 CUDA tensor with {n} entries")
+
+    def mixed_fan_tensors(self, R, nu, tau, x, df, lo, hi, mstate, xfan, slope):
+        """The R line-search candidates of every restart: x, df (K, nt, nx), lo, hi (nt, nu), xfan (R, K, nt, nx),
+        slope (R, K) float64 CUDA tensors; enqueued (mioc_mixed_fan_device)."""
+        if x.dim() != 3:
+            raise ValueError("x must have the shape (K, nt, nx)")
+        K, nt, nx = x.shape
+        self._mixed_check(K, R, nu, nx, nt, mstate,
+                          (("x", x, K * nt * nx), ("df", df, K * nt * nx), ("lo", lo, nt * nu), ("hi", hi, nt * nu),
+                           ("xfan", xfan, R * K * nt * nx), ("slope", slope, R * K)), "mixed_fan")
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        self._check(self.lib.mioc_mixed_fan_device(self.h, K, int(R), int(nu), nx, nt, float(tau), p(x), p(df), p(lo),
+                                                   p(hi), p(mstate), p(xfan), p(slope)))
+
+    def mixed_select_tensors(self, R, nu, c1, smax, ctol, mstate, trm_state, xfan, slope, Jfan, J_old, x):
+        """Per restart the first candidate that passes the Armijo test, the step-size update and the finality rule
+        (mioc_mixed_select_device): xfan (R, K, nt, nx), slope, Jfan (R, K), J_old (K,), x (K, nt, nx); trm_state the
+        block of trm_state_tensor(K).  Enqueued."""
+        if x.dim() != 3:
+            raise ValueError("x must have the shape (K, nt, nx)")
+        K, nt, nx = x.shape
+        self._mixed_check(K, R, nu, nx, nt, mstate,
+                          (("x", x, K * nt * nx), ("xfan", xfan, R * K * nt * nx), ("slope", slope, R * K),
+                           ("Jfan", Jfan, R * K), ("J_old", J_old, K)), "mixed_select")
+        if not trm_state.is_cuda or trm_state.numel() != int(self.lib.mioc_trm_state_bytes(K)):
+            raise ValueError("trm_state must be the CUDA tensor of trm_state_tensor(K)")
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        self._check(self.lib.mioc_mixed_select_device(self.h, K, int(R), int(nu), nx, nt, float(c1), float(smax),
+                                                      float(ctol), p(mstate), p(trm_state), p(xfan), p(slope), p(Jfan),
+                                                      p(J_old), p(x)))
+
+    def mixed_poll(self, mstate, trm_state):
+        """Synchronise once; (any restart inside its inner loop, any restart that can still move)
+        (mioc_mixed_poll)."""
+        out = np.zeros(2, dtype=np.int32)
+        self._check(self.lib.mioc_mixed_poll(self.h, ctypes.c_void_p(mstate.data_ptr()),
+                                             ctypes.c_void_p(trm_state.data_ptr()), _p(out)))
+        return bool(out[0]), bool(out[1])
+
+    def mixed_state_arrays(self, mstate, K):
+        """The mixed state block on the host: s, flags (1 final, 2 moved), jsel, csteps."""
+        self.synchronize()
+        b = mstate.cpu().numpy()
+        o = 16
+        out = {}
+        for name, dt in (("s", np.float64), ("flags", np.int32), ("jsel", np.int32), ("csteps", np.int32)):
+            n = K * np.dtype(dt).itemsize
+            out[name] = b[o:o + n].view(dt).copy()
+            o += n
+        return out
 
     def heat_setup(self, M_invA, M_invF, mass, state0, yd, T0, T1, gamma):
         """Hand the heat objective's matrices to the device (mioc_heat_setup; example_heat.jl:101-115): M_invA, mass

@@ -18,14 +18,33 @@ from .objective import AbstractObjectiveLazy
 
 
 class AbstractODEObjective(AbstractObjectiveLazy):
-    """min ∫ G(t, y, u) dt  s.t.  y' = F(t, y, u), y(T0) = y0 -- explicit Euler + trapezoid."""
+    """min ∫ G(t, y, u) dt  s.t.  y' = F(t, y, u), y(T0) = y0 -- explicit Euler + trapezoid.
 
-    def __init__(self, T0, T1, nt, V, iterator, state0):
+    ``nu`` continuous controls may stand in front of the ``len(V)`` integer ones (the reference's obj.nu, obj.umin,
+    obj.umax): the hooks then see x with nx = nu + nv rows, rows 0..nu-1 continuous.  ``umin`` / ``umax`` are their
+    pointwise bounds, scalars, (nu,) or (nu, nt), stored as (nu, nt) arrays; mioc.trm_mixed.TRM_mixed optimises such an
+    objective.  nu = 0 (the default) is the integer-only objective."""
+
+    def __init__(self, T0, T1, nt, V, iterator, state0, nu=0, umin=None, umax=None):
         self.T0, self.T1, self.nt = float(T0), float(T1), int(nt)
         self.V = [list(v) for v in V]
         self.iterator = iterator
         self.state0 = np.array(state0, dtype=np.float64)
-        self.nu = 0
+        self.nu = int(nu)
+        if self.nu < 0:
+            raise ValueError("nu must not be negative")
+        if self.nu:
+            if umin is None or umax is None:
+                raise ValueError("continuous controls need their bounds umin and umax")
+
+            def bound(b):
+                b = np.asarray(b, dtype=np.float64)
+                if b.ndim == 1:
+                    b = b[:, None]
+                return np.array(np.broadcast_to(b, (self.nu, self.nt)), order="C", copy=True)
+            self.umin, self.umax = bound(umin), bound(umax)
+            if not np.all(self.umin <= self.umax):
+                raise ValueError("need umin <= umax everywhere")
         self.nv = len(self.V)
         self.ny = len(self.state0)
         self.nx = self.nu + self.nv

@@ -163,6 +163,43 @@ class DeviceODEProblem:
         ctx.ode_program_eval_tensors(self.program, x, self.T0, self.T1, self.state0, self.params, J, df)
 
 
+class MixedODEProblem:
+    """An ODE-constrained problem with mixed controls for mioc.trm_mixed.TRM_mixed_batch: a compiled ``ODEProgram``
+    whose first ``nu`` controls are continuous with the pointwise bounds ``lo`` <= ``hi`` (scalars, (nu,) or (nt, nu);
+    kept as (nt, nu) numpy arrays, the device layout) and whose other nx - nu controls take the levels V with their
+    iterator (None: the product grid); then [T0, T1], the number of steps nt, state0 and the parameters."""
+
+    def __init__(self, program, nu, lo, hi, V, iterator, T0, T1, nt, state0, params=()):
+        import numpy as np
+        self.program = program
+        self.nu = int(nu)
+        self.V = [list(v) for v in V]
+        self.iterator = iterator
+        self.T0, self.T1, self.nt = float(T0), float(T1), int(nt)
+        self.state0 = [float(v) for v in state0]
+        self.params = [float(v) for v in params]
+        if int(nu) != nu or not 1 <= self.nu < program.nx:
+            raise ValueError(f"nu must be an integer in 1..{program.nx - 1} (nu = 0: DeviceODEProblem), not {nu!r}")
+        if len(self.V) != program.nx - self.nu:
+            raise ValueError("V must have one entry per integer control: the program's nx - nu")
+        if len(self.state0) != program.ny or len(self.params) != program.nparams:
+            raise ValueError("state0 and params must match the program's ny and nparams")
+        if not self.T1 > self.T0 or self.nt < 1:
+            raise ValueError("need T1 > T0 and nt >= 1")
+
+        def bound(b, name):
+            b = np.asarray(b, dtype=np.float64)
+            if b.ndim > 2 or (b.ndim == 1 and b.shape != (self.nu,)) or (b.ndim == 2 and b.shape != (self.nt, self.nu)):
+                raise ValueError(f"{name} must be a scalar or have the shape (nu,) or (nt, nu)")
+            return np.array(np.broadcast_to(b, (self.nt, self.nu)), order="C", copy=True)
+        self.lo, self.hi = bound(lo, "lo"), bound(hi, "hi")
+        if not np.all(self.lo <= self.hi):  # also refuses a NaN bound
+            raise ValueError("need lo <= hi everywhere")
+
+    def eval_tensors(self, ctx, x, J=None, df=None):
+        ctx.ode_program_eval_mixed_tensors(self.program, self.nu, x, self.T0, self.T1, self.state0, self.params, J, df)
+
+
 _SIG = "(const double *p, int i, double t, const double *y, const double *x"
 
 EXAMPLE_SOURCES = {
