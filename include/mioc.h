@@ -442,6 +442,50 @@ int32_t mioc_ode_eval_device(mioc_ctx *ctx, int32_t problem, int64_t K, const do
  *   b.v = 0, pow of a negative base with a Dual exponent (log of the base), pow(a, c) at a.v = 0 with c < 1; with
  *   a.v = 0 and a.d[k] = 0 such a rule gives 0.0/0.0 or 0.0*Inf = NaN where the derivative's limit may exist.
  *
+ * Terminal cost, sampled data, state output.  mioc_ode_program_create_bolza(..., ndata, ..., derive, flags, ...) widens
+ * the problem class to  min ∫ G(t, y, u, d(t)) dt + E(T1, y(T1))  s.t.  y' = F(t, y, u, d(t))  and hands the state
+ * trajectory back.  Each part is compiled in only when asked for: the head then #defines ND (= ndata, when > 0),
+ * MIOC_TERMINAL 1 (flag MIOC_ODE_TERMINAL) and MIOC_STATES 1 (flag MIOC_ODE_STATES) behind NY / NX / NP.  With
+ * ndata == 0 and flags == 0 the head is _create_ad's byte for byte and the skeletons preprocess to the same tokens, so
+ * such a program is the program it was.  mioc_ode_program_create_ad(...) is _bolza(ndata = 0, flags = 0).
+ *   data       d_data is nt x ndata doubles on the device, [i][e], 0 <= ndata <= 16: shared by all restarts and
+ *              piecewise constant on the control grid, like x.  The hook signatures do not change.  With ND > 0 the
+ *              p a hook receives has NP + ND entries: p[0..NP-1] the parameters, p[NP + e] = data[c][e], where c is
+ *              the control column whose x the hook is given:
+ *                Euler    column i for F(i, y_i, x_i);  column i+1 for G(i+1, y_{i+1}, x_{i+1});  column nt-1 for the
+ *                         last half-weight G and for the terminal Gy(nt, y_nt, x_{nt-1});  column i for everything in
+ *                         the backward sweep (Fu, Gu, Gy, Fy at (i, y_i, x_i)).
+ *                Heun, RK4, backward Euler, midpoint   column i = the control interval, for every stage and substep,
+ *                         forward and backward.
+ *              p is never differentiated, so derived hooks need no change.  The kernel reads the row straight from
+ *              global memory; the row index is the same for every lane and the pointer is restrict-qualified, so
+ *              the rows are scalar loads: d_data must not overlap d_J, d_df or d_Y.
+ *   terminal   with MIOC_ODE_TERMINAL the text also defines
+ *                __device__ double E (const double *p, double t, const double *y);
+ *                __device__ void   Ey(const double *p, double t, const double *y, double *ey);   ey[c] = dE/dy_c
+ *              or, with MIOC_ODE_DERIVE_EY (valid only with MIOC_ODE_TERMINAL; the head #defines MIOC_DERIVE_EY 1, for
+ *              an `#ifndef MIOC_DERIVE_EY` guard like the other four),
+ *                template <class T> __device__ T E(const double *p, double t, const T *y);
+ *              and Ey is generated with mioc_ad::Dual<NY> (ey[r] = E.d[r], every entry written).  E and Ey are called
+ *              once each, at the last state y_nt (Euler) or y_{nt*m}, with the data of column nt-1 and t the end time
+ *              as the skeleton forms it: Euler T0 + (double)nt*tau, the other schemes T0 + (double)(nt*m)*h.  ey is
+ *              zeroed once per evaluation, like gy.  A text without E fails to compile under "hooks:N".
+ *   rounding   Euler: J = fval*tau + E (one product, one sum);  terminal lam_r = (-0.5*tau)*gy_r - ey_r.
+ *              Heun, RK4, backward Euler, midpoint: J = q + E;  the backward sweep starts from w_r = ey_r in place of
+ *              0.0.  Nothing else in the orders above changes.
+ *   states     with MIOC_ODE_STATES the kernel takes one more pointer, d_Y: K x (nt+1) x ny doubles, [k][i][r], the
+ *              state at the control-grid points t_i = T0 + i*tau, i = 0..nt (Euler: y_i; the other schemes: y_{i*m});
+ *              row 0 is state0.  Substep and stage states are not output.  It is written in the forward sweep when
+ *              d_Y is not NULL, whether or not d_J and d_df are given.  A restart whose Newton iteration fails
+ *              (implicit schemes) has all its rows NaN.  The context's scratch and its layout are as before.
+ *   MIOC_EINVAL from _bolza: ndata outside 0..16, flag bits other than the two, MIOC_ODE_DERIVE_EY without
+ *              MIOC_ODE_TERMINAL (and every case of _create_ad).
+ * mioc_ode_program_eval_bolza_device is the body of the two eval entries with d_data and d_Y: nu == 0 applies the
+ *   check of mioc_ode_program_eval_device (nx == the levels' M), nu >= 1 that of _eval_mixed_device.  MIOC_EINVAL also
+ *   for ndata > 0 with d_data NULL and for d_Y on a program without MIOC_ODE_STATES; d_data is ignored with
+ *   ndata == 0.  The two older entries refuse a program with ndata > 0 (MIOC_EINVAL) and work as before on one with
+ *   the terminal or the states flag and ndata == 0 (no state output).  Gate, stream and scratch growth as there.
+ *
  * mioc_ode_program_create needs no context and no GPU: it compiles for gfx950 and keeps the code object.  Limits:
  *   1 <= ny <= 8, 1 <= nx <= 8, 0 <= nparams <= 32, source text of at most 1 MiB (else MIOC_EINVAL).  A compile
  *   failure returns MIOC_ECOMPILE; the compiler's log (also the warnings of a successful compile) is copied into
@@ -480,6 +524,14 @@ int32_t mioc_ode_program_create_ex(const char *hooks, int32_t ny, int32_t nx, in
 #define MIOC_ODE_DERIVE_ALL 15
 int32_t mioc_ode_program_create_ad(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t integrator,
                                    int32_t substeps, int32_t derive, mioc_ode_program **out, char *log, int64_t log_cap);
+/* The same with a terminal cost, ndata columns of sampled data and the state trajectory as an output (see "Terminal
+ * cost, sampled data, state output" above). */
+#define MIOC_ODE_TERMINAL 1      /* flags: the text defines E (and Ey unless derived) */
+#define MIOC_ODE_STATES   2      /* flags: the kernel can write the state trajectory */
+#define MIOC_ODE_DERIVE_EY 16    /* derive bit, valid only with MIOC_ODE_TERMINAL; not part of MIOC_ODE_DERIVE_ALL */
+int32_t mioc_ode_program_create_bolza(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
+                                      int32_t integrator, int32_t substeps, int32_t derive, int32_t flags,
+                                      mioc_ode_program **out, char *log, int64_t log_cap);
 int32_t mioc_ode_program_destroy(mioc_ode_program *prog);
 int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t K, const double *d_x, int64_t nt,
                                      double T0, double T1, const double *state0, const double *params, double *d_J,
@@ -530,6 +582,10 @@ int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int6
 int32_t mioc_ode_program_eval_mixed_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K,
                                            const double *d_x, int64_t nt, double T0, double T1, const double *state0,
                                            const double *params, double *d_J, double *d_df);
+int32_t mioc_ode_program_eval_bolza_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K,
+                                           const double *d_x, int64_t nt, double T0, double T1, const double *state0,
+                                           const double *params, const double *d_data, double *d_J, double *d_df,
+                                           double *d_Y);
 int32_t mioc_rows_copy_device(mioc_ctx *ctx, int64_t K, int64_t nt, double *d_dst, int64_t dst_nx, int64_t dst_row0,
                               const double *d_src, int64_t src_nx, int64_t src_row0, int64_t nrows);
 int64_t mioc_mixed_state_bytes(int64_t K);

@@ -294,6 +294,58 @@ function ode_program_eval_device!(ctx::Context, prog::Ptr{Cvoid}, K::Integer, d_
     nothing
 end
 
+# ---- a terminal cost, sampled data and the state trajectory (include/mioc.h, "Terminal cost, sampled data, state
+# output").  Thin wrappers of the two entries; they have not been run under Julia (none is installed where this was
+# written).
+const MIOC_ODE_TERMINAL = Int32(1)
+const MIOC_ODE_STATES = Int32(2)
+const MIOC_ODE_DERIVE_EY = Int32(16)
+
+"""
+    ode_program_create_bolza(hooks, ny, nx, nparams; ndata = 0, terminal = false, states = false,
+                             integrator = :euler, substeps = 1, derive = Symbol[]) -> Ptr{Cvoid}
+
+`ode_program_create` with `ndata` (0..16) columns of sampled data behind the parameters (`p[NP + e]`), a terminal cost
+(`terminal`: the text also defines E and Ey, or `derive` names `:Ey`; `:all` then includes it) and the state
+trajectory as an output (`states`) (mioc_ode_program_create_bolza).
+"""
+function ode_program_create_bolza(hooks::String, ny::Integer, nx::Integer, nparams::Integer; ndata::Integer = 0,
+                                  terminal::Bool = false, states::Bool = false, integrator::Symbol = :euler,
+                                  substeps::Integer = 1, derive = Symbol[])
+    haskey(ODE_INTEGRATORS, integrator) || error("integrator must be :euler, :heun, :rk4, :beuler or :midpoint")
+    bits = terminal ? merge(ODE_DERIVE, Dict(:Ey => MIOC_ODE_DERIVE_EY)) : ODE_DERIVE
+    names = derive === :all ? collect(keys(bits)) : collect(derive)
+    all(n -> haskey(bits, n), names) ||
+        error("derive must be :all or a collection of :Fy, :Fu, :Gy, :Gu (:Ey with terminal)")
+    mask = reduce(|, (bits[n] for n in names); init = Int32(0))
+    flags = (terminal ? MIOC_ODE_TERMINAL : Int32(0)) | (states ? MIOC_ODE_STATES : Int32(0))
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    log = zeros(UInt8, 1 << 16)
+    rc = ccall((:mioc_ode_program_create_bolza, libmioc), Int32,
+               (Cstring, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Ptr{Ptr{Cvoid}}, Ptr{UInt8}, Int64),
+               hooks, ny, nx, nparams, ndata, ODE_INTEGRATORS[integrator], substeps, mask, flags, r, log, length(log))
+    rc == MIOC_OK || error("mioc_ode_program_create_bolza failed with $rc:\n" * unsafe_string(pointer(log)))
+    r[]
+end
+
+"""
+    ode_program_eval_bolza_device!(ctx, prog, nu, K, d_x, nt, T0, T1, state0, params, d_data, d_J, d_df, d_Y)
+
+The eval entry with the data (`d_data`: nt × ndata doubles on the device, row i for control column i; C_NULL for a
+program without data) and the states (`d_Y`: K × (nt+1) × ny doubles, or C_NULL).  `nu = 0`: every control is the
+DP's; `nu ≥ 1`: a mixed control (mioc_ode_program_eval_bolza_device).
+"""
+function ode_program_eval_bolza_device!(ctx::Context, prog::Ptr{Cvoid}, nu::Integer, K::Integer, d_x::Ptr{Float64},
+                                        nt::Integer, T0::Float64, T1::Float64, state0::Vector{Float64},
+                                        params::Vector{Float64}, d_data::Ptr{Float64}, d_J::Ptr{Float64},
+                                        d_df::Ptr{Float64}, d_Y::Ptr{Float64})
+    check(ctx, ccall((:mioc_ode_program_eval_bolza_device, libmioc), Int32,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Float64, Float64, Ptr{Float64},
+                      Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ctx.ptr, prog, nu, K, d_x,
+                     nt, T0, T1, state0, params, d_data, d_J, d_df, d_Y))
+    nothing
+end
+
 # ---- mixed controls: nu continuous controls in front of the DP's integer ones (include/mioc.h, "Mixed controls").
 # Thin wrappers of the six entries; they have not been run under Julia (none is installed where this was written).
 

@@ -21,6 +21,12 @@
 // mioc_ode_program_create_ad generates Fy / Fu / Gy / Gu from templated F and G with a dual-number type (kAdPrelude,
 // kAdHooks) that is compiled into the same kernel; the skeletons and the launch are the same, and with derive == 0 so
 // is the source text.
+//
+// mioc_ode_program_create_bolza adds a terminal cost E (and Ey), ND columns of sampled data behind the parameters and
+// the state trajectory as an output (include/mioc.h, "Terminal cost, sampled data, state output").  Each is an #if in
+// the three skeletons, switched by a macro of the head (ND, MIOC_TERMINAL, MIOC_STATES), and the kernel takes the data
+// and the state pointer only then: with ndata == 0 and flags == 0 the head has no new byte and the skeletons preprocess
+// to the tokens they had, so such a program's code object is the one it was.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -37,7 +43,7 @@
 
 namespace {
 
-constexpr int kMaxNY = 8, kMaxNX = 8, kMaxNP = 32, kMaxSubsteps = 64;
+constexpr int kMaxNY = 8, kMaxNX = 8, kMaxNP = 32, kMaxND = 16, kMaxSubsteps = 64;
 constexpr size_t kMaxSource = 1u << 20;
 const char *const kKernelName = "mioc_ode_program_kernel";
 const char *const kNoinlineNote =
@@ -45,6 +51,25 @@ const char *const kNoinlineNote =
 
 // The skeleton follows the user text.  NY, NX, NP are #defined in front of both.
 const char *const kSkeleton = R"SKEL(
+#ifndef ND
+#define ND 0
+#endif
+#if ND > 0  // sampled data: p is a per-lane copy of the parameters with the data row of the current column behind them
+#define MIOC_DATA_ARG , const double *__restrict__ DATA
+#define MIOC_DATA_ROW(c)                                \
+  {                                                     \
+    const double *row = DATA + (size_t)(c) * ND;        \
+    _Pragma("unroll") for (int e = 0; e < ND; ++e) pe[NP + e] = row[e]; \
+  }
+#else
+#define MIOC_DATA_ARG
+#define MIOC_DATA_ROW(c)
+#endif
+#ifdef MIOC_STATES  // YO: the states at the control-grid points, [k][i][r], i = 0..nt
+#define MIOC_STATES_ARG , double *YO
+#else
+#define MIOC_STATES_ARG
+#endif
 namespace mioc_skeleton {
 struct Par {
   double y0[NY];
@@ -54,12 +79,19 @@ struct Par {
 
 extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
     int K, int nt, double T0, double tau, mioc_skeleton::Par P, const double *X, double *J, double *DF, double *ST,
-    const int *gate) {
+    const int *gate MIOC_DATA_ARG MIOC_STATES_ARG) {
   if (gate && *gate == 0) return;  // device TRM control: no restart is inside its inner loop
   const unsigned ku = blockIdx.x * 64u + threadIdx.x;
   if (ku >= (unsigned)K) return;
   const size_t k = ku, KK = (size_t)K;
+#if ND > 0
+  double pe[NP + ND];
+#pragma unroll
+  for (int e = 0; e < NP; ++e) pe[e] = P.p[e];
+  const double *p = pe;
+#else
   const double *p = P.p;
+#endif
   const double *x = X + k * (size_t)nt * NX;
   // ---- forward: explicit Euler, trapezoid cost (ODEObjective.jl:125-150) ----
   double y[NY], f[NY], xc[NX], xn[NX];
@@ -67,6 +99,14 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
   for (int r = 0; r < NY; ++r) y[r] = P.y0[r];
 #pragma unroll
   for (int m = 0; m < NX; ++m) xc[m] = x[m];
+  MIOC_DATA_ROW(0)  // the data row is that of the control column: xc's for F, xn's for G, column nt - 1 at the end
+#ifdef MIOC_STATES
+  double *yo = YO ? YO + k * ((size_t)nt + 1) * NY : nullptr;
+  if (yo) {
+#pragma unroll
+    for (int r = 0; r < NY; ++r) yo[r] = y[r];
+  }
+#endif
   double fval = 0.5 * G(p, 0, T0 + 0.0 * tau, y, xc);
   for (int i = 0; i < nt; ++i) {
     F(p, i, T0 + (double)i * tau, y, xc, f);
@@ -76,9 +116,16 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
 #pragma unroll
       for (int r = 0; r < NY; ++r) ST[((size_t)i * NY + r) * KK + k] = y[r];
     }
+#ifdef MIOC_STATES
+    if (yo) {
+#pragma unroll
+      for (int r = 0; r < NY; ++r) yo[((size_t)i + 1) * NY + r] = y[r];
+    }
+#endif
     if (i < nt - 1) {  // G at step i + 1 sees the control column of step i + 1
 #pragma unroll
       for (int m = 0; m < NX; ++m) xn[m] = x[(size_t)(i + 1) * NX + m];
+      MIOC_DATA_ROW(i + 1)
       fval = fval + G(p, i + 1, T0 + (double)(i + 1) * tau, y, xn);
 #pragma unroll
       for (int m = 0; m < NX; ++m) xc[m] = xn[m];
@@ -86,7 +133,11 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
       fval = fval + 0.5 * G(p, nt - 1, T0 + (double)(nt - 1) * tau, y, xc);
     }
   }
+#ifdef MIOC_TERMINAL  // the Mayer term at the end time and the last state, data column nt - 1
+  if (J) J[k] = fval * tau + E(p, T0 + (double)nt * tau, y);
+#else
   if (J) J[k] = fval * tau;
+#endif
   if (!DF) return;
   // ---- backward: adjoint and df = Gu - Fu' lambda (ODEObjective.jl:153-184) ----
   // here y is the state after the last step and xc the last control column
@@ -103,8 +154,17 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
 #pragma unroll
   for (int m = 0; m < NX; ++m) gu[m] = 0.0;
   Gy(p, nt, T0 + (double)nt * tau, y, xc, gy);
+#ifdef MIOC_TERMINAL
+  double ey[NY];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) ey[r] = 0.0;
+  Ey(p, T0 + (double)nt * tau, y, ey);
+#pragma unroll
+  for (int r = 0; r < NY; ++r) lam[r] = (-0.5 * tau) * gy[r] - ey[r];
+#else
 #pragma unroll
   for (int r = 0; r < NY; ++r) lam[r] = (-0.5 * tau) * gy[r];
+#endif
   for (int i = nt - 1; i >= 0; --i) {
     // df[:, i] needs lambda_i and the state before step i (state0 for i = 0); xc is the control column of step i
     const double t = T0 + (double)i * tau;
@@ -139,6 +199,7 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
     for (int c = 0; c < NY; ++c) lam[c] = lam[c] + tau * (a[c] - gy[c]);
 #pragma unroll
     for (int m = 0; m < NX; ++m) xc[m] = x[(size_t)(i - 1) * NX + m];
+    MIOC_DATA_ROW(i - 1)
   }
 }
 )SKEL";
@@ -148,6 +209,25 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
 // stage loop is fully unrolled, so ch / ha / hb and the stage arrays are indexed by constants and stay in registers.
 // ST holds y_n for every substep n = 0 .. nt*ms - 1, [n][r][k].
 const char *const kSkeletonRK = R"SKEL(
+#ifndef ND
+#define ND 0
+#endif
+#if ND > 0  // sampled data: p is a per-lane copy of the parameters with the data row of the current column behind them
+#define MIOC_DATA_ARG , const double *__restrict__ DATA
+#define MIOC_DATA_ROW(c)                                \
+  {                                                     \
+    const double *row = DATA + (size_t)(c) * ND;        \
+    _Pragma("unroll") for (int e = 0; e < ND; ++e) pe[NP + e] = row[e]; \
+  }
+#else
+#define MIOC_DATA_ARG
+#define MIOC_DATA_ROW(c)
+#endif
+#ifdef MIOC_STATES  // YO: the states at the control-grid points, [k][i][r], i = 0..nt
+#define MIOC_STATES_ARG , double *YO
+#else
+#define MIOC_STATES_ARG
+#endif
 namespace mioc_skeleton {
 struct Par {
   double y0[NY];
@@ -157,12 +237,19 @@ struct Par {
 
 extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
     int K, int nt, int ms, double T0, double tau, double h, mioc_skeleton::Par P, const double *X, double *J,
-    double *DF, double *ST, const int *gate) {
+    double *DF, double *ST, const int *gate MIOC_DATA_ARG MIOC_STATES_ARG) {
   if (gate && *gate == 0) return;  // device TRM control: no restart is inside its inner loop
   const unsigned ku = blockIdx.x * 64u + threadIdx.x;
   if (ku >= (unsigned)K) return;
   const size_t k = ku, KK = (size_t)K;
+#if ND > 0
+  double pe[NP + ND];
+#pragma unroll
+  for (int e = 0; e < NP; ++e) pe[e] = P.p[e];
+  const double *p = pe;
+#else
   const double *p = P.p;
+#endif
   const double *x = X + k * (size_t)nt * NX;
   // stage time offsets c_s h, stage weights h a_{s,s-1} (ha[0] unused) and h b_s
   double ch[NS], ha[NS], hb[NS];
@@ -179,10 +266,18 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
   double y[NY], Y[NY], kk[NS][NY], g[NS], xc[NX];
 #pragma unroll
   for (int r = 0; r < NY; ++r) y[r] = P.y0[r];
+#ifdef MIOC_STATES
+  double *yo = YO ? YO + k * ((size_t)nt + 1) * NY : nullptr;
+  if (yo) {
+#pragma unroll
+    for (int r = 0; r < NY; ++r) yo[r] = y[r];
+  }
+#endif
   double q = 0.0;
   for (int i = 0; i < nt; ++i) {
 #pragma unroll
     for (int m = 0; m < NX; ++m) xc[m] = x[(size_t)i * NX + m];
+    MIOC_DATA_ROW(i)  // the data row of the control interval, for every stage and substep
     for (int j = 0; j < ms; ++j) {
       const long long n = (long long)i * ms + j;
       const double tn = T0 + (double)n * h;
@@ -209,8 +304,19 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
       for (int s = 1; s < NS; ++s) inc = inc + hb[s] * g[s];
       q = q + inc;
     }
+#ifdef MIOC_STATES
+    if (yo) {
+#pragma unroll
+      for (int r = 0; r < NY; ++r) yo[((size_t)i + 1) * NY + r] = y[r];
+    }
+#endif
   }
+#ifdef MIOC_TERMINAL  // the Mayer term at the end time and the last state, data column nt - 1
+  const double tend = T0 + (double)((long long)nt * ms) * h;
+  if (J) J[k] = q + E(p, tend, y);
+#else
   if (J) J[k] = q;
+#endif
   if (!DF) return;
   // ---- backward: the scheme's discrete adjoint; df[:, i] = xbar_i / tau ----
   double *df = DF + k * (size_t)nt * NX;
@@ -227,12 +333,21 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
   }
 #pragma unroll
   for (int m = 0; m < NX; ++m) gu[m] = 0.0;
+#ifdef MIOC_TERMINAL  // the sweep starts from w = Ey at the last state (y still holds it; the data row is nt - 1's)
+  double ey[NY];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) ey[r] = 0.0;
+  Ey(p, tend, y, ey);
+#pragma unroll
+  for (int r = 0; r < NY; ++r) w[r] = ey[r];
+#endif
   for (int i = nt - 1; i >= 0; --i) {
 #pragma unroll
     for (int m = 0; m < NX; ++m) {
       xc[m] = x[(size_t)i * NX + m];
       xbar[m] = 0.0;
     }
+    MIOC_DATA_ROW(i)
     for (int j = ms - 1; j >= 0; --j) {
       const long long n = (long long)i * ms + j;
       const double tn = T0 + (double)n * h;
@@ -288,6 +403,25 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
 const char *const kSkeletonTheta = R"SKEL(
 #define MIOC_ODE_NEWTON_MAX 12
 #define MIOC_ODE_NEWTON_TOL 1e-10
+#ifndef ND
+#define ND 0
+#endif
+#if ND > 0  // sampled data: p is a per-lane copy of the parameters with the data row of the current column behind them
+#define MIOC_DATA_ARG , const double *__restrict__ DATA
+#define MIOC_DATA_ROW(c)                                \
+  {                                                     \
+    const double *row = DATA + (size_t)(c) * ND;        \
+    _Pragma("unroll") for (int e = 0; e < ND; ++e) pe[NP + e] = row[e]; \
+  }
+#else
+#define MIOC_DATA_ARG
+#define MIOC_DATA_ROW(c)
+#endif
+#ifdef MIOC_STATES  // YO: the states at the control-grid points, [k][i][r], i = 0..nt
+#define MIOC_STATES_ARG , double *YO
+#else
+#define MIOC_STATES_ARG
+#endif
 namespace mioc_skeleton {
 struct Par {
   double y0[NY];
@@ -334,12 +468,19 @@ __device__ __forceinline__ void solve(double (*A)[NY], double *b, double *d) {
 
 extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
     int K, int nt, int ms, double T0, double tau, double h, mioc_skeleton::Par P, const double *X, double *J,
-    double *DF, double *ST, const int *gate) {
+    double *DF, double *ST, const int *gate MIOC_DATA_ARG MIOC_STATES_ARG) {
   if (gate && *gate == 0) return;  // device TRM control: no restart is inside its inner loop
   const unsigned ku = blockIdx.x * 64u + threadIdx.x;
   if (ku >= (unsigned)K) return;
   const size_t k = ku, KK = (size_t)K;
+#if ND > 0
+  double pe[NP + ND];
+#pragma unroll
+  for (int e = 0; e < NP; ++e) pe[e] = P.p[e];
+  const double *p = pe;
+#else
   const double *p = P.p;
+#endif
   const double *x = X + k * (size_t)nt * NX;
   const double th = TH * h, thh = th * h;  // theta h and (theta h) h, each rounded once
   // ---- forward: Newton on k = F(y_n + th k) from k = F(y_n); y_{n+1} = y_n + h k, q_{n+1} = q_n + h G(Y) ----
@@ -350,11 +491,19 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
 #pragma unroll
     for (int c = 0; c < NY; ++c) fy[r][c] = 0.0;  // zeroed once per evaluation, as in the other skeletons
   }
+#ifdef MIOC_STATES
+  double *yo = YO ? YO + k * ((size_t)nt + 1) * NY : nullptr;
+  if (yo) {
+#pragma unroll
+    for (int r = 0; r < NY; ++r) yo[r] = y[r];
+  }
+#endif
   double q = 0.0;
   bool failed = false;
   for (int i = 0; i < nt && !failed; ++i) {
 #pragma unroll
     for (int m = 0; m < NX; ++m) xc[m] = x[(size_t)i * NX + m];
+    MIOC_DATA_ROW(i)  // the data row of the control interval, for every substep
     for (int j = 0; j < ms && !failed; ++j) {
       const long long n = (long long)i * ms + j;
       const double ts = (T0 + (double)n * h) + th;
@@ -396,15 +545,30 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
 #pragma unroll
       for (int r = 0; r < NY; ++r) y[r] = y[r] + h * kv[r];
     }
+#ifdef MIOC_STATES
+    if (yo) {
+#pragma unroll
+      for (int r = 0; r < NY; ++r) yo[((size_t)i + 1) * NY + r] = y[r];
+    }
+#endif
   }
   if (failed) {  // a substep's Newton iteration did not converge: this restart's J and df row are NaN
     const double nan = __builtin_nan("");
     if (J) J[k] = nan;
     if (DF)
       for (size_t e = 0; e < (size_t)nt * NX; ++e) DF[k * (size_t)nt * NX + e] = nan;
+#ifdef MIOC_STATES  // and so is its state trajectory, the rows already written included
+    if (yo)
+      for (size_t e = 0; e < ((size_t)nt + 1) * NY; ++e) yo[e] = nan;
+#endif
     return;
   }
+#ifdef MIOC_TERMINAL  // the Mayer term at the end time and the last state, data column nt - 1
+  const double tend = T0 + (double)((long long)nt * ms) * h;
+  if (J) J[k] = q + E(p, tend, y);
+#else
   if (J) J[k] = q;
+#endif
   if (!DF) return;
   // ---- backward: (I - th Fy)' mu = h w + (th h) Gy at the stored Y; df[:, i] = xbar_i / tau ----
   double *df = DF + k * (size_t)nt * NX;
@@ -418,12 +582,21 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
   }
 #pragma unroll
   for (int m = 0; m < NX; ++m) gu[m] = 0.0;
+#ifdef MIOC_TERMINAL  // the sweep starts from w = Ey at the last state (y still holds it; the data row is nt - 1's)
+  double ey[NY];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) ey[r] = 0.0;
+  Ey(p, tend, y, ey);
+#pragma unroll
+  for (int r = 0; r < NY; ++r) w[r] = ey[r];
+#endif
   for (int i = nt - 1; i >= 0; --i) {
 #pragma unroll
     for (int m = 0; m < NX; ++m) {
       xc[m] = x[(size_t)i * NX + m];
       xbar[m] = 0.0;
     }
+    MIOC_DATA_ROW(i)
     for (int j = ms - 1; j >= 0; --j) {
       const long long n = (long long)i * ms + j;
       const double ts = (T0 + (double)n * h) + th;
@@ -675,9 +848,9 @@ MIOC_AD_FN fmax(double a, const Dual<N> &b) { return b.v > a ? b : Dual<N>(a); }
 }  // namespace mioc_ad
 )SKEL";
 
-// The generated hooks: F or G once with T = mioc_ad::Dual<N>, the unit tangents on y (Fy, Gy: N = NY) or on x (Fu,
-// Gu: N = NX), the other argument constant.  Every entry of the output is written.  Each stands under the guard macro
-// that the head defines for a derived hook.  MIOC_AD_NOINLINE (the second compile of mioc_ode_program_create_ad) makes
+// The generated hooks: F, G or E once with T = mioc_ad::Dual<N>, the unit tangents on y (Fy, Gy, Ey: N = NY) or on x
+// (Fu, Gu: N = NX), the other argument constant.  Every entry of the output is written.  Each stands under the guard
+// macro that the head defines for a derived hook.  MIOC_AD_NOINLINE (the second compile of mioc_ode_program_create_ad) makes
 // them functions that are called: one body each, where the Heun / RK4 skeleton would inline one per stage.
 const char *const kAdHooks = R"SKEL(
 #ifdef MIOC_AD_NOINLINE
@@ -749,6 +922,19 @@ MIOC_AD_HOOK void Gu(const double *p, int i, double t, const double *y, const do
   const mioc_ad::Dual<NX> g = G(p, i, t, (const mioc_ad::Dual<NX> *)yd, (const mioc_ad::Dual<NX> *)xd);
 #pragma unroll
   for (int m = 0; m < NX; ++m) gu[m] = g.d[m];
+}
+#endif
+#ifdef MIOC_DERIVE_EY
+MIOC_AD_HOOK void Ey(const double *p, double t, const double *y, double *ey) {
+  mioc_ad::Dual<NY> yd[NY];
+#pragma unroll
+  for (int r = 0; r < NY; ++r) {
+    yd[r] = y[r];
+    yd[r].d[r] = 1.0;
+  }
+  const mioc_ad::Dual<NY> e = E(p, t, (const mioc_ad::Dual<NY> *)yd);
+#pragma unroll
+  for (int r = 0; r < NY; ++r) ey[r] = e.d[r];
 }
 #endif
 )SKEL";
@@ -839,7 +1025,7 @@ std::string without_remarks(const std::string &log) {
 }  // namespace
 
 struct mioc_ode_program {
-  int ny = 0, nx = 0, np = 0;
+  int ny = 0, nx = 0, np = 0, nd = 0, flags = 0;
   int integrator = MIOC_ODE_INT_EULER, substeps = 1;
   std::vector<char> code;  // the gfx950 code object
   struct Loaded {
@@ -866,15 +1052,23 @@ int32_t mioc_ode_program_create_ex(const char *hooks, int32_t ny, int32_t nx, in
 int32_t mioc_ode_program_create_ad(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t integrator,
                                    int32_t substeps, int32_t derive, mioc_ode_program **out, char *log,
                                    int64_t log_cap) {
+  return mioc_ode_program_create_bolza(hooks, ny, nx, nparams, 0, integrator, substeps, derive, 0, out, log, log_cap);
+}
+
+int32_t mioc_ode_program_create_bolza(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
+                                      int32_t integrator, int32_t substeps, int32_t derive, int32_t flags,
+                                      mioc_ode_program **out, char *log, int64_t log_cap) {
   put_log(log, log_cap, "", 0);
   if (!out) return MIOC_EINVAL;
   *out = nullptr;
   if (!hooks || ny < 1 || ny > kMaxNY || nx < 1 || nx > kMaxNX || nparams < 0 || nparams > kMaxNP) return MIOC_EINVAL;
+  if (ndata < 0 || ndata > kMaxND || (flags & ~(MIOC_ODE_TERMINAL | MIOC_ODE_STATES))) return MIOC_EINVAL;
   const bool implicit = integrator == MIOC_ODE_INT_BEULER || integrator == MIOC_ODE_INT_MIDPOINT;
   if (integrator != MIOC_ODE_INT_EULER && integrator != MIOC_ODE_INT_HEUN && integrator != MIOC_ODE_INT_RK4 && !implicit)
     return MIOC_EINVAL;
   if (substeps < 1 || substeps > kMaxSubsteps || (integrator == MIOC_ODE_INT_EULER && substeps != 1)) return MIOC_EINVAL;
-  if (derive & ~MIOC_ODE_DERIVE_ALL) return MIOC_EINVAL;
+  if (derive & ~(MIOC_ODE_DERIVE_ALL | MIOC_ODE_DERIVE_EY)) return MIOC_EINVAL;
+  if ((derive & MIOC_ODE_DERIVE_EY) && !(flags & MIOC_ODE_TERMINAL)) return MIOC_EINVAL;
   // the reference scheme keeps its own skeleton and its head, so its source text is what it was
   const char *const skeleton = integrator == MIOC_ODE_INT_EULER ? kSkeleton : implicit ? kSkeletonTheta : kSkeletonRK;
   const size_t len = strnlen(hooks, kMaxSource + 1);
@@ -897,16 +1091,24 @@ int32_t mioc_ode_program_create_ad(const char *hooks, int32_t ny, int32_t nx, in
                     (int)nparams, integrator == MIOC_ODE_INT_HEUN ? 2 : 4);
     src.reserve(len + std::strlen(skeleton) + (derive ? std::strlen(kAdPrelude) + std::strlen(kAdHooks) : 0) + 512);
     src = head;
+    // sampled data, the terminal cost and the state output are compiled in only when asked for: none adds a byte here
+    if (ndata > 0) src += "#define ND " + std::to_string((int)ndata) + "\n";
+    if (flags & MIOC_ODE_TERMINAL) src += "#define MIOC_TERMINAL 1\n";
+    if (flags & MIOC_ODE_STATES) src += "#define MIOC_STATES 1\n";
     if (derive) {  // the guard macros and the dual type in front of the caller's text; derive == 0 adds no byte
       if (derive & MIOC_ODE_DERIVE_FY) src += "#define MIOC_DERIVE_FY 1\n";
       if (derive & MIOC_ODE_DERIVE_FU) src += "#define MIOC_DERIVE_FU 1\n";
       if (derive & MIOC_ODE_DERIVE_GY) src += "#define MIOC_DERIVE_GY 1\n";
       if (derive & MIOC_ODE_DERIVE_GU) src += "#define MIOC_DERIVE_GU 1\n";
+      if (derive & MIOC_ODE_DERIVE_EY) src += "#define MIOC_DERIVE_EY 1\n";
       src += "#line 1 \"mioc_ad\"";
       src += kAdPrelude;
     }
     src += "#line 1 \"hooks\"\n";
     src.append(hooks, len);
+    if (flags & MIOC_ODE_TERMINAL)  // still under "hooks": a text without E is diagnosed there (hooks:N) first
+      src += "\n__device__ inline double mioc_terminal_needs_E(const double *p, double t, const double *y) "
+             "{ return E(p, t, y); }";
     if (derive) {  // the generated hooks between the caller's text and the skeleton
       src += "\n#line 1 \"mioc_ad_hooks\"";
       src += kAdHooks;
@@ -954,7 +1156,7 @@ int32_t mioc_ode_program_create_ad(const char *hooks, int32_t ny, int32_t nx, in
       } else {
         size_t cn = 0;
         mioc_ode_program *p = new mioc_ode_program;
-        p->ny = ny, p->nx = nx, p->np = nparams;
+        p->ny = ny, p->nx = nx, p->np = nparams, p->nd = ndata, p->flags = flags;
         p->integrator = integrator, p->substeps = substeps;
         if (R.code_size(prog, &cn) != HIPRTC_SUCCESS || cn == 0) {
           ret = MIOC_ECOMPILE;
@@ -997,14 +1199,17 @@ int32_t mioc_ode_program_destroy(mioc_ode_program *prog) {
 // The body of both eval entries.  nu = 0: every control is the DP's (mioc_ode_program_eval_device); nu >= 1: the first
 // nu controls are continuous and the levels describe the other nx - nu (mioc_ode_program_eval_mixed_device).
 static int32_t program_eval(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K, const double *d_x, int64_t nt,
-                            double T0, double T1, const double *state0, const double *params, double *d_J,
-                            double *d_df) {
+                            double T0, double T1, const double *state0, const double *params, const double *d_data,
+                            double *d_J, double *d_df, double *d_Y) {
   if (!ctx) return MIOC_EINVAL;
   MIOC_JOIN_BT(ctx);
   if (!prog) return fail(ctx, MIOC_EINVAL, "no ODE program");
   if (K < 1 || nt < 1 || K > INT32_MAX || nt > INT32_MAX || !d_x) return fail(ctx, MIOC_EINVAL, "bad K / nt / x");
   if (!state0 || (prog->np > 0 && !params)) return fail(ctx, MIOC_EINVAL, "state0 / params missing");
   if (!(T1 > T0)) return fail(ctx, MIOC_EINVAL, "need T1 > T0");
+  if (prog->nd > 0 && !d_data) return fail(ctx, MIOC_EINVAL, "the program reads sampled data: d_data missing");
+  if (d_Y && !(prog->flags & MIOC_ODE_STATES))
+    return fail(ctx, MIOC_EINVAL, "the program was not created with MIOC_ODE_STATES");
   if (nu < 0 || nu >= prog->nx) return fail(ctx, MIOC_EINVAL, "need 1 <= nu < the program's nx");
   if (ctx->have_levels && ctx->M != prog->nx - nu)
     return fail(ctx, MIOC_EINVAL, nu ? "the program's nx differs from nu + the levels' number of controls"
@@ -1048,9 +1253,13 @@ static int32_t program_eval(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, i
   const double *X = d_x;
   double *ST = ctx->d_ode_state.get();
   const int32_t *gate = ctx->gate;
-  void *args_euler[] = {&Ki, &nti, &t0, &tau, par, &X, &d_J, &d_df, &ST, &gate};
-  void *args_rk[] = {&Ki, &nti, &ms, &t0, &tau, &h, par, &X, &d_J, &d_df, &ST, &gate};
+  // the data pointer and the state output follow the gate, each only in a kernel compiled with it
+  void *args_euler[12] = {&Ki, &nti, &t0, &tau, par, &X, &d_J, &d_df, &ST, &gate};
+  void *args_rk[14] = {&Ki, &nti, &ms, &t0, &tau, &h, par, &X, &d_J, &d_df, &ST, &gate};
   void **args = euler ? args_euler : args_rk;
+  int na = euler ? 10 : 12;
+  if (prog->nd > 0) args[na++] = &d_data;
+  if (prog->flags & MIOC_ODE_STATES) args[na++] = &d_Y;
   const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)((K + 63) / 64), 1, 1, 64, 1, 1, 0, ctx->stream, args, nullptr);
   if (e != hipSuccess) return fail(ctx, MIOC_EHIP, std::string("launching the ODE program: ") + hipGetErrorString(e));
   return MIOC_OK;
@@ -1059,14 +1268,25 @@ static int32_t program_eval(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, i
 int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t K, const double *d_x, int64_t nt,
                                      double T0, double T1, const double *state0, const double *params, double *d_J,
                                      double *d_df) {
-  return program_eval(ctx, prog, 0, K, d_x, nt, T0, T1, state0, params, d_J, d_df);
+  if (ctx && prog && prog->nd > 0)
+    return fail(ctx, MIOC_EINVAL, "the program reads sampled data: use mioc_ode_program_eval_bolza_device");
+  return program_eval(ctx, prog, 0, K, d_x, nt, T0, T1, state0, params, nullptr, d_J, d_df, nullptr);
 }
 
 int32_t mioc_ode_program_eval_mixed_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K,
                                            const double *d_x, int64_t nt, double T0, double T1, const double *state0,
                                            const double *params, double *d_J, double *d_df) {
   if (ctx && nu < 1) return fail(ctx, MIOC_EINVAL, "need 1 <= nu < the program's nx");
-  return program_eval(ctx, prog, nu, K, d_x, nt, T0, T1, state0, params, d_J, d_df);
+  if (ctx && prog && prog->nd > 0)
+    return fail(ctx, MIOC_EINVAL, "the program reads sampled data: use mioc_ode_program_eval_bolza_device");
+  return program_eval(ctx, prog, nu, K, d_x, nt, T0, T1, state0, params, nullptr, d_J, d_df, nullptr);
+}
+
+int32_t mioc_ode_program_eval_bolza_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K,
+                                           const double *d_x, int64_t nt, double T0, double T1, const double *state0,
+                                           const double *params, const double *d_data, double *d_J, double *d_df,
+                                           double *d_Y) {
+  return program_eval(ctx, prog, nu, K, d_x, nt, T0, T1, state0, params, d_data, d_J, d_df, d_Y);
 }
 
 }  // extern "C"

@@ -40,6 +40,7 @@ MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_RK4 = 0, 1, 2
 MIOC_ODE_INT_BEULER, MIOC_ODE_INT_MIDPOINT = 16, 17  # the implicit schemes start at 16
 MIOC_ODE_NEWTON_MAX, MIOC_ODE_NEWTON_TOL = 12, 1e-10
 MIOC_ODE_DERIVE_FY, MIOC_ODE_DERIVE_FU, MIOC_ODE_DERIVE_GY, MIOC_ODE_DERIVE_GU, MIOC_ODE_DERIVE_ALL = 1, 2, 4, 8, 15
+MIOC_ODE_TERMINAL, MIOC_ODE_STATES, MIOC_ODE_DERIVE_EY = 1, 2, 16  # flags of _create_bolza; the derive bit of Ey
 
 EXPORTED = [
     "mioc_version", "mioc_create", "mioc_destroy", "mioc_last_error", "mioc_set_option", "mioc_set_levels",
@@ -55,6 +56,7 @@ EXPORTED = [
     "mioc_trm_poll",
     "mioc_ode_program_create", "mioc_ode_program_destroy", "mioc_ode_program_eval_device",
     "mioc_ode_program_create_ex", "mioc_ode_program_create_ad",
+    "mioc_ode_program_create_bolza", "mioc_ode_program_eval_bolza_device",
     "mioc_ode_program_eval_mixed_device", "mioc_rows_copy_device", "mioc_mixed_state_bytes", "mioc_mixed_fan_device",
     "mioc_mixed_select_device", "mioc_mixed_poll",
 ]
@@ -146,7 +148,10 @@ def load_library(path=None):
                                              ctypes.c_char_p, i64]),
         "mioc_ode_program_create_ad": (i32, [ctypes.c_char_p, i32, i32, i32, i32, i32, i32, ctypes.POINTER(vp),
                                              ctypes.c_char_p, i64]),
+        "mioc_ode_program_create_bolza": (i32, [ctypes.c_char_p, i32, i32, i32, i32, i32, i32, i32, i32,
+                                                ctypes.POINTER(vp), ctypes.c_char_p, i64]),
         "mioc_ode_program_destroy": (i32, [vp]),
+        "mioc_ode_program_eval_bolza_device": (i32, [vp, vp, i64, i64, vp, i64, dbl, dbl, vp, vp, vp, vp, vp, vp]),
         "mioc_ode_program_eval_device": (i32, [vp, vp, i64, vp, i64, dbl, dbl, vp, vp, vp, vp]),
         "mioc_ode_program_eval_mixed_device": (i32, [vp, vp, i64, i64, vp, i64, dbl, dbl, vp, vp, vp, vp]),
         "mioc_rows_copy_device": (i32, [vp, i64, i64, vp, i64, i64, vp, i64, i64, i64]),
@@ -461,58 +466,56 @@ class Context:
             ctypes.c_void_p(J.data_ptr()) if J is not None else None,
             ctypes.c_void_p(df.data_ptr()) if df is not None else None))
 
-    def ode_program_eval_tensors(self, prog, x, T0, T1, state0, params, J=None, df=None):
+    def _ode_program_eval(self, prog, nu, x, T0, T1, state0, params, J, df, data, Y):
+        """The body of ode_program_eval_tensors (nu None) and ode_program_eval_mixed_tensors.  Without data and Y the
+        call goes to the entry it always went to; with either to mioc_ode_program_eval_bolza_device."""
+        if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
+            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
+        K, nt, nx = x.shape
+        if nx != prog.nx:
+            raise ValueError(f"x has {nx} controls, the program {prog.nx}")
+        if nu is not None and (int(nu) != nu or not 1 <= nu < nx):
+            raise ValueError(f"nu must be an integer in 1..{nx - 1}, not {nu!r}")
+        for name, t, n in (("J", J, K), ("df", df, x.numel()), ("data", data, nt * getattr(prog, "ndata", 0)),
+                           ("Y", Y, K * (nt + 1) * prog.ny)):
+            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or
+                                  t.numel() != n):
+                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries")
+        if Y is not None and not getattr(prog, "states", False):
+            raise ValueError("the program was not compiled with states=True")
+        y0 = np.ascontiguousarray(state0, dtype=np.float64).reshape(-1)
+        par = np.ascontiguousarray(() if params is None else params, dtype=np.float64).reshape(-1)
+        if y0.size != prog.ny or par.size != prog.nparams:
+            raise ValueError(f"the program takes {prog.ny} initial states and {prog.nparams} parameters")
+        if not prog.h:
+            raise ValueError("the ODE program is closed")
+
+        def ptr(t):
+            return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        bolza = data is not None or Y is not None
+        head = (self.h, prog.h) + ((int(nu or 0),) if nu is not None or bolza else ())
+        args = (K, ptr(x), nt, float(T0), float(T1), _p(y0), _p(par) if par.size else None)
+        if bolza:
+            self._check(self.lib.mioc_ode_program_eval_bolza_device(*head, *args, ptr(data), ptr(J), ptr(df), ptr(Y)))
+        elif nu is not None:
+            self._check(self.lib.mioc_ode_program_eval_mixed_device(*head, *args, ptr(J), ptr(df)))
+        else:
+            self._check(self.lib.mioc_ode_program_eval_device(*head, *args, ptr(J), ptr(df)))
+
+    def ode_program_eval_tensors(self, prog, x, T0, T1, state0, params, J=None, df=None, data=None, Y=None):
         """eval_f! / eval_df! of a user-defined ODE objective (mioc.ode_device.ODEProgram) for K controls x
         (K, nt, nx) float64 CUDA tensor: J (K,) and df (K, nt, nx) float64 CUDA tensors (each optional); state0 (ny)
-        and params (nparams) host values; enqueued (mioc_ode_program_eval_device)."""
-        if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
-            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
-        K, nt, nx = x.shape
-        if nx != prog.nx:
-            raise ValueError(f"x has {nx} controls, the program {prog.nx}")
-        for name, t, n in (("J", J, K), ("df", df, x.numel())):
-            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or
-                                  t.numel() != n):
-                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries")
-        y0 = np.ascontiguousarray(state0, dtype=np.float64).reshape(-1)
-        par = np.ascontiguousarray(() if params is None else params, dtype=np.float64).reshape(-1)
-        if y0.size != prog.ny or par.size != prog.nparams:
-            raise ValueError(f"the program takes {prog.ny} initial states and {prog.nparams} parameters")
-        if not prog.h:
-            raise ValueError("the ODE program is closed")
-        self._check(self.lib.mioc_ode_program_eval_device(
-            self.h, prog.h, K, ctypes.c_void_p(x.data_ptr()), nt, float(T0), float(T1), _p(y0),
-            _p(par) if par.size else None,
-            ctypes.c_void_p(J.data_ptr()) if J is not None else None,
-            ctypes.c_void_p(df.data_ptr()) if df is not None else None))
+        and params (nparams) host values; enqueued (mioc_ode_program_eval_device).  data: the (nt, ndata) float64 CUDA
+        tensor of a program with sampled data; Y: a (K, nt + 1, ny) float64 CUDA tensor to receive the states at the
+        control-grid points (a program compiled with states=True); with either, mioc_ode_program_eval_bolza_device."""
+        self._ode_program_eval(prog, None, x, T0, T1, state0, params, J, df, data, Y)
 
     # ---- mixed controls: the continuous step beside the DP (include/mioc.h, "Mixed controls") -----------------
-    def ode_program_eval_mixed_tensors(self, prog, nu, x, T0, T1, state0, params, J=None, df=None):
+    def ode_program_eval_mixed_tensors(self, prog, nu, x, T0, T1, state0, params, J=None, df=None, data=None, Y=None):
         """ode_program_eval_tensors for a mixed control: the first nu of the program's nx controls are continuous, the
         levels describe the other nx - nu; x may hold the K*R candidates of a fan
-        (mioc_ode_program_eval_mixed_device)."""
-        if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
-            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
-        K, nt, nx = x.shape
-        if nx != prog.nx:
-            raise ValueError(f"x has {nx} controls, the program {prog.nx}")
-        if int(nu) != nu or not 1 <= nu < nx:
-            raise ValueError(f"nu must be an integer in 1..{nx - 1}, not {nu!r}")
-        for name, t, n in (("J", J, K), ("df", df, x.numel())):
-            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or
-                                  t.numel() != n):
-                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries")
-        y0 = np.ascontiguousarray(state0, dtype=np.float64).reshape(-1)
-        par = np.ascontiguousarray(() if params is None else params, dtype=np.float64).reshape(-1)
-        if y0.size != prog.ny or par.size != prog.nparams:
-            raise ValueError(f"the program takes {prog.ny} initial states and {prog.nparams} parameters")
-        if not prog.h:
-            raise ValueError("the ODE program is closed")
-        self._check(self.lib.mioc_ode_program_eval_mixed_device(
-            self.h, prog.h, int(nu), K, ctypes.c_void_p(x.data_ptr()), nt, float(T0), float(T1), _p(y0),
-            _p(par) if par.size else None,
-            ctypes.c_void_p(J.data_ptr()) if J is not None else None,
-            ctypes.c_void_p(df.data_ptr()) if df is not None else None))
+        (mioc_ode_program_eval_mixed_device; with data or Y mioc_ode_program_eval_bolza_device)."""
+        self._ode_program_eval(prog, nu, x, T0, T1, state0, params, J, df, data, Y)
 
     def rows_copy_tensors(self, dst, dst_row0, src, src_row0, nrows):
         """dst[:, :, dst_row0:dst_row0 + nrows] = src[:, :, src_row0:src_row0 + nrows] for float64 CUDA tensors

@@ -12,6 +12,10 @@ gradient by the implicit function theorem; a restart whose Newton iteration fail
 ``ODEProgram(..., derive="all" | ("Fy", "Gy", ...))`` takes F and G as templates over the scalar type and has the
 library generate the named derivative hooks by forward-mode AD (mioc_ode_program_create_ad; include/mioc.h, "Derived
 hooks"); ``check_hooks`` uses that to tell which hand-written derivative hook is wrong.
+``ODEProgram(..., ndata=n, terminal=True, states=True)`` (mioc_ode_program_create_bolza; include/mioc.h, "Terminal
+cost, sampled data, state output") adds n columns of sampled data behind the parameters (``p[NP + e]``, the row of the
+hook's control column), a terminal cost ``E`` with ``Ey`` (derivable: ``derive`` takes "Ey"), and the states at the
+control-grid points as an output (``DeviceODEProblem.states``).
 
 ``EXAMPLE_SOURCES`` restates the three built-in problems as hook text, term for term as ``Hooks<...>`` of
 csrc/mioc_ode.hip has them, so each reproduces mioc_ode_eval_device bit for bit; they double as templates.  Parameter
@@ -25,9 +29,9 @@ import ctypes
 import sys
 import weakref
 
-from .native import (MIOC_ECOMPILE, MIOC_ODE_DERIVE_FU, MIOC_ODE_DERIVE_FY, MIOC_ODE_DERIVE_GU, MIOC_ODE_DERIVE_GY,
-                     MIOC_ODE_INT_BEULER, MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_MIDPOINT,
-                     MIOC_ODE_INT_RK4, MIOC_OK, MiocNativeError, load_library)
+from .native import (MIOC_ECOMPILE, MIOC_ODE_DERIVE_EY, MIOC_ODE_DERIVE_FU, MIOC_ODE_DERIVE_FY, MIOC_ODE_DERIVE_GU,
+                     MIOC_ODE_DERIVE_GY, MIOC_ODE_INT_BEULER, MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_MIDPOINT,
+                     MIOC_ODE_INT_RK4, MIOC_ODE_STATES, MIOC_ODE_TERMINAL, MIOC_OK, MiocNativeError, load_library)
 
 
 class MiocCompileError(MiocNativeError):
@@ -55,20 +59,26 @@ def _close_live_programs():
 INTEGRATORS = {"euler": MIOC_ODE_INT_EULER, "heun": MIOC_ODE_INT_HEUN, "rk4": MIOC_ODE_INT_RK4,
                "beuler": MIOC_ODE_INT_BEULER, "midpoint": MIOC_ODE_INT_MIDPOINT}
 MAX_SUBSTEPS = 64
+MAX_NDATA = 16
 DERIVE_BITS = {"Fy": MIOC_ODE_DERIVE_FY, "Fu": MIOC_ODE_DERIVE_FU, "Gy": MIOC_ODE_DERIVE_GY, "Gu": MIOC_ODE_DERIVE_GU}
+DERIVE_BITS_TERMINAL = dict(DERIVE_BITS, Ey=MIOC_ODE_DERIVE_EY)  # with a terminal cost
 
 
-def derive_names(derive):
-    """``derive`` ("all" or an iterable of hook names) as a tuple of names in the order Fy, Fu, Gy, Gu."""
+def derive_names(derive, terminal=False):
+    """``derive`` ("all" or an iterable of hook names) as a tuple of names in the order Fy, Fu, Gy, Gu(, Ey: only a
+    program with a terminal cost has it, and "all" includes it there)."""
+    bits = DERIVE_BITS_TERMINAL if terminal else DERIVE_BITS
     if isinstance(derive, str):
         if derive != "all":
-            raise ValueError(f'derive must be "all" or an iterable of {list(DERIVE_BITS)}, not {derive!r}')
-        return tuple(DERIVE_BITS)
+            raise ValueError(f'derive must be "all" or an iterable of {list(bits)}, not {derive!r}')
+        return tuple(bits)
     names = set(derive)
-    unknown = sorted(str(n) for n in names if n not in DERIVE_BITS)
+    if "Ey" in names and not terminal:
+        raise ValueError('derive "Ey" needs terminal=True')
+    unknown = sorted(str(n) for n in names if n not in bits)
     if unknown:
-        raise ValueError(f"derive names must be among {list(DERIVE_BITS)}, not {unknown}")
-    return tuple(n for n in DERIVE_BITS if n in names)
+        raise ValueError(f"derive names must be among {list(bits)}, not {unknown}")
+    return tuple(n for n in bits if n in names)
 
 
 class ODEProgram:
@@ -82,13 +92,24 @@ class ODEProgram:
 
     ``derive``: "all" or an iterable of "Fy", "Fu", "Gy", "Gu" -- the hooks the library generates by forward-mode AD
     from F and G, which the text then defines as templates over the scalar type (include/mioc.h, "Derived hooks");
-    the text defines the others.  ``ODEProgram.derive`` is the tuple of names; empty: all six hooks are the text's."""
+    the text defines the others.  ``ODEProgram.derive`` is the tuple of names; empty: all six hooks are the text's.
+
+    ``ndata``: columns of sampled data (0..16); a hook then finds the data row of its control column in
+    ``p[NP] .. p[NP + ndata - 1]`` and every evaluation takes ``data``, an (nt, ndata) tensor.  ``terminal``: the text
+    also defines the terminal cost ``E(p, t, y)`` and ``Ey`` (or ``derive`` names "Ey"; "all" then includes it).
+    ``states``: evaluations can return the states at the control-grid points (``Y``).  All three: include/mioc.h,
+    "Terminal cost, sampled data, state output"; none asked for: the program is what it was without them."""
 
     LOG_CAP = 1 << 16
 
-    def __init__(self, source, ny, nx, nparams, integrator="euler", substeps=1, derive=()):
+    def __init__(self, source, ny, nx, nparams, integrator="euler", substeps=1, derive=(), ndata=0, terminal=False,
+                 states=False):
         self.h = None
-        self.derive = derive_names(derive)
+        self.terminal, self.states = bool(terminal), bool(states)
+        if int(ndata) != ndata or not 0 <= ndata <= MAX_NDATA:
+            raise ValueError(f"ndata must be an integer in 0..{MAX_NDATA}, not {ndata!r}")
+        self.ndata = int(ndata)
+        self.derive = derive_names(derive, self.terminal)
         if integrator not in INTEGRATORS:
             raise ValueError(f"integrator must be one of {sorted(INTEGRATORS)}, not {integrator!r}")
         if int(substeps) != substeps or not 1 <= substeps <= MAX_SUBSTEPS:
@@ -101,7 +122,13 @@ class ODEProgram:
         h = ctypes.c_void_p()
         log = ctypes.create_string_buffer(self.LOG_CAP)
         text = source.encode() if isinstance(source, str) else source
-        if self.derive:
+        if self.ndata or self.terminal or self.states:
+            mask = sum(DERIVE_BITS_TERMINAL[n] for n in self.derive)
+            flags = (MIOC_ODE_TERMINAL if self.terminal else 0) | (MIOC_ODE_STATES if self.states else 0)
+            rc = self.lib.mioc_ode_program_create_bolza(text, self.ny, self.nx, self.nparams, self.ndata,
+                                                        INTEGRATORS[integrator], self.substeps, mask, flags,
+                                                        ctypes.byref(h), log, self.LOG_CAP)
+        elif self.derive:
             mask = sum(DERIVE_BITS[n] for n in self.derive)
             rc = self.lib.mioc_ode_program_create_ad(text, self.ny, self.nx, self.nparams, INTEGRATORS[integrator],
                                                      self.substeps, mask, ctypes.byref(h), log, self.LOG_CAP)
@@ -116,7 +143,8 @@ class ODEProgram:
             raise MiocCompileError(rc, self.log)
         if rc != MIOC_OK:
             raise MiocNativeError(rc, self.log or "mioc_ode_program_create: bad ny / nx / nparams / source "
-                                                  "(1 <= ny, nx <= 8, 0 <= nparams <= 32, at most 1 MiB of text)")
+                                                  "(1 <= ny, nx <= 8, 0 <= nparams <= 32, 0 <= ndata <= 16, at most 1 MiB "
+                                                  "of text)")
         self.h = h
         _LIVE.add(self)
 
@@ -145,9 +173,10 @@ class ODEProgram:
 class DeviceODEProblem:
     """An ODE-constrained problem for TRM_batch: a compiled ``ODEProgram`` with the data the Julia objective holds --
     the levels V and their iterator (None: the product grid), [T0, T1], the default number of steps nt, state0 and
-    the parameters."""
+    the parameters; ``data``: the (nt, ndata) samples of a program with ndata > 0, which fix nt (uploaded once per
+    device and kept)."""
 
-    def __init__(self, program, V, iterator, T0, T1, nt, state0, params=()):
+    def __init__(self, program, V, iterator, T0, T1, nt, state0, params=(), data=None):
         self.program = program
         self.V = [list(v) for v in V]
         self.iterator = iterator
@@ -158,18 +187,27 @@ class DeviceODEProblem:
             raise ValueError("V, state0 and params must match the program's nx, ny and nparams")
         if not self.T1 > self.T0 or self.nt < 1:
             raise ValueError("need T1 > T0 and nt >= 1")
+        self.data = _problem_data(program, self.nt, data)
+        self._device_data = {}
 
     def eval_tensors(self, ctx, x, J=None, df=None):
-        ctx.ode_program_eval_tensors(self.program, x, self.T0, self.T1, self.state0, self.params, J, df)
+        ctx.ode_program_eval_tensors(self.program, x, self.T0, self.T1, self.state0, self.params, J, df,
+                                     data=_data_on(self, x))
+
+    def states(self, ctx, x):
+        """The states (K, nt + 1, ny) of the controls x (K, nt, nx) at the control-grid points t_i = T0 + i tau; row 0
+        is state0.  The program must have been compiled with states=True.  Synchronises the context."""
+        return _states(self, ctx, x, None)
 
 
 class MixedODEProblem:
     """An ODE-constrained problem with mixed controls for mioc.trm_mixed.TRM_mixed_batch: a compiled ``ODEProgram``
     whose first ``nu`` controls are continuous with the pointwise bounds ``lo`` <= ``hi`` (scalars, (nu,) or (nt, nu);
     kept as (nt, nu) numpy arrays, the device layout) and whose other nx - nu controls take the levels V with their
-    iterator (None: the product grid); then [T0, T1], the number of steps nt, state0 and the parameters."""
+    iterator (None: the product grid); then [T0, T1], the number of steps nt, state0, the parameters and ``data``, the
+    (nt, ndata) samples of a program with ndata > 0 (uploaded once per device and kept)."""
 
-    def __init__(self, program, nu, lo, hi, V, iterator, T0, T1, nt, state0, params=()):
+    def __init__(self, program, nu, lo, hi, V, iterator, T0, T1, nt, state0, params=(), data=None):
         import numpy as np
         self.program = program
         self.nu = int(nu)
@@ -195,9 +233,58 @@ class MixedODEProblem:
         self.lo, self.hi = bound(lo, "lo"), bound(hi, "hi")
         if not np.all(self.lo <= self.hi):  # also refuses a NaN bound
             raise ValueError("need lo <= hi everywhere")
+        self.data = _problem_data(program, self.nt, data)
+        self._device_data = {}
 
     def eval_tensors(self, ctx, x, J=None, df=None):
-        ctx.ode_program_eval_mixed_tensors(self.program, self.nu, x, self.T0, self.T1, self.state0, self.params, J, df)
+        ctx.ode_program_eval_mixed_tensors(self.program, self.nu, x, self.T0, self.T1, self.state0, self.params, J, df,
+                                           data=_data_on(self, x))
+
+    def states(self, ctx, x):
+        """DeviceODEProblem.states for a mixed control."""
+        return _states(self, ctx, x, self.nu)
+
+
+def _problem_data(program, nt, data):
+    """The (nt, ndata) float64 array of a problem's samples, None for a program without data."""
+    import numpy as np
+    nd = getattr(program, "ndata", 0)
+    if data is None:
+        if nd:
+            raise ValueError(f"the program reads {nd} columns of sampled data: give data of shape (nt, {nd})")
+        return None
+    data = np.array(data, dtype=np.float64, order="C", copy=True)
+    if nd == 0 or data.shape != (nt, nd):
+        raise ValueError(f"data must have the shape (nt, ndata) = ({nt}, {nd})")
+    return data
+
+
+def _data_on(problem, x):
+    """The problem's data on the device of x: uploaded at the first use there, then kept."""
+    if problem.data is None:
+        return None
+    if x.shape[1] != problem.nt:
+        raise ValueError(f"the problem's data fix nt = {problem.nt}; x has {x.shape[1]} steps")
+    key = str(x.device)
+    if key not in problem._device_data:
+        import torch
+        problem._device_data[key] = torch.tensor(problem.data, dtype=torch.float64, device=x.device)
+        torch.cuda.current_stream(x.device).synchronize()  # the upload before the context's stream reads it
+    return problem._device_data[key]
+
+
+def _states(problem, ctx, x, nu):
+    import torch
+    prog = problem.program
+    Y = torch.empty(x.shape[0], x.shape[1] + 1, prog.ny, dtype=torch.float64, device=x.device)
+    torch.cuda.current_stream(x.device).synchronize()
+    args = (x, problem.T0, problem.T1, problem.state0, problem.params)
+    if nu is None:
+        ctx.ode_program_eval_tensors(prog, *args, data=_data_on(problem, x), Y=Y)
+    else:
+        ctx.ode_program_eval_mixed_tensors(prog, nu, *args, data=_data_on(problem, x), Y=Y)
+    ctx.synchronize()
+    return Y
 
 
 _SIG = "(const double *p, int i, double t, const double *y, const double *x"
@@ -347,7 +434,8 @@ def example_program(name, integrator="euler", substeps=1, ad=False):
     return ODEProgram(EXAMPLE_SOURCES[name], *EXAMPLE_SHAPES[name], integrator=integrator, substeps=substeps)
 
 
-def check_hooks(ctx, source, ny, nx, nparams, x, T0, T1, state0, params, integrator="euler", substeps=1):
+def check_hooks(ctx, source, ny, nx, nparams, x, T0, T1, state0, params, integrator="euler", substeps=1, ndata=0,
+                terminal=False, data=None):
     """Which hand-written derivative hook is wrong?  The program-level counterpart of the reference's test_Fy! /
     test_Fu! (ODEObjective.jl:186-241), without finite differences.
 
@@ -359,15 +447,18 @@ def check_hooks(ctx, source, ny, nx, nparams, x, T0, T1, state0, params, integra
       "Fy", "Fu", "Gy", "Gu"   max|df(that hook derived) - df(all by hand)| / max|df(all derived)|: replacing a correct
                   hand-written hook by the derived one changes df by rounding only, a wrong one by its error;
       "all"       the same for all four derived against all by hand.
-    A wrong hook shows in its own entry and in "all" alone.  The programs are closed before returning."""
+    A wrong hook shows in its own entry and in "all" alone.  The programs are closed before returning.
+    ``terminal``: the text also defines E as a template and Ey by hand under ``#ifndef MIOC_DERIVE_EY``; there is one
+    more program and the key "Ey".  ``ndata``, ``data``: the (nt, ndata) float64 CUDA tensor of a text with data."""
     import torch
-    masks = [("hand", ()), ("all", "all")] + [(n, (n,)) for n in DERIVE_BITS]
+    masks = [("hand", ()), ("all", "all")] + [(n, (n,)) for n in (DERIVE_BITS_TERMINAL if terminal else DERIVE_BITS)]
     res = {}
     for key, derive in masks:
-        with ODEProgram(source, ny, nx, nparams, integrator=integrator, substeps=substeps, derive=derive) as prog:
+        with ODEProgram(source, ny, nx, nparams, integrator=integrator, substeps=substeps, derive=derive, ndata=ndata,
+                        terminal=terminal) as prog:
             J = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
             df = torch.empty_like(x)
-            ctx.ode_program_eval_tensors(prog, x, T0, T1, state0, params, J, df)
+            ctx.ode_program_eval_tensors(prog, x, T0, T1, state0, params, J, df, data=data)
             ctx.synchronize()
             res[key] = (J, df)
     J0, df0 = res["hand"]

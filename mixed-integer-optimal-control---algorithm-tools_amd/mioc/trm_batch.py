@@ -80,6 +80,8 @@ def TRM_batch(problem, par, K=None, x0=None, seed=0, nt=None, device=0, log=None
     elif isinstance(problem, DeviceODEProblem):  # a user-defined ODE objective (mioc_ode_program_eval_device)
         dp = problem
         nt_def, T0, T1 = dp.nt, dp.T0, dp.T1
+        if dp.data is not None and nt is not None and int(nt) != dp.nt:
+            raise ValueError("the problem's sampled data fix nt")
         lt = LevelTable(dp.V, dp.iterator)
 
         def evalf(x, J, df):
