@@ -205,11 +205,6 @@ int32_t mioc_pred_batch_device(mioc_ctx *ctx, double *d_int_val, double *d_tv_ol
 int32_t mioc_tv_device(mioc_ctx *ctx, int64_t K, const double *d_u, int64_t nx, int64_t nt, double *d_tv);
 
 /*
- * The trust-region step decision of multi-trust.jl:127-158 per subproblem, on the device:
- *   ared = J_old − J_new + β·(tv_old − tv_new);   decision = 2 if pred <= 0 (stop: optimal),
- *   1 if ared < σ·pred (bad step: halve Δ), else 0 (good step: accept).  d_ared nullable; enqueued.
- */
-/*
  * Device-resident TRM control (multi-trust.jl:92-163) for K restarts, so that the host reads back one flag per
  * inner-loop chunk instead of K decisions plus stream syncs per inner iteration:
  *   mioc_trm_state_bytes(K): bytes of the zero-initialised state block the caller allocates on the device
@@ -217,7 +212,9 @@ int32_t mioc_tv_device(mioc_ctx *ctx, int64_t K, const double *d_u, int64_t nx, 
  *     K int32 flags (1 inner, 2 halved, 4 stopped), K int32 outer iterations per restart).
  *   mioc_trm_attach(ctx, d_state): while the gate word is 0, the kernels of mioc_backtrack_batch*_device,
  *     mioc_pred_batch_device, mioc_ode_eval_device, mioc_ode_program_eval_device (and _eval_mixed_device),
- *     mioc_rows_copy_device, mioc_heat_eval_device and mioc_conv_eval_device return at once;
+ *     mioc_rows_copy_device, mioc_heat_eval_device and mioc_conv_eval_device return at once; so does the kernel of
+ *     mioc_tv_device and of the host mioc_pred, which then leave their outputs as they were (mioc_pred returns the
+ *     stale words of its staging buffer): detach around a TV_p or a pred that must run whatever the gate says;
  *     NULL detaches.
  *   mioc_trm_outer_begin_device: multi-trust.jl:99-107 (TV_old = TV_p(u), Δᵏ = Δ⁰, k = 1, budgets = B, every
  *     restart not stopped enters its inner loop; the gate opens if any did).
@@ -238,6 +235,11 @@ int32_t mioc_trm_inner_end_device(mioc_ctx *ctx, int64_t K, void *d_state, doubl
                                   double *d_u_old);
 int32_t mioc_trm_poll(mioc_ctx *ctx, const void *d_state, int32_t *out);
 
+/*
+ * The trust-region step decision of multi-trust.jl:127-158 per subproblem, on the device:
+ *   ared = J_old − J_new + β·(tv_old − tv_new);   decision = 2 if pred <= 0 (stop: optimal),
+ *   1 if ared < σ·pred (bad step: halve Δ), else 0 (good step: accept).  d_ared nullable; enqueued.
+ */
 int32_t mioc_trm_decide_device(mioc_ctx *ctx, int64_t K, const double *d_J_old, const double *d_J_new,
                                const double *d_tv_old, const double *d_tv_new, const double *d_pred, double sigma,
                                double *d_ared, int32_t *d_decision);
