@@ -135,6 +135,11 @@ int32_t mioc_set_cost(mioc_ctx *ctx, int32_t p_kind, int64_t p_int, double beta,
  *   the others                 B <= 2^20, as far as device memory holds the tables.
  * MIOC_ALGO_AUTO takes another algorithm beyond such a limit; a forced algorithm returns MIOC_EINVAL.
  *
+ * u_old: integral entries with |u_old| < 4e15 (else MIOC_EINEXACT).  A step whose u_old is further than B from every
+ * level makes every cell +Inf, as in the reference: the call returns MIOC_OK and the backtrack reports
+ * MIOC_EINFEASIBLE for that subproblem alone.  The context keeps its copy of u_old clamped, per component, to within
+ * 1e8 of the level range; mioc_pred*'s tv_old of such a (necessarily infeasible) subproblem is that of the clamped copy.
+ *
  * What a failed call leaves behind (mioc_bellman, mioc_bellman_batch_device and mioc_batch_multi alike):
  *   - A call rejected for its arguments (MIOC_EINVAL for nx, K, nt, B or dt, or a NULL pointer) changes nothing:
  *     the previous DP, its inputs and its last backtrack stay valid, and mioc_backtrack*, mioc_pred* and

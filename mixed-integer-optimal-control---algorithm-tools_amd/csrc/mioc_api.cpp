@@ -220,7 +220,8 @@ int pinf_prepare_flags(mioc_ctx *ctx) {
   return MIOC_OK;
 }
 
-// validation pass: finite df, integral u_old, max budget class
+// validation pass: finite df, integral u_old, max budget class; the context's copy of u_old is clamped to within 1e8
+// of the level range (k_validate), so that no kernel's budget class can leave int
 int validate_inputs(mioc_ctx *ctx, int *bmax) {
   // fills queued before the host sync below, so that they overlap the previous call's device work: the DP counters,
   // and (p = Inf, the likely algorithm) the segmented recursion's flags
@@ -230,7 +231,8 @@ int validate_inputs(mioc_ctx *ctx, int *bmax) {
   if (ctx->p_kind == MIOC_P_INF && !ctx->force_steps && (rc = pinf_prepare_flags(ctx))) return rc;
   // (words 0, 1 only: 2, 3 are a backtrack's, which may still run on the other stream)
   HIP_TRY(ctx, hipMemsetAsync(ctx->d_flags.get(), 0, 2 * sizeof(int32_t), ctx->stream));
-  HIP_TRY(ctx, launch_validate(ctx->stream, problem_dev(ctx), ctx->d_numin.get(), ctx->d_numax.get(), ctx->d_flags.get()));
+  HIP_TRY(ctx, launch_validate(ctx->stream, problem_dev(ctx), ctx->cur().uold.get(), ctx->d_numin.get(), ctx->d_numax.get(),
+                               ctx->d_flags.get()));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_flags.get(), ctx->d_flags.get(), 2 * sizeof(int32_t), hipMemcpyDeviceToHost,
                               ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -83,7 +83,7 @@ __device__ __forceinline__ double fu_t1(const LevelsDev &Lv, int l, const double
   return t;
 }
 __device__ __forceinline__ int fu_bt(const LevelsDev &Lv, int l, const double *uo) {
-  int b = 0;  // saturated: far off-grid u_old entries only ever mean "beyond every budget"
+  int b = 0;  // (k_validate has clamped u_old to within 1e8 of the level range; the fmin is a second bound)
   for (int m = 0; m < Lv.M; ++m) b += (int)fmin(fabs(Lv.nuval[l * Lv.M + m] - uo[m]), 1.0e8);
   return b;
 }
@@ -136,7 +136,7 @@ __device__ __forceinline__ void fu_prepare(const ProblemDev &P, const LevelsDev 
     const int lane = tid;
     int b = 1 << 29;
     if (lane < L) {
-      b = 0;  // saturated: far off-grid u_old entries only ever mean "beyond every budget"
+      b = 0;  // (as fu_bt)
       for (int m = 0; m < M; ++m) b += (int)fmin(fabs(nul[lane * M + m] - uo[m]), 1.0e8);
     }
     if (lane < LP) btb[buf * LP + lane] = b;

@@ -31,7 +31,7 @@ __device__ __forceinline__ double t1_of(const double *nuv, const double *dfi, in
 }
 
 __device__ __forceinline__ int bt_of(const double *nuv, const double *uoi, int M) {
-  int b = 0;
+  int b = 0;  // (u_old is k_validate's clamped copy: the sum stays in int)
   for (int m = 0; m < M; ++m) b += (int)fabs(nuv[m] - uoi[m]);
   return b;
 }
@@ -69,15 +69,20 @@ __device__ __forceinline__ uint64_t jl_key(double v) {
 // ---------------------------------------------------------------------------------------------
 // input validation: finite df, integral u_old (the reference's InexactError), max budget class
 // flags[0] |= 1 non-finite df, |= 2 non-integral u_old;  flags[1] = max_i max_l b̃(l, i) (capped)
+//
+// uold_own is the context's own copy of u_old (P.uold, writable): every component is clamped to
+// [numin_m - 1e8, numax_m + 1e8] here, once.  A clamped component is further than any budget (B <= 2^20) from every
+// level before and after the clamp, so the DP is the reference's (every cell of that step +Inf), and every kernel
+// after this one may take b̃ = Σ_m (int)|ν_m - u_old_m| in int: at most kMaxM·(1e8 + 2^25) < 2^31.
 // ---------------------------------------------------------------------------------------------
-__global__ void k_validate(ProblemDev P, const double *__restrict__ numin, const double *__restrict__ numax,
-                           int32_t *flags) {
+__global__ void k_validate(ProblemDev P, double *__restrict__ uold_own, const double *__restrict__ numin,
+                           const double *__restrict__ numax, int32_t *flags) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int k = blockIdx.y;
   int bad = 0, bm = 0;
   if (i < P.nt) {
     const double *dfi = P.df + ((size_t)k * P.nt + i) * P.M;
-    const double *uoi = P.uold + ((size_t)k * P.nt + i) * P.M;
+    double *uoi = uold_own + ((size_t)k * P.nt + i) * P.M;
     long long bmax = 0;
     for (int m = 0; m < P.M; ++m) {
       double d = dfi[m];
@@ -86,6 +91,8 @@ __global__ void k_validate(ProblemDev P, const double *__restrict__ numin, const
       if (!(u == floor(u)) || !(fabs(u) < 4.0e15)) bad |= 2;
       double e = fmax(fabs(numax[m] - u), fabs(numin[m] - u));
       bmax += (e > 1.0e9 || e != e) ? 1000000000LL : (long long)e;
+      const double uc = fmin(fmax(u, numin[m] - 1.0e8), numax[m] + 1.0e8);
+      if (uc != u) uoi[m] = uc;  // (this thread alone reads and writes step i of subproblem k)
     }
     bm = bmax > (long long)P.B ? P.B : (int)bmax;
   }
@@ -102,10 +109,10 @@ __global__ void k_validate(ProblemDev P, const double *__restrict__ numin, const
   }
 }
 
-hipError_t launch_validate(hipStream_t s, const ProblemDev &P, const double *numin, const double *numax,
-                           int32_t *flags) {
+hipError_t launch_validate(hipStream_t s, const ProblemDev &P, double *uold_own, const double *numin,
+                           const double *numax, int32_t *flags) {
   dim3 grid((P.nt + 255) / 256, P.K);
-  hipLaunchKernelGGL(k_validate, grid, dim3(256), 0, s, P, numin, numax, flags);
+  hipLaunchKernelGGL(k_validate, grid, dim3(256), 0, s, P, uold_own, numin, numax, flags);
   return hipGetLastError();
 }
 

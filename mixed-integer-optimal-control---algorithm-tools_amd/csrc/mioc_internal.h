@@ -158,8 +158,8 @@ __device__ __forceinline__ int start_budget(const ProblemDev &P, int k, int Bu, 
 }
 
 // ---- kernel launchers (mioc_generic.hip) ------------------------------------------------------
-hipError_t launch_validate(hipStream_t s, const ProblemDev &P, const double *numin, const double *numax,
-                           int32_t *flags);
+hipError_t launch_validate(hipStream_t s, const ProblemDev &P, double *uold_own, const double *numin,
+                           const double *numax, int32_t *flags);
 hipError_t launch_generic_terminal(hipStream_t s, const ProblemDev &P, const LevelsDev &Lv, double *front,
                                    size_t front_stride);
 hipError_t launch_generic_step(hipStream_t s, const ProblemDev &P, const LevelsDev &Lv, int i,

@@ -15,7 +15,7 @@ from conftest import golden_files, load_golden
 from mioc import native
 from mioc.iterators import LevelTable
 from mioc.synth import CONFIGS, make_inputs
-from oracle.oracle import P_INF, P_INTLUT, P_ONE, Levels
+from oracle.oracle import P_INF, P_INTLUT, P_ONE, Levels, OracleError
 
 pytestmark = pytest.mark.gpu
 
@@ -469,6 +469,60 @@ def test_error_codes():
     with pytest.raises(native.MiocNativeError) as e:
         ctx.bellman(np.ones((2, 4)), np.zeros((2, 4)), 3, 0.1)
     assert e.value.code == native.MIOC_EINVAL
+    ctx.close()
+
+
+_FAR_ALGOS = [("generic", 1), ("pyramid", 1), ("fused", 1), ("fused_separable", 1), ("pinf", math.inf),
+              ("generic", math.inf)]
+
+
+@pytest.mark.parametrize("F", [2.0 ** 31, 3.0e9, 2.0 ** 40], ids=["2^31", "3e9", "2^40"])
+@pytest.mark.parametrize("algo,p", _FAR_ALGOS, ids=[f"{a}-p{p}" for a, p in _FAR_ALGOS])
+def test_far_off_grid_u_old_is_infeasible_not_fatal(oracle_c, algo, p, F):
+    """An integral u_old far off the level grid (mioc_bellman accepts |u_old| < 4e15, as the reference's Int64 class
+    does): one step of restart 0 has u_old = (F, -F), whose distances to the levels do not fit an int and whose sum
+    would wrap.  The contract is the reference's: every cell of that restart is +Inf, bellman succeeds, the backtrack
+    reports MIOC_EINFEASIBLE for it and leaves its u row NaN; restart 1 (on the grid) is untouched: u, Phi* and every
+    U cell equal the oracle's run of restart 1 alone."""
+    import torch
+    aid = {"generic": native.MIOC_ALGO_GENERIC, "pyramid": native.MIOC_ALGO_PYRAMID, "fused": native.MIOC_ALGO_FUSED,
+           "fused_separable": native.MIOC_ALGO_FUSED_SEPARABLE, "pinf": native.MIOC_ALGO_PINF}[algo]
+    pk = P_INF if p == math.inf else P_ONE
+    lv = Levels.product([list(range(4))] * 2)
+    lt = LevelTable(lv.nu, [tuple(t) for t in lv.tuples])
+    K, nt, B, beta, dt = 2, 8, 10, 1e-3, 2.0 ** -6
+    rng = np.random.default_rng(2031)
+    dfs = [rng.standard_normal((2, nt)) for _ in range(K)]
+    uos = [np.array([lv.nuval[rng.integers(lv.L)] for _ in range(nt)], dtype=np.float64).T.copy() for _ in range(K)]
+    uos[0][:, 3] = (F, -F)
+    phi0, U0 = oracle_c.bellman(lv, dfs[0], uos[0], B, pk, beta, dt)  # the reference's restart 0: no finite cell
+    assert np.all(np.isinf(phi0[:, :, 0]))
+    with pytest.raises(OracleError):
+        oracle_c.backtrack(lv, uos[0], phi0, U0, B, B)
+    phi, U = oracle_c.bellman(lv, dfs[1], uos[1], B, pk, beta, dt)
+    ou, ops = oracle_c.backtrack(lv, uos[1], phi, U, B, B)
+    ddf = torch.tensor(np.ascontiguousarray(np.stack([d.T for d in dfs])), dtype=torch.float64, device="cuda")
+    duo = torch.tensor(np.ascontiguousarray(np.stack([d.T for d in uos])), dtype=torch.float64, device="cuda")
+    du = torch.zeros_like(ddf)
+    dphi = torch.empty(K, dtype=torch.float64, device="cuda")
+    dst = torch.empty(K, dtype=torch.int32, device="cuda")
+    ctx = _ctx(lt, pk, beta, aid)
+    torch.cuda.synchronize()
+    ctx.bellman_batch_tensors(ddf, duo, B, dt)
+    assert ctx.last_algo() == aid
+    ctx.backtrack_batch_tensors(B, du, dphi, dst)
+    ctx.synchronize()
+    assert np.array_equal(duo.cpu().numpy(), np.stack([d.T for d in uos]))  # the caller's u_old is not written to
+    ub = du.cpu().numpy()
+    assert dst.cpu().tolist() == [native.MIOC_EINFEASIBLE, native.MIOC_OK]
+    assert np.all(np.isnan(ub[0]))
+    assert np.array_equal(ub[1].T, ou) and dphi[1].item() == ops
+    assert ctx.diagnostics()[3] == 0
+    if aid != native.MIOC_ALGO_PINF:
+        for i in range(nt - 1):
+            d, o = ctx.argmin_table(i, k=1), U[:, :, i]
+            m = o >= 0
+            assert np.array_equal(d[m], o[m]), f"step {i}"
     ctx.close()
 
 
