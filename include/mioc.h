@@ -412,7 +412,9 @@ int32_t mioc_ode_eval_device(mioc_ctx *ctx, int32_t problem, int64_t K, const do
  * with a Dual: both return MIOC_ECOMPILE with the compiler's message in the log.  The assembled text is the head with
  * the MIOC_DERIVE_* macros, the dual type under `#line 1 "mioc_ad"`, the caller's text under `#line 1 "hooks"` (its
  * diagnostics keep its own line numbers; the 1 MiB limit is the caller's text alone), the generated hooks under
- * `#line 1 "mioc_ad_hooks"`, the skeleton.  The namespace mioc_ad exists only with derive != 0.
+ * `#line 1 "mioc_ad_hooks"`, the skeleton under `#line 1 "mioc_ode_program_skeleton"` (what all integrators share,
+ * then the integrator's kernel).  The namespace mioc_ad exists only with derive != 0.  mioc_ode_program_source returns
+ * this text.
  *   A generated hook is inlined at each of its call sites like a hand-written one (Heun / RK4: one per stage).  If
  *   the kernel then needs more than the 256 architectural VGPRs (the compiler reports AGPRs in use or vector spills),
  *   the text is compiled a second time with the generated hooks as functions that are called (the head then also
@@ -539,6 +541,14 @@ int32_t mioc_ode_program_create_ad(const char *hooks, int32_t ny, int32_t nx, in
 int32_t mioc_ode_program_create_bolza(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
                                       int32_t integrator, int32_t substeps, int32_t derive, int32_t flags,
                                       mioc_ode_program **out, char *log, int64_t log_cap);
+/* The text _create_bolza would hand to the compiler for these arguments (its order: "Derived hooks" above), copied
+ * into `text`, NUL-terminated and truncated to text_cap bytes like a log (text nullable).  noinline != 0: the text of
+ * the second compile, with MIOC_AD_NOINLINE in the head.  Returns the text's length without the NUL (a buffer of that
+ * plus one holds all of it), or MIOC_EINVAL exactly where _create_bolza returns it for these arguments.  Needs neither
+ * hiprtc nor a GPU. */
+int64_t mioc_ode_program_source(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
+                                int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t noinline,
+                                char *text, int64_t text_cap);
 int32_t mioc_ode_program_destroy(mioc_ode_program *prog);
 int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t K, const double *d_x, int64_t nt,
                                      double T0, double T1, const double *state0, const double *params, double *d_J,

@@ -56,7 +56,7 @@ EXPORTED = [
     "mioc_trm_poll",
     "mioc_ode_program_create", "mioc_ode_program_destroy", "mioc_ode_program_eval_device",
     "mioc_ode_program_create_ex", "mioc_ode_program_create_ad",
-    "mioc_ode_program_create_bolza", "mioc_ode_program_eval_bolza_device",
+    "mioc_ode_program_create_bolza", "mioc_ode_program_source", "mioc_ode_program_eval_bolza_device",
     "mioc_ode_program_eval_mixed_device", "mioc_rows_copy_device", "mioc_mixed_state_bytes", "mioc_mixed_fan_device",
     "mioc_mixed_select_device", "mioc_mixed_poll",
 ]
@@ -150,6 +150,8 @@ def load_library(path=None):
                                              ctypes.c_char_p, i64]),
         "mioc_ode_program_create_bolza": (i32, [ctypes.c_char_p, i32, i32, i32, i32, i32, i32, i32, i32,
                                                 ctypes.POINTER(vp), ctypes.c_char_p, i64]),
+        "mioc_ode_program_source": (i64, [ctypes.c_char_p, i32, i32, i32, i32, i32, i32, i32, i32, i32, ctypes.c_char_p,
+                                          i64]),
         "mioc_ode_program_destroy": (i32, [vp]),
         "mioc_ode_program_eval_bolza_device": (i32, [vp, vp, i64, i64, vp, i64, dbl, dbl, vp, vp, vp, vp, vp, vp]),
         "mioc_ode_program_eval_device": (i32, [vp, vp, i64, vp, i64, dbl, dbl, vp, vp, vp, vp]),

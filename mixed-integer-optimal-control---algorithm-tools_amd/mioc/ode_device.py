@@ -81,6 +81,24 @@ def derive_names(derive, terminal=False):
     return tuple(n for n in bits if n in names)
 
 
+def program_source(source, ny, nx, nparams, integrator="euler", substeps=1, derive=(), ndata=0, terminal=False,
+                   states=False, noinline=False):
+    """The text the library hands to the compiler for ``ODEProgram(source, ny, ...)`` (mioc_ode_program_source), as a
+    str; nothing is compiled.  noinline: the text of the second compile of derived hooks (include/mioc.h)."""
+    lib = load_library()
+    text = source.encode() if isinstance(source, str) else source
+    mask = sum(DERIVE_BITS_TERMINAL[n] for n in derive_names(derive, terminal))
+    flags = (MIOC_ODE_TERMINAL if terminal else 0) | (MIOC_ODE_STATES if states else 0)
+    args = (text, int(ny), int(nx), int(nparams), int(ndata), INTEGRATORS[integrator], int(substeps), mask, flags,
+            int(bool(noinline)))
+    need = lib.mioc_ode_program_source(*args, None, 0)
+    if need < 0:
+        raise MiocNativeError(need, "mioc_ode_program_source: bad arguments")
+    buf = ctypes.create_string_buffer(need + 1)
+    lib.mioc_ode_program_source(*args, buf, need + 1)
+    return buf.value.decode()
+
+
 class ODEProgram:
     """Six hooks (HIP source text) compiled for gfx950: ny states, nx controls, nparams parameters.  Needs no GPU to
     compile; one program serves any number of contexts.  ``close()`` destroys it (also ``with ODEProgram(...) as p``).
@@ -146,7 +164,13 @@ class ODEProgram:
                                                   "(1 <= ny, nx <= 8, 0 <= nparams <= 32, 0 <= ndata <= 16, at most 1 MiB "
                                                   "of text)")
         self.h = h
+        self._source = text
         _LIVE.add(self)
+
+    def source_text(self, noinline=False):
+        """The text this program was compiled from (mioc_ode_program_source); noinline: that of the second compile."""
+        return program_source(self._source, self.ny, self.nx, self.nparams, self.integrator, self.substeps,
+                              self.derive, self.ndata, self.terminal, self.states, noinline)
 
     def close(self):
         if self.h:

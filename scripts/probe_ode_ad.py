@@ -11,9 +11,9 @@ the medians.  Also the wall time of mioc_ode_program_create_ad against mioc_ode_
 the process loads hiprtc and is reported apart), and whether J is bit-identical and how far df deviates.  One
 integrator per process: run it once each for euler, rk4 and midpoint.
 
-`resources` assembles the same source text as the library does (head, dual type, text, generated hooks, skeleton: the
-strings of csrc/mioc_ode_rtc.cpp) and compiles it offline with the library's flags and
--Rpass-analysis=kernel-resource-usage, for euler, rk4 and midpoint.
+`resources` takes the source text the library assembles (head, dual type, text, generated hooks, skeleton:
+mioc_ode_program_source) and compiles it offline with the library's flags and -Rpass-analysis=kernel-resource-usage,
+for euler, rk4 and midpoint.
 """
 import os
 import re
@@ -28,28 +28,7 @@ PKG = os.path.join(ROOT, "mixed-integer-optimal-control---algorithm-tools_amd")
 sys.path[:0] = [PKG, ROOT]
 
 from mioc.ode_device import (EXAMPLE_PARAMS, EXAMPLE_SHAPES, EXAMPLE_SOURCES, EXAMPLE_SOURCES_AD,  # noqa: E402
-                             EXAMPLE_STATE0, INTEGRATORS, ODEProgram)
-
-HEADS = {"euler": "", "heun": "#define NS 2\n", "rk4": "#define NS 4\n", "beuler": "#define TH 1.0\n",
-         "midpoint": "#define TH 0.5\n"}
-SKELETONS = {"euler": "kSkeleton", "heun": "kSkeletonRK", "rk4": "kSkeletonRK", "beuler": "kSkeletonTheta",
-             "midpoint": "kSkeletonTheta"}
-
-
-def assembled_source(text, ny, nx, nparams, integrator, derive):
-    """The text mioc_ode_program_create_ad hands to the compiler (derive: all four hooks or none)."""
-    cpp = open(os.path.join(PKG, "csrc", "mioc_ode_rtc.cpp")).read()
-
-    def raw(name):
-        return re.search(r"const char \*const " + name + r' = R"SKEL\((.*?)\)SKEL";', cpp, re.S).group(1)
-    src = f"#define NY {ny}\n#define NX {nx}\n#define NP {nparams}\n" + HEADS[integrator]
-    if derive:
-        src += "".join(f"#define MIOC_DERIVE_{n} 1\n" for n in ("FY", "FU", "GY", "GU"))
-        src += '#line 1 "mioc_ad"' + raw("kAdPrelude")
-    src += '#line 1 "hooks"\n' + text
-    if derive:
-        src += '\n#line 1 "mioc_ad_hooks"' + raw("kAdHooks")
-    return src + '\n#line 1 "mioc_ode_program_skeleton"' + raw(SKELETONS[integrator])
+                             EXAMPLE_STATE0, INTEGRATORS, ODEProgram, program_source)
 
 
 def resources(out):
@@ -57,12 +36,12 @@ def resources(out):
     lines = ["probe_ode_ad resources: fishing (ny, nx) = (2, 3), the assembled source compiled offline for gfx950 "
              "(-O3 -ffp-contract=off -fno-fast-math)"]
     for integrator in ("euler", "rk4", "midpoint"):
-        for label, text, derive in (("hand", EXAMPLE_SOURCES["fishing"], False),
-                                    ("AD  ", EXAMPLE_SOURCES_AD["fishing"], True)):
+        for label, text, derive in (("hand", EXAMPLE_SOURCES["fishing"], ()),
+                                    ("AD  ", EXAMPLE_SOURCES_AD["fishing"], "all")):
             with tempfile.TemporaryDirectory() as d:
                 path = os.path.join(d, "prog.hip")
                 with open(path, "w") as f:
-                    f.write(assembled_source(text, *EXAMPLE_SHAPES["fishing"], integrator, derive))
+                    f.write(program_source(text, *EXAMPLE_SHAPES["fishing"], integrator, derive=derive))
                 r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math",
                                     "--cuda-device-only", "-include", "hip/hip_runtime.h",
                                     "-Rpass-analysis=kernel-resource-usage", "-c", path, "-o",

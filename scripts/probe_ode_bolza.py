@@ -12,7 +12,7 @@ Per call with J and df and per value-only call, by HIP events on the library's s
 alternating between all the calls, REP launches per round after a warm-up; medians with the min-max spread over the
 rounds and the ratio to the plain program of the same integrator.
 
-`resources` assembles the source text as the library does (the strings of csrc/mioc_ode_rtc.cpp) for the problem of
+`resources` takes the source text the library assembles (mioc_ode_program_source) for the problem of
 tests/ode_bolza_problem.py (ny = 3, nx = 2, NP = 3, ND = 2, terminal cost, state output), hand-written and derived
 hooks, and compiles it offline with the library's flags and -Rpass-analysis=kernel-resource-usage for each of the five
 integrators; and the fishing text with and without ND = 2, to show what the per-lane parameter copy costs a
@@ -29,12 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "mixed-integer-optimal-control---algorithm-tools_amd")
 sys.path[:0] = [PKG, ROOT]
 
-from mioc.ode_device import EXAMPLE_PARAMS, EXAMPLE_SHAPES, EXAMPLE_SOURCES, EXAMPLE_STATE0, ODEProgram  # noqa: E402
-
-HEADS = {"euler": "", "heun": "#define NS 2\n", "rk4": "#define NS 4\n", "beuler": "#define TH 1.0\n",
-         "midpoint": "#define TH 0.5\n"}
-SKELETONS = {"euler": "kSkeleton", "heun": "kSkeletonRK", "rk4": "kSkeletonRK", "beuler": "kSkeletonTheta",
-             "midpoint": "kSkeletonTheta"}
+from mioc.ode_device import (EXAMPLE_PARAMS, EXAMPLE_SHAPES, EXAMPLE_SOURCES, EXAMPLE_STATE0, ODEProgram,  # noqa: E402
+                             program_source)
 
 FISH = EXAMPLE_SOURCES["fishing"]
 FISH_TERMINAL = FISH + """
@@ -49,27 +45,6 @@ __device__ void Ey(const double *p, double t, const double *y, double *ey) {
 """
 FISH_DATA = FISH.replace("y[0] - 1.0", "y[0] - p[NP]").replace("y[1] - 1.0", "y[1] - p[NP + 1]")
 assert FISH_DATA.count("p[NP") == 4
-
-
-def assembled_source(text, ny, nx, nparams, integrator, derive, ndata, terminal, states):
-    """The text mioc_ode_program_create_bolza hands to the compiler (derive: every derivative hook or none)."""
-    cpp = open(os.path.join(PKG, "csrc", "mioc_ode_rtc.cpp")).read()
-
-    def raw(name):
-        return re.search(r"const char \*const " + name + r' = R"SKEL\((.*?)\)SKEL";', cpp, re.S).group(1)
-    src = f"#define NY {ny}\n#define NX {nx}\n#define NP {nparams}\n" + HEADS[integrator]
-    src += (f"#define ND {ndata}\n" if ndata else "") + ("#define MIOC_TERMINAL 1\n" if terminal else "")
-    src += "#define MIOC_STATES 1\n" if states else ""
-    if derive:
-        src += "".join(f"#define MIOC_DERIVE_{n} 1\n" for n in ("FY", "FU", "GY", "GU") + (("EY",) if terminal else ()))
-        src += '#line 1 "mioc_ad"' + raw("kAdPrelude")
-    src += '#line 1 "hooks"\n' + text
-    if terminal:
-        src += ("\n__device__ inline double mioc_terminal_needs_E(const double *p, double t, const double *y) "
-                "{ return E(p, t, y); }")
-    if derive:
-        src += '\n#line 1 "mioc_ad_hooks"' + raw("kAdHooks")
-    return src + '\n#line 1 "mioc_ode_program_skeleton"' + raw(SKELETONS[integrator])
 
 
 def resources(out):
@@ -90,7 +65,8 @@ def resources(out):
             with tempfile.TemporaryDirectory() as d:
                 path = os.path.join(d, "prog.hip")
                 with open(path, "w") as f:
-                    f.write(assembled_source(text, *shape, integrator, derive, ndata, terminal, states))
+                    f.write(program_source(text, *shape, integrator, derive="all" if derive else (), ndata=ndata,
+                                           terminal=terminal, states=states))
                 r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math",
                                     "--cuda-device-only", "-include", "hip/hip_runtime.h",
                                     "-Rpass-analysis=kernel-resource-usage", "-c", path, "-o",

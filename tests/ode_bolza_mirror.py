@@ -43,7 +43,7 @@ def _div(a, b):
 
 
 def euler_eval(hooks, p, data, state0, T0, T1, x, want_df=True):
-    """The reference's explicit Euler / trapezoid scheme (kSkeleton)."""
+    """The reference's explicit Euler / trapezoid scheme (kBodyEuler of csrc/mioc_ode_skeleton.h)."""
     x = [[float(v) for v in row] for row in x]
     nt, nx, ny = len(x), len(x[0]), len(state0)
     tau = (T1 - T0) / nt
@@ -109,7 +109,7 @@ def euler_eval(hooks, p, data, state0, T0, T1, x, want_df=True):
 
 
 def rk_eval(hooks, p, data, state0, T0, T1, x, integrator, substeps, want_df=True):
-    """Heun / classical RK4 with substeps (kSkeletonRK)."""
+    """Heun / classical RK4 with substeps (kBodyRK)."""
     c, a, b = TABLEAUX[integrator]
     S, ms = len(c), int(substeps)
     x = [[float(v) for v in row] for row in x]
@@ -225,7 +225,7 @@ def solve(A, b):
 
 
 def theta_eval(hooks, p, data, state0, T0, T1, x, integrator, substeps, want_df=True):
-    """Backward Euler / implicit midpoint with substeps (kSkeletonTheta); a failed Newton iteration gives NaN."""
+    """Backward Euler / implicit midpoint with substeps (kBodyTheta); a failed Newton iteration gives NaN."""
     theta, ms = THETA[integrator], int(substeps)
     x = [[float(v) for v in row] for row in x]
     nt, nx, ny = len(x), len(x[0]), len(state0)

@@ -14,6 +14,7 @@ from mioc.ode_device import MixedODEProblem, ODEProgram
 from mioc.trm_mixed import MixedParameters, MixedState, TRM_mixed, TRM_mixed_batch, fan_host, select_host
 
 import ode_mixed_problem as mixed
+from ode_gpu_support import program_objective
 from test_mixed_host import E2E, assert_not_vacuous
 
 pytestmark = pytest.mark.gpu
@@ -319,38 +320,6 @@ def test_random_starts_are_admissible_and_reproducible(programs):
 
 
 # ---- end to end ------------------------------------------------------------------------------------------------------
-class _MixedProgramODE:
-    """Test double (the pattern of _ProgramODE in test_gpu_ode_program.py): the mixed problem's host objective whose
-    eval_f / eval_df run through mioc_ode_program_eval_mixed_device for one restart, so that the host loop TRM_mixed
-    and TRM_mixed_batch see bit-identical objective values and gradients."""
-
-    def __new__(cls, prog, nt, ctx):
-        import torch
-        obj = mixed.MixedLVObj(nt=nt)
-
-        def ev(X, J, D):
-            ctx.ode_program_eval_mixed_tensors(prog, mixed.NU, X, obj.T0, obj.T1, mixed.STATE0, mixed.PARAMS, J, D)
-            ctx.synchronize()
-
-        def f_helper(x, cache):
-            X = torch.tensor(np.ascontiguousarray(np.asarray(x).T[None]), dtype=torch.float64, device="cuda")
-            J = torch.empty(1, dtype=torch.float64, device="cuda")
-            torch.cuda.synchronize()
-            ev(X, J, None)
-            return J.item()
-
-        def df_helper():
-            X = torch.tensor(np.ascontiguousarray(obj.x.T[None]), dtype=torch.float64, device="cuda")
-            D = torch.empty_like(X)
-            torch.cuda.synchronize()
-            ev(X, None, D)
-            obj.df[:, :] = D[0].cpu().numpy().T
-
-        obj.eval_f_helper = f_helper
-        obj.eval_df_helper = df_helper
-        return obj
-
-
 def test_trm_mixed_batch_equals_host_loop(programs):
     K, nt = E2E["K"], E2E["nt"]
     par, cpar = mioc.TRM_parameters(**E2E["par"]), MixedParameters(**E2E["cpar"])
@@ -365,7 +334,8 @@ def test_trm_mixed_batch_equals_host_loop(programs):
     rows = []
     with native.Context(0) as ctx:
         for k in range(K):
-            obj = _MixedProgramODE(programs["lv"], nt, ctx)
+            obj = program_objective(mixed.MixedLVObj(nt=nt), programs["lv"], ctx, mixed.STATE0, mixed.PARAMS,
+                                    nu=mixed.NU, sync_torch=True)
             st = {}
             J = TRM_mixed(obj, par, cpar, x0=x0[k].T, stats=st)
             assert J == vals[k], (k, J, vals[k])

@@ -23,6 +23,7 @@ from mioc.trm_mixed import MixedParameters, TRM_mixed, TRM_mixed_batch
 import ode_bolza_problem as bp
 import ode_program_problem as fourth
 from ode_bolza_mirror import bolza_eval
+from ode_gpu_support import assert_at_bar as _assert_at_bar, grid as _grid, program_objective, run_program
 
 pytestmark = pytest.mark.gpu
 
@@ -51,27 +52,9 @@ def programs():
         p.close()
 
 
-def _grid(K, nt, seed):
-    """Random controls (K, nt, 2) on the product grid [[0,1,2],[0,1]]."""
-    rng = np.random.default_rng(seed)
-    return np.ascontiguousarray(np.stack([rng.integers(0, 3, size=(K, nt)), rng.integers(0, 2, size=(K, nt))],
-                                         axis=2).astype(np.float64))
-
-
-def _run(ctx, prog, x, T1, state0, params, data, want_J=True, want_df=True, want_Y=True):
-    """J (K,), df (K, nt, nx) and Y (K, nt + 1, ny) as numpy from NaN-prefilled device buffers (None where not asked
-    for)."""
-    import torch
-    dx = torch.tensor(x, dtype=torch.float64, device="cuda")
-    K, nt, _ = x.shape
-    dd = None if data is None else torch.tensor(data, dtype=torch.float64, device="cuda")
-    J = torch.full((K,), math.nan, dtype=torch.float64, device="cuda") if want_J else None
-    df = torch.full_like(dx, math.nan) if want_df else None
-    Y = torch.full((K, nt + 1, prog.ny), math.nan, dtype=torch.float64, device="cuda") if want_Y else None
-    torch.cuda.synchronize()
-    ctx.ode_program_eval_tensors(prog, dx, 0.0, T1, state0, params, J, df, data=dd, Y=Y)
-    ctx.synchronize()
-    return tuple(None if t is None else t.cpu().numpy() for t in (J, df, Y))
+def _run(ctx, prog, x, T1, state0, params, data, want_Y=True, **kw):
+    """J, df and Y from NaN-prefilled device buffers (None where not asked for)."""
+    return run_program(ctx, prog, x, 0.0, T1, state0, params, data=data, want_Y=want_Y, **kw)
 
 
 def _run_bolza(ctx, prog, x, T1, **kw):
@@ -85,21 +68,6 @@ def _mirror(x, T1, integrator, substeps):
     for k in range(K):
         Jh[k], dfh[k], Yh[k] = bolza_eval(bp.HOOKS, bp.PARAMS, data, bp.STATE0, 0.0, T1, x[k], integrator, substeps)
     return Jh, dfh, Yh
-
-
-def _assert_at_bar(dev, ref, label=""):
-    """1e-12 relative for J, 1e-12 of the maximum for df and Y, per restart; every figure printed before it is held."""
-    (J, df, Y), (Jh, dfh, Yh) = dev, ref
-    K = Jh.shape[0]
-    eJ = max(abs(J[k] - Jh[k]) / abs(Jh[k]) for k in range(K))
-    ed = max(np.max(np.abs(df[k] - dfh[k])) / max(1e-300, np.max(np.abs(dfh[k]))) for k in range(K))
-    eY = max(np.max(np.abs(Y[k] - Yh[k])) / max(1e-300, np.max(np.abs(Yh[k]))) for k in range(K))
-    exact = sum(int(J[k] == Jh[k]) + int(np.array_equal(df[k], dfh[k])) + int(np.array_equal(Y[k], Yh[k]))
-                for k in range(K))
-    print(f"{label}: {exact} of {3 * K} J / df / Y arrays bit-identical to the mirror; worst relative errors "
-          f"J {eJ:.3e}, df {ed:.3e}, Y {eY:.3e}")
-    assert np.all(np.isfinite(J)) and np.all(np.isfinite(df)) and np.all(np.isfinite(Y))
-    assert eJ <= 1e-12 and ed <= 1e-12 and eY <= 1e-12, (label, eJ, ed, eY)
 
 
 @pytest.fixture(scope="module")
@@ -313,40 +281,6 @@ def test_refusals_of_the_device_entries(programs, x70):
         assert bool(torch.isfinite(J).all())
 
 
-class _ProgramODE:
-    """Test double (the pattern of _ProgramODE in test_gpu_ode_integrators.py): the problem's host shape whose eval_f! /
-    eval_df! run the same program with the same data for one restart, so that the host TRM loops and the batch
-    drivers see bit-identical objective values and gradients.  nu None: TRM; nu >= 1: TRM_mixed."""
-
-    def __new__(cls, prog, nt, ctx, data, nu=None):
-        import torch
-        obj = bp.BolzaObj(nt=nt, T1=T1) if nu is None else bp.BolzaMixedObj(nt=nt, T1=T1)
-
-        def ev(X, J, D):
-            torch.cuda.synchronize()
-            if nu is None:
-                ctx.ode_program_eval_tensors(prog, X, obj.T0, obj.T1, bp.STATE0, bp.PARAMS, J, D, data=data)
-            else:
-                ctx.ode_program_eval_mixed_tensors(prog, nu, X, obj.T0, obj.T1, bp.STATE0, bp.PARAMS, J, D, data=data)
-            ctx.synchronize()
-
-        def f_helper(x, cache):
-            X = torch.tensor(np.ascontiguousarray(np.asarray(x).T[None]), dtype=torch.float64, device="cuda")
-            J = torch.empty(1, dtype=torch.float64, device="cuda")
-            ev(X, J, None)
-            return J.item()
-
-        def df_helper():
-            X = torch.tensor(np.ascontiguousarray(obj.x.T[None]), dtype=torch.float64, device="cuda")
-            D = torch.empty_like(X)
-            ev(X, None, D)
-            obj.df[:, :] = D[0].cpu().numpy().T
-
-        obj.eval_f_helper = f_helper
-        obj.eval_df_helper = df_helper
-        return obj
-
-
 def test_trm_batch_equals_sequential_trm(programs):
     import torch
     from mioc.trm_batch import TRM_batch
@@ -368,7 +302,8 @@ def test_trm_batch_equals_sequential_trm(programs):
         assert not np.array_equal(ub, x0.cpu().numpy())
         data = torch.tensor(rows, dtype=torch.float64, device="cuda")
         for k in range(K):
-            obj = _ProgramODE(prog, nt, ctx, data)
+            obj = program_objective(bp.BolzaObj(nt=nt, T1=T1), prog, ctx, bp.STATE0, bp.PARAMS, data=data,
+                                    sync_torch=True)
             J = mioc.TRM(obj, par, x0=x0[k].cpu().numpy().T.copy())
             assert J == vals[k], (k, J, vals[k])
             assert np.array_equal(obj.x, ub[k].T), k
@@ -415,7 +350,8 @@ def test_trm_mixed_batch_equals_host_loop(programs):
     with native.Context(0) as ctx:
         data = torch.tensor(rows, dtype=torch.float64, device="cuda")
         for k in range(K):
-            obj = _ProgramODE(prog, nt, ctx, data, nu=nu)
+            obj = program_objective(bp.BolzaMixedObj(nt=nt, T1=T1), prog, ctx, bp.STATE0, bp.PARAMS, data=data, nu=nu,
+                                    sync_torch=True)
             st = {}
             J = TRM_mixed(obj, par, cpar, x0=x0[k].T, stats=st)
             assert J == vals[k], (k, J, vals[k])

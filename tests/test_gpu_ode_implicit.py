@@ -6,8 +6,6 @@ the stiff problem at the bar of test_gpu_ode_program.py (1e-12 relative for J, 1
 operation order differs from the documented one.  Then independence of K, the finite-difference criterion and the order
 on the device's own numbers, the NaN contract of a restart whose Newton iteration cannot converge, scratch growth, and
 TRM_batch against the sequential TRM."""
-import math
-
 import numpy as np
 import pytest
 
@@ -18,6 +16,7 @@ from mioc.ode_device import DeviceODEProblem, ODEProgram
 
 import ode_program_problem as fourth
 import ode_stiff_problem as stiff
+from ode_gpu_support import assert_at_bar, grid as _grid, program_objective, run_program
 from ode_implicit_mirror import ORDER_BANDS, theta_eval
 from ode_rk_mirror import order_control
 
@@ -48,24 +47,10 @@ def programs():
         p.close()
 
 
-def _grid(K, nt, seed):
-    """Random controls (K, nt, 2) on the product grid [[0,1,2],[0,1]] of both problems."""
-    rng = np.random.default_rng(seed)
-    return np.ascontiguousarray(np.stack([rng.integers(0, 3, size=(K, nt)), rng.integers(0, 2, size=(K, nt))],
-                                         axis=2).astype(np.float64))
-
-
-def _run(ctx, prog, x, T1, want_J=True, want_df=True, state0=fourth.STATE0, params=fourth.PARAMS):
-    """J (K,) and df (K, nt, nx) as numpy from buffers prefilled with 7.0 (None where not asked for): a NaN in the
-    output is one the kernel wrote."""
-    import torch
-    dx = torch.tensor(x, dtype=torch.float64, device="cuda")
-    J = torch.full((x.shape[0],), 7.0, dtype=torch.float64, device="cuda") if want_J else None
-    df = torch.full_like(dx, 7.0) if want_df else None
-    torch.cuda.synchronize()
-    ctx.ode_program_eval_tensors(prog, dx, 0.0, T1, state0, params, J, df)
-    ctx.synchronize()
-    return (None if J is None else J.cpu().numpy()), (None if df is None else df.cpu().numpy())
+def _run(ctx, prog, x, T1, state0=fourth.STATE0, params=fourth.PARAMS, **kw):
+    """J and df from buffers prefilled with 7.0 (None where not asked for): a NaN in the output is one the kernel
+    wrote."""
+    return run_program(ctx, prog, x, 0.0, T1, state0, params, fill=7.0, **kw)[:2]
 
 
 def _run_p(ctx, programs, problem, integrator, substeps, x, T1, **kw):
@@ -81,12 +66,6 @@ def _mirror(problem, x, T1, integrator, substeps):
         Jh[k], d = theta_eval(obj, x[k].T, integrator, substeps)
         dfh[k] = d.T
     return Jh, dfh
-
-
-def _assert_at_bar(J, df, Jh, dfh):
-    for k in range(Jh.shape[0]):
-        assert abs(J[k] - Jh[k]) <= 1e-12 * abs(Jh[k]), (k, J[k], Jh[k])
-        assert np.max(np.abs(df[k] - dfh[k])) <= 1e-12 * max(1e-300, np.max(np.abs(dfh[k]))), k
 
 
 @pytest.fixture(scope="module")
@@ -116,7 +95,7 @@ def test_vs_mirror(programs, x70, device70, problem, integrator, substeps):
     Jh, dfh = _mirror(problem, x70, 0.96, integrator, substeps)
     exact = sum(int(J[k] == Jh[k]) + int(np.array_equal(df[k], dfh[k])) for k in range(70))
     print(f"{problem} {integrator} m={substeps}: {exact} of 140 J / df arrays bit-identical to the mirror")
-    _assert_at_bar(J, df, Jh, dfh)
+    assert_at_bar((J, df), (Jh, dfh))
     with native.Context(0) as ctx:
         J1, none = _run_p(ctx, programs, problem, integrator, substeps, x70, 0.96, want_df=False)  # no states stored
         assert none is None and np.array_equal(J1, J)
@@ -132,7 +111,7 @@ def test_edge_shapes(programs, integrator, substeps, nt):
     with native.Context(0) as ctx:
         J, df = _run_p(ctx, programs, "fourth", integrator, substeps, x, T1)
     assert np.all(np.isfinite(J)) and np.all(np.isfinite(df))
-    _assert_at_bar(J, df, *_mirror("fourth", x, T1, integrator, substeps))
+    assert_at_bar((J, df), _mirror("fourth", x, T1, integrator, substeps))
 
 
 @pytest.mark.parametrize("integrator,substeps", SCHEMES)
@@ -204,7 +183,7 @@ def test_non_convergence_is_nan_for_that_restart_only(programs, integrator, subs
     assert np.array_equal(Jv, J, equal_nan=True) and np.array_equal(dfv, df, equal_nan=True)
     obj = stiff.NoRootObj(nt=nt, T1=T1)
     Jh, dfh = theta_eval(obj, x[0].T, integrator, substeps)
-    _assert_at_bar(J[:1], df[:1], np.array([Jh]), dfh.T[None])
+    assert_at_bar((J[:1], df[:1]), (np.array([Jh]), dfh.T[None]))
 
 
 def test_scratch_growth_equals_fresh_context(programs):
@@ -217,36 +196,6 @@ def test_scratch_growth_equals_fresh_context(programs):
         J2, df2 = _run(ctx, prog, xl, 0.96)
     assert np.all(np.isfinite(J1)) and np.all(np.isfinite(df1))
     assert np.array_equal(J1, J2) and np.array_equal(df1, df2)
-
-
-class _ProgramODE:
-    """Test double (the pattern of _ProgramODE in test_gpu_ode_integrators.py): the fourth problem's host objective
-    whose eval_f! / eval_df! run the same program for one restart, so that the host TRM loop and TRM_batch see
-    bit-identical objective values and gradients."""
-
-    def __new__(cls, prog, nt, T1, ctx):
-        import torch
-        obj = fourth.FourthObj(nt=nt, T1=T1)
-
-        def ev(x, J, df):
-            ctx.ode_program_eval_tensors(prog, x, obj.T0, obj.T1, fourth.STATE0, fourth.PARAMS, J, df)
-            ctx.synchronize()
-
-        def f_helper(x, cache):
-            X = torch.tensor(np.ascontiguousarray(np.asarray(x).T[None]), dtype=torch.float64, device="cuda")
-            J = torch.empty(1, dtype=torch.float64, device="cuda")
-            ev(X, J, None)
-            return J.item()
-
-        def df_helper():
-            X = torch.tensor(np.ascontiguousarray(obj.x.T[None]), dtype=torch.float64, device="cuda")
-            D = torch.empty_like(X)
-            ev(X, None, D)
-            obj.df[:, :] = D[0].cpu().numpy().T
-
-        obj.eval_f_helper = f_helper
-        obj.eval_df_helper = df_helper
-        return obj
 
 
 def test_trm_batch_midpoint_equals_sequential_trm(programs):
@@ -267,7 +216,7 @@ def test_trm_batch_midpoint_equals_sequential_trm(programs):
         ub = u.cpu().numpy()
         assert not np.array_equal(ub, x0.cpu().numpy())
         for k in range(K):
-            obj = _ProgramODE(prog, nt, T1, ctx)
+            obj = program_objective(fourth.FourthObj(nt=nt, T1=T1), prog, ctx, fourth.STATE0, fourth.PARAMS)
             J = mioc.TRM(obj, par, x0=x0[k].cpu().numpy().T.copy())
             assert J == vals[k], (k, J, vals[k])
             assert np.array_equal(obj.x, ub[k].T), k

@@ -16,6 +16,7 @@ from mioc.iterators import LevelTable
 from mioc.ode_device import EXAMPLE_PARAMS, EXAMPLE_SHAPES, EXAMPLE_SOURCES, EXAMPLE_STATE0, DeviceODEProblem, ODEProgram
 
 import ode_program_problem as fourth
+from ode_gpu_support import assert_at_bar, grid as _grid, program_objective, run_program
 from ode_rk_mirror import ORDER_BANDS, order_control, rk_eval
 
 pytestmark = pytest.mark.gpu
@@ -39,23 +40,9 @@ def programs():
         p.close()
 
 
-def _grid(K, nt, seed):
-    """Random controls (K, nt, 2) on the fourth problem's product grid [[0,1,2],[0,1]]."""
-    rng = np.random.default_rng(seed)
-    return np.ascontiguousarray(np.stack([rng.integers(0, 3, size=(K, nt)), rng.integers(0, 2, size=(K, nt))],
-                                         axis=2).astype(np.float64))
-
-
-def _run(ctx, prog, x, T1, want_J=True, want_df=True):
-    """J (K,) and df (K, nt, nx) as numpy from NaN-prefilled device buffers (None where not asked for)."""
-    import torch
-    dx = torch.tensor(x, dtype=torch.float64, device="cuda")
-    J = torch.full((x.shape[0],), math.nan, dtype=torch.float64, device="cuda") if want_J else None
-    df = torch.full_like(dx, math.nan) if want_df else None
-    torch.cuda.synchronize()
-    ctx.ode_program_eval_tensors(prog, dx, 0.0, T1, fourth.STATE0, fourth.PARAMS, J, df)
-    ctx.synchronize()
-    return (None if J is None else J.cpu().numpy()), (None if df is None else df.cpu().numpy())
+def _run(ctx, prog, x, T1, **kw):
+    """J and df of the fourth problem from NaN-prefilled device buffers (None where not asked for)."""
+    return run_program(ctx, prog, x, 0.0, T1, fourth.STATE0, fourth.PARAMS, **kw)[:2]
 
 
 def _mirror(x, T1, integrator, substeps):
@@ -66,12 +53,6 @@ def _mirror(x, T1, integrator, substeps):
         Jh[k], d = rk_eval(obj, x[k].T, integrator, substeps)
         dfh[k] = d.T
     return Jh, dfh
-
-
-def _assert_at_bar(J, df, Jh, dfh):
-    for k in range(Jh.shape[0]):
-        assert abs(J[k] - Jh[k]) <= 1e-12 * abs(Jh[k]), (k, J[k], Jh[k])
-        assert np.max(np.abs(df[k] - dfh[k])) <= 1e-12 * max(1e-300, np.max(np.abs(dfh[k]))), k
 
 
 @pytest.fixture(scope="module")
@@ -99,7 +80,7 @@ def test_fourth_problem_vs_mirror(programs, x70, device70, integrator, substeps)
     Jh, dfh = _mirror(x70, 0.96, integrator, substeps)
     exact = sum(int(J[k] == Jh[k]) + int(np.array_equal(df[k], dfh[k])) for k in range(70))
     print(f"{integrator} m={substeps}: {exact} of 140 J / df arrays bit-identical to the mirror")
-    _assert_at_bar(J, df, Jh, dfh)
+    assert_at_bar((J, df), (Jh, dfh))
     assert np.all(df[:, :, 1] != 0.0)  # Gu[1] = 0.1 y0 is in every column
     with native.Context(0) as ctx:
         J1, none = _run(ctx, programs(integrator, substeps), x70, 0.96, want_df=False)  # d_df NULL: no states stored
@@ -116,7 +97,7 @@ def test_edge_shapes(programs, integrator, substeps, nt):
     with native.Context(0) as ctx:
         J, df = _run(ctx, programs(integrator, substeps), x, T1)
     assert np.all(np.isfinite(J)) and np.all(np.isfinite(df))
-    _assert_at_bar(J, df, *_mirror(x, T1, integrator, substeps))
+    assert_at_bar((J, df), _mirror(x, T1, integrator, substeps))
 
 
 @pytest.mark.parametrize("integrator,substeps", SCHEMES)
@@ -212,36 +193,6 @@ def test_scratch_growth_equals_fresh_context(programs):
     assert np.array_equal(J1, J2) and np.array_equal(df1, df2)
 
 
-class _ProgramODE:
-    """Test double (the pattern of _ProgramODE in test_gpu_ode_program.py): the fourth problem's host objective whose
-    eval_f! / eval_df! run the same program for one restart, so that the host TRM loop and TRM_batch see bit-identical
-    objective values and gradients."""
-
-    def __new__(cls, prog, nt, T1, ctx):
-        import torch
-        obj = fourth.FourthObj(nt=nt, T1=T1)
-
-        def ev(x, J, df):
-            ctx.ode_program_eval_tensors(prog, x, obj.T0, obj.T1, fourth.STATE0, fourth.PARAMS, J, df)
-            ctx.synchronize()
-
-        def f_helper(x, cache):
-            X = torch.tensor(np.ascontiguousarray(np.asarray(x).T[None]), dtype=torch.float64, device="cuda")
-            J = torch.empty(1, dtype=torch.float64, device="cuda")
-            ev(X, J, None)
-            return J.item()
-
-        def df_helper():
-            X = torch.tensor(np.ascontiguousarray(obj.x.T[None]), dtype=torch.float64, device="cuda")
-            D = torch.empty_like(X)
-            ev(X, None, D)
-            obj.df[:, :] = D[0].cpu().numpy().T
-
-        obj.eval_f_helper = f_helper
-        obj.eval_df_helper = df_helper
-        return obj
-
-
 def test_trm_batch_rk4_equals_sequential_trm(programs):
     """The parameters of test_gpu_ode_program.py::test_trm_batch_fourth_problem_equals_sequential_trm on a coarser
     control grid (nt = 48) with RK4 and 2 substeps."""
@@ -260,7 +211,7 @@ def test_trm_batch_rk4_equals_sequential_trm(programs):
         ub = u.cpu().numpy()
         assert not np.array_equal(ub, x0.cpu().numpy())
         for k in range(K):
-            obj = _ProgramODE(prog, nt, T1, ctx)
+            obj = program_objective(fourth.FourthObj(nt=nt, T1=T1), prog, ctx, fourth.STATE0, fourth.PARAMS)
             J = mioc.TRM(obj, par, x0=x0[k].cpu().numpy().T.copy())
             assert J == vals[k], (k, J, vals[k])
             assert np.array_equal(obj.x, ub[k].T), k

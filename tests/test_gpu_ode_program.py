@@ -18,6 +18,7 @@ from mioc.ode_device import (EXAMPLE_PARAMS, EXAMPLE_SHAPES, EXAMPLE_SOURCES, EX
                              ODEProgram)
 
 import ode_program_problem as fourth
+from ode_gpu_support import grid as _grid, program_objective, run_eval as _run, sos1 as _sos1
 
 pytestmark = pytest.mark.gpu
 
@@ -39,31 +40,6 @@ def _data(name):
     if name == "fourth":
         return fourth.STATE0, fourth.PARAMS
     return EXAMPLE_STATE0[name], EXAMPLE_PARAMS[name]
-
-
-def _sos1(K, nt, seed):
-    """Random admissible SOS1 controls (K, nt, 3): one control is 1 at every step."""
-    rng = np.random.default_rng(seed)
-    return np.ascontiguousarray(np.eye(3)[rng.integers(0, 3, size=(K, nt))])
-
-
-def _grid(K, nt, seed):
-    """Random controls (K, nt, 2) on the fourth problem's product grid [[0,1,2],[0,1]]."""
-    rng = np.random.default_rng(seed)
-    return np.ascontiguousarray(np.stack([rng.integers(0, 3, size=(K, nt)), rng.integers(0, 2, size=(K, nt))],
-                                         axis=2).astype(np.float64))
-
-
-def _run(ctx, x, evalf, want_J=True, want_df=True):
-    """J (K,) and df (K, nt, nx) as numpy from NaN-prefilled device buffers (None where not asked for)."""
-    import torch
-    dx = torch.tensor(x, dtype=torch.float64, device="cuda")
-    J = torch.full((x.shape[0],), math.nan, dtype=torch.float64, device="cuda") if want_J else None
-    df = torch.full_like(dx, math.nan) if want_df else None
-    torch.cuda.synchronize()
-    evalf(dx, J, df)
-    ctx.synchronize()
-    return (None if J is None else J.cpu().numpy()), (None if df is None else df.cpu().numpy())
 
 
 def _prog_eval(ctx, prog, name, T1):
@@ -199,36 +175,6 @@ def test_trm_batch_fishing_source_equals_builtin(programs):
     assert not torch.equal(ub, x0)  # the runs moved
 
 
-class _ProgramODE:
-    """Test double (the pattern of _DeviceODE in test_gpu_ode.py): the fourth problem's host objective whose eval_f! /
-    eval_df! run through mioc_ode_program_eval_device for one restart, so that the host TRM loop and TRM_batch see
-    bit-identical objective values and gradients."""
-
-    def __new__(cls, prog, nt, T1, ctx):
-        import torch
-        obj = fourth.FourthObj(nt=nt, T1=T1)
-
-        def ev(x, J, df):
-            ctx.ode_program_eval_tensors(prog, x, obj.T0, obj.T1, fourth.STATE0, fourth.PARAMS, J, df)
-            ctx.synchronize()
-
-        def f_helper(x, cache):
-            X = torch.tensor(np.ascontiguousarray(np.asarray(x).T[None]), dtype=torch.float64, device="cuda")
-            J = torch.empty(1, dtype=torch.float64, device="cuda")
-            ev(X, J, None)
-            return J.item()
-
-        def df_helper():
-            X = torch.tensor(np.ascontiguousarray(obj.x.T[None]), dtype=torch.float64, device="cuda")
-            D = torch.empty_like(X)
-            ev(X, None, D)
-            obj.df[:, :] = D[0].cpu().numpy().T
-
-        obj.eval_f_helper = f_helper
-        obj.eval_df_helper = df_helper
-        return obj
-
-
 def test_trm_batch_fourth_problem_equals_sequential_trm(programs):
     import torch
     from mioc.trm_batch import TRM_batch
@@ -244,7 +190,8 @@ def test_trm_batch_fourth_problem_equals_sequential_trm(programs):
         ub = u.cpu().numpy()
         assert not np.array_equal(ub, x0.cpu().numpy())
         for k in range(K):
-            obj = _ProgramODE(programs["fourth"], nt, T1, ctx)
+            obj = program_objective(fourth.FourthObj(nt=nt, T1=T1), programs["fourth"], ctx, fourth.STATE0,
+                                    fourth.PARAMS)
             J = mioc.TRM(obj, par, x0=x0[k].cpu().numpy().T.copy())
             assert J == vals[k], (k, J, vals[k])
             assert np.array_equal(obj.x, ub[k].T), k

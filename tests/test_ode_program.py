@@ -89,6 +89,110 @@ def test_null_arguments_and_oversize_source():
         ODEProgram(EXAMPLE_SOURCES["fishing"], 9, 3, 12)
 
 
+INTEGRATORS = {"euler": (native.MIOC_ODE_INT_EULER, ""), "heun": (native.MIOC_ODE_INT_HEUN, "#define NS 2\n"),
+               "rk4": (native.MIOC_ODE_INT_RK4, "#define NS 4\n"), "beuler": (native.MIOC_ODE_INT_BEULER, "#define TH 1.0\n"),
+               "midpoint": (native.MIOC_ODE_INT_MIDPOINT, "#define TH 0.5\n")}
+MARKERS = ['#line 1 "mioc_ad"', '#line 1 "hooks"\n', '\n#line 1 "mioc_ad_hooks"', '\n#line 1 "mioc_ode_program_skeleton"']
+
+
+def _source(text, ny, nx, nparams, ndata=0, integrator=native.MIOC_ODE_INT_EULER, substeps=1, derive=0, flags=0,
+            noinline=0, cap=1 << 18):
+    """mioc_ode_program_source into a prefilled buffer with 8 guard bytes behind cap: (return value, buffer)."""
+    lib = native.load_library()
+    buf = ctypes.create_string_buffer(cap + 8)
+    buf.raw = b"\xff" * (cap + 8)
+    return lib.mioc_ode_program_source(text, ny, nx, nparams, ndata, integrator, substeps, derive, flags, noinline, buf,
+                                       cap), buf
+
+
+@pytest.mark.parametrize("derive", [0, native.MIOC_ODE_DERIVE_ALL])
+@pytest.mark.parametrize("integrator", list(INTEGRATORS))
+def test_source_has_the_hooks_verbatim_and_the_documented_order(integrator, derive):
+    """include/mioc.h, "Derived hooks": the head, the dual type under mioc_ad, the caller's text under hooks, the
+    generated hooks under mioc_ad_hooks, the skeleton; the two mioc_ad parts only with derive != 0."""
+    code, head = INTEGRATORS[integrator]
+    hooks = fourth.SOURCE.encode()
+    n, buf = _source(hooks, fourth.NY, fourth.NX, len(fourth.PARAMS), integrator=code, derive=derive)
+    text = buf.value
+    assert n == len(text) > len(hooks)
+    assert text.startswith(f"#define NY {fourth.NY}\n#define NX {fourth.NX}\n#define NP {len(fourth.PARAMS)}\n{head}"
+                           .encode() + (b"#define MIOC_DERIVE_FY 1\n" if derive else b'#line 1 "hooks"\n'))
+    at = [text.find(m.encode()) for m in MARKERS]
+    present = [a for a, m in zip(at, MARKERS) if derive or "mioc_ad" not in m]
+    assert all(a >= 0 for a in present) and present == sorted(present), at
+    assert all(text.count(m.encode()) == (1 if derive or "mioc_ad" not in m else 0) for m in MARKERS)
+    assert text[at[1] + len(MARKERS[1]):].startswith(hooks + b"\n#line 1 ")    # verbatim, directly behind its marker
+    for once in (b"struct Par {", b"*gate == 0", b"pe[e] = P.p[e]", b"+ E(p, tend, y)", b"#define MIOC_DATA_ARG ,"):
+        assert text.count(once) == 1, once                                     # what every integrator shares: once
+    n1, buf1 = _source(hooks, fourth.NY, fourth.NX, len(fourth.PARAMS), integrator=code, derive=derive, noinline=1)
+    assert buf1.value == b"#define MIOC_AD_NOINLINE 1\n" + text and n1 == len(buf1.value)
+
+
+def test_source_of_a_plain_program_names_no_feature():
+    for integrator, (code, _) in INTEGRATORS.items():
+        n, buf = _source(fourth.SOURCE.encode(), fourth.NY, fourth.NX, len(fourth.PARAMS), integrator=code)
+        for word in (b"mioc_ad", b"MIOC_TERMINAL 1", b"MIOC_STATES 1", b"MIOC_DERIVE_", b"NOINLINE 1"):
+            assert n > 0 and word not in buf.value, (integrator, word)
+        # ND: only the skeleton's own default, "#ifndef ND / #define ND 0"; nothing in front of the skeleton defines it
+        assert buf.value.count(b"#define ND") == 1 and b"#ifndef ND\n#define ND 0\n#endif\n" in buf.value
+        assert b"#define ND" not in buf.value[:buf.value.index(MARKERS[3].encode())]
+    both = native.MIOC_ODE_TERMINAL | native.MIOC_ODE_STATES
+    n, buf = _source(fourth.SOURCE.encode(), fourth.NY, fourth.NX, len(fourth.PARAMS), ndata=3, flags=both)
+    head = buf.value[:buf.value.index(b"#line 1")]
+    assert head.endswith(b"#define ND 3\n#define MIOC_TERMINAL 1\n#define MIOC_STATES 1\n")
+
+
+def test_source_is_truncated_and_terminated():
+    args = (fourth.SOURCE.encode(), fourth.NY, fourth.NX, len(fourth.PARAMS))
+    need, full = _source(*args)
+    assert need == len(full.value)
+    for cap in (need + 1, need, 24, 1):
+        n, buf = _source(*args, cap=cap)
+        raw = buf.raw
+        assert n == need                                               # the length needed, whatever fits
+        assert raw[:cap] == full.value[:cap - 1] + b"\x00"             # cap - 1 characters, then the terminator
+        assert raw[cap:] == b"\xff" * 8                                # nothing written past the capacity
+    lib = native.load_library()
+    assert lib.mioc_ode_program_source(*args, 0, native.MIOC_ODE_INT_EULER, 1, 0, 0, 0, None, 0) == need  # a NULL buffer
+
+
+BOLZA_REFUSALS = [dict(ndata=17), dict(ndata=-1), dict(flags=4), dict(derive=32), dict(derive=native.MIOC_ODE_DERIVE_EY),
+                  dict(integrator=3), dict(substeps=2), dict(integrator=native.MIOC_ODE_INT_RK4, substeps=65),
+                  dict(integrator=native.MIOC_ODE_INT_HEUN, substeps=0)]
+
+
+@pytest.mark.parametrize("kw", [dict(zip(("ny", "nx", "nparams"), c)) for c in
+                                [(0, 3, 0), (9, 3, 0), (2, 9, 0), (2, 0, 0), (2, 3, 33), (2, 3, -1)]] + BOLZA_REFUSALS,
+                         ids=str)
+def test_source_fails_where_create_fails_its_argument_checks(kw):
+    """The cases of test_limits and the refusals of mioc_ode_program_create_bolza: both entries return MIOC_EINVAL."""
+    a = dict(ny=2, nx=3, nparams=12, ndata=0, integrator=native.MIOC_ODE_INT_EULER, substeps=1, derive=0, flags=0)
+    a.update(kw)
+    text = EXAMPLE_SOURCES["fishing"].encode()
+    lib, h, log = native.load_library(), ctypes.c_void_p(), ctypes.create_string_buffer(256)
+    rc = lib.mioc_ode_program_create_bolza(text, a["ny"], a["nx"], a["nparams"], a["ndata"], a["integrator"],
+                                           a["substeps"], a["derive"], a["flags"], ctypes.byref(h), log, 256)
+    n, buf = _source(text, **a)
+    assert rc == native.MIOC_EINVAL and not h.value
+    assert n == native.MIOC_EINVAL and buf.value == b""
+    assert _source(None, 2, 3, 12)[0] == native.MIOC_EINVAL
+    assert _source(b" " * ((1 << 20) + 1), 2, 3, 12)[0] == native.MIOC_EINVAL
+    assert _source(b" " * (1 << 20), 2, 3, 12, cap=16)[0] > (1 << 20)
+
+
+def test_python_source_text():
+    """ODEProgram.source_text and program_source return the entry's text."""
+    from mioc.ode_device import program_source
+    shape = (fourth.NY, fourth.NX, len(fourth.PARAMS))
+    want = _source(fourth.SOURCE.encode(), *shape, integrator=native.MIOC_ODE_INT_RK4, substeps=2)[1].value.decode()
+    assert program_source(fourth.SOURCE, *shape, integrator="rk4", substeps=2) == want
+    with ODEProgram(fourth.SOURCE, *shape, integrator="rk4", substeps=2) as prog:
+        assert prog.source_text() == want
+        assert prog.source_text(noinline=True) == "#define MIOC_AD_NOINLINE 1\n" + want
+    with pytest.raises(native.MiocNativeError):
+        program_source(fourth.SOURCE, 9, 2, 5)
+
+
 def _fd(obj, x, h, t):
     """fd_check of oracle/ode_oracle.py (the reference's test_df) on a host objective."""
     obj.x[:, :] = x
