@@ -194,7 +194,7 @@ __device__ __forceinline__ void sd_scan(const uint16_t *list, int nl, const doub
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
         const int j = tid + T * s;
-        const double val = (t1 + beta * (double)(dpre + (unsigned)abs(s - xl[M - 1]))) + psi[j];
+        const double val = (t1 + beta * (double)(dpre + (unsigned)abs(s - xl[M - 1]))) + psi[sd_swz_top<M>(tid, s)];
         if (val < bv) {
           bv = val;
           bj = j;
@@ -231,10 +231,11 @@ __device__ __forceinline__ void sd_scan(const uint16_t *list, int nl, const doub
       const unsigned pr = sd_bytes(r);
       double bv = INFINITY;
       int bj = -1;
+      const int lsw = lane ^ (lane >> 3);  // sd_swz(lane + 64·t) = (lsw ^ (t & 3) << 3) + 64·t: lane part, uniform part
       for (int t = 0; t < L / 64; ++t) {
         const int j = lane + 64 * t;
         const unsigned d = sd_l1(sd_bytes(j), pr);
-        const double val = (t1 + beta * (double)d) + psi[j];
+        const double val = (t1 + beta * (double)d) + psi[(lsw ^ ((t & 3) << 3)) + 64 * t];
         if (val < bv) {
           bv = val;
           bj = j;
@@ -368,7 +369,8 @@ __device__ __forceinline__ void sd_perm_load(SdPerm &pm, const uint32_t *__restr
 }
 
 // The first phase of row c' of step i: its loaded Ψ (v: this thread's eight positions, + the straddle element srank / xs)
-// into the LDS by rank (psi, for the winners and exact scans) and raw into the transform buffer (stamped by pass 0); the
+// into the LDS once, at the swizzled position of its rank (psi[sd_swz(j)]: pass 0 reads its lines from there without
+// bank conflicts and stamps them into the transform buffer; the winners and exact scans read Ψ_j through the swizzle); the
 // wave's min and max of Ψ and its counts (targets in the trust region, low 16 bits, per-step driver only; finite sources,
 // high 16 bits, exact where the wave holds a +Inf and L / NW otherwise) into sh.rmn / rmx / rnv[w].  Returns this lane's
 // trust-region targets (bit x: target tid | x << 3(M-1) has c' + b̃ <= B).
@@ -382,8 +384,7 @@ __device__ __forceinline__ unsigned sdt_stats(const ProblemDev &P, const PyrGeom
                                               const double *__restrict__ df_all, const double *__restrict__ uo_all,
                                               int srank = -1, double xs = 0.0) {
   constexpr int L = 1 << (3 * M);
-  double *psi = reinterpret_cast<double *>(sds);  // [L] Ψ_j by rank
-  double *dtv = psi + L;                          // [L] transform values (swizzled)
+  double *psi = reinterpret_cast<double *>(sds);  // [L] Ψ_j at sd_swz(rank j)
   const int tid = sd_tid(), lane = tid & 63, w = tid >> 6;
   const int B = P.B;
   const double *uoi = PERSIST ? reinterpret_cast<const double *>(sds + sd_dfuo_offset<M>()) +
@@ -419,15 +420,13 @@ __device__ __forceinline__ unsigned sdt_stats(const ProblemDev &P, const PyrGeom
       for (int hh = 0; hh < 2; ++hh) {
         const double x = v[2 * q + hh];
         const int j = (int)((hh ? ein[q].y : ein[q].x) & 0xFFFFu);
-        psi[j] = x;
-        dtv[sd_swz(j)] = x;  // raw, stamped by pass 0
+        psi[sd_swz(j)] = x;  // the row's one copy of Ψ: pass 0 reads its lines from it, stamps them into dtv
       }
     double xe = __longlong_as_double(0x7FF8000000000000ll);
     if constexpr (sd_strad<M>()) {  // this lane's straddle element
       const double x = (srank & 0x10000) ? INFINITY : xs;
       if (srank >= 0) {
-        psi[srank & 0xFFFF] = x;
-        dtv[sd_swz(srank & 0xFFFF)] = x;
+        psi[sd_swz(srank & 0xFFFF)] = x;
         xe = x;
       }
     }
@@ -485,8 +484,7 @@ __device__ __forceinline__ unsigned sdt_stats(const ProblemDev &P, const PyrGeom
       const double x = v[2 * q + hh];  // (sd_strad: +Inf for a straddling second element, written by its loader)
       // written anyway: the straddle lane is in this wave and writes after it (in-wave LDS order)
       const int j = (int)((hh ? ein[q].y : ein[q].x) & 0xFFFFu);
-      psi[j] = x;
-      dtv[sd_swz(j)] = x;  // raw, stamped by pass 0
+      psi[sd_swz(j)] = x;
       const bool fin = x < INFINITY;
       nv += __popcll(__ballot(fin)) << 16;
       pmn = sd_min(pmn, x);  // +Inf is neutral
@@ -531,8 +529,8 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
                                          const double *__restrict__ uo_all, int par, unsigned smask = 0,
                                          int srank = -1) {
   constexpr int L = 1 << (3 * M), T = L / 8, NW = T / 64, Smax = 7 * M;
-  double *psi = reinterpret_cast<double *>(sds);        // [L] Ψ_j by rank
-  double *dtv = psi + L;                                // [L] transform values (swizzled)
+  double *psi = reinterpret_cast<double *>(sds);        // [L] Ψ_j at sd_swz(rank j)
+  double *dtv = psi + L;                                // [L] the passes' values (swizzled the same way)
   uint16_t *uu = reinterpret_cast<uint16_t *>(dtv + L);  // [L] the U row (natural order)
   // [L] the outputs (natural order): a buffer of their own, so that the winners of one wave need not wait for every
   // other wave's last pass
@@ -604,17 +602,17 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
   // the whole row through the counting transform again (below); +Inf - +Inf is NaN, which v_min_f64 ignores
   double dmin = INFINITY;
   // COUNT = false: each merge is add, min, and the |a - b| folded into dmin off the value chain (the first transform);
-  // COUNT = true: the certified merge with the near-tie count in the payload (sd_merge), pass 0 reading the raw Ψ by
-  // rank (the redo: dtv holds the first transform's values by then)
+  // COUNT = true: the certified merge with the near-tie count in the payload (sd_merge).  Pass 0 of either reads the
+  // raw Ψ from psi, which no pass writes, so the redo starts from the same values
   auto pass = [&](int m, auto count_tag) {
     constexpr bool COUNT = decltype(count_tag)::value;
     int pos[8];
 #pragma unroll
     for (int x = 0; x < 8; ++x) {
       pos[x] = sd_swz(sd_rank((int)threadIdx.x, m, x));  // tid-only: hoisted out of the row loop
-      o[x] = (COUNT && m == 0) ? psi[sd_rank((int)threadIdx.x, 0, x)] : dtv[pos[x]];
+      o[x] = m == 0 ? psi[pos[x]] : dtv[pos[x]];
     }
-    if (m == 0) {  // the raw Ψ of ranks 8·tid + x (written with Ψ by rank): stamp them here
+    if (m == 0) {  // the raw Ψ of ranks 8·tid + x: stamp them here
 #pragma unroll
       for (int x = 0; x < 8; ++x) o[x] = stamp_inf(o[x], sd_rank((int)threadIdx.x, 0, x));
     }
@@ -658,7 +656,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
 #pragma unroll
     for (int x = 0; x < 8; ++x) jx[x] = (__double2loint(o[x]) >> SD_CB) & ((1 << SD_RB) - 1);  // +Inf: payload 0
 #pragma unroll
-    for (int x = 0; x < 8; ++x) pv[x] = psi[jx[x]];  // branch-free: the eight winners' Ψ reads issue together
+    for (int x = 0; x < 8; ++x) pv[x] = psi[sd_swz(jx[x])];  // branch-free: the eight winners' Ψ reads issue together
 #pragma unroll
     for (int x = 0; x < 8; ++x) {
       const int r = tid | (x << (3 * (M - 1))), j = jx[x];
@@ -774,24 +772,24 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
   if (sparse) {
     if (tid == 0) sh.nsp = 0;
     sd_bar();
-    // this lane's finite sources, from Ψ by rank (sd_strad: a straddling second element is its straddle lane's to add;
+    // this lane's finite sources, from Ψ in the LDS (sd_strad: a straddling second element is its straddle lane's to add;
     // otherwise this lane loaded it itself)
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
         const int j = (int)((hh ? ein[q].y : ein[q].x) & 0xFFFFu);
-        const double x = psi[j];
+        const double x = psi[sd_swz(j)];
         if (x < INFINITY && !(sd_strad<M>() && hh && (smask >> (3 * q + 2) & 1))) {
           const int e = atomicAdd(&sh.nsp, 1);
           sh.spj[e] = j;
           sh.spv[e] = x;
         }
       }
-    if (sd_strad<M>() && srank >= 0 && !(srank & 0x10000) && psi[srank & 0xFFFF] < INFINITY) {
+    if (sd_strad<M>() && srank >= 0 && !(srank & 0x10000) && psi[sd_swz(srank & 0xFFFF)] < INFINITY) {
       const int e = atomicAdd(&sh.nsp, 1);
       sh.spj[e] = srank & 0xFFFF;
-      sh.spv[e] = psi[srank & 0xFFFF];
+      sh.spv[e] = psi[sd_swz(srank & 0xFFFF)];
     }
     sd_bar();
 #pragma unroll
@@ -810,7 +808,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
     // every other source by more than tol); a row that met a near tie anywhere is redone below, counting them
     unsigned listed = 0;
     if (is_one()) {
-      // ---- the one-target item: the reference loop for target l0 over every source, Ψ by rank from the LDS (thread t:
+      // ---- the one-target item: the reference loop for target l0 over every source, Ψ from the LDS (thread t:
       // sources t + T·s, ascending, so a strict `<` keeps the lower rank; a +Inf source never wins), the wave's
       // (value, rank) minimum through DPP, one partial per wave.  No outputs through the LDS, no list, no barrier of
       // its own: the drain's barrier below publishes the partials, and the lanes fold them in registers past it.
@@ -822,7 +820,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
       const unsigned dpre = sd_l1(sd_bytes(tid), sd_bytes(l0 & ((1 << (3 * (M - 1))) - 1)));
       double ps[8];
 #pragma unroll
-      for (int s = 0; s < 8; ++s) ps[s] = psi[tid + T * s];
+      for (int s = 0; s < 8; ++s) ps[s] = psi[sd_swz_top<M>(tid, s)];
       double bv = INFINITY;
       int bj = -1;
 #pragma unroll
@@ -893,7 +891,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
       return nl;
     };
     // (persistent driver) a direct row has no passes between go() and the drain: it would sit out the whole latency of
-    // the next row's loads in the drain and only then scan.  Its scans need nothing the drain brings (Ψ by rank and the
+    // the next row's loads in the drain and only then scan.  Its scans need nothing the drain brings (Ψ and the
     // list are in the LDS), so they run first, under that latency; the drain's barrier then publishes their results
     // together with the previous row's `done`.  (Row B of every step, with its one target, has scanned above without a
     // list: the one-target item.  This is for direct rows with two to SD_FEW targets, or whose scale does not fit.)
@@ -1199,7 +1197,7 @@ struct SdHooksNone {
   }
 };
 
-// LDS bytes of the row body: Ψ by rank, the transform / output values, the U row, the scan list, and two
+// LDS bytes of the row body: Ψ (swizzled by rank), the transform / output values, the U row, the scan list, and two
 // sphere-order slots (steps i+1 and i)
 size_t sdt_lds_bytes(const PyrGeom &G) { return G.M == 4 ? sd_lds_total<4>() : sd_lds_total<3>(); }
 

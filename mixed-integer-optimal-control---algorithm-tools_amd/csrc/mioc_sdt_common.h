@@ -152,6 +152,18 @@ __device__ __forceinline__ void sd_wave_argmin(double &bv, int &bj) {
 // 32 distinct 8-byte bank slots in every pass: slot = (x0 ^ x1) + 8·((x1 ^ x2) & 3)
 __device__ __forceinline__ int sd_swz(int r) { return r ^ ((r >> 3) & 7) ^ (((r >> 6) & 3) << 3); }
 
+// sd_swz(q + 8^(M-1)·s), the LDS position of rank q with top coordinate s (q < 8^(M-1)).  The swizzle reads rank bits
+// 3..7 only: at M = 4 the top coordinate (bits 9..11) is outside them, so it is sd_swz(q) plus the top term, and a
+// loop over s hoists the swizzle; at M = 3 the top coordinate's low bits (6, 7) feed the swizzle
+template <int M>
+__device__ __forceinline__ int sd_swz_top(int q, int s) {
+  constexpr int T = 1 << (3 * (M - 1));
+  if constexpr (3 * (M - 1) >= 8)
+    return sd_swz(q) + T * s;
+  else
+    return sd_swz(q + T * s);
+}
+
 // rank of element x of line q in the pass over dimension m (q enumerates the other coordinates, lowest
 // dimension fastest)
 __device__ __forceinline__ int sd_rank(int q, int m, int x) {
