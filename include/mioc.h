@@ -654,10 +654,19 @@ int32_t mioc_heat_eval(mioc_ctx *ctx, int64_t K, const double *x, double *J, dou
  *        built here from τ = (T1 − T0) / nt.
  * One control with signed levels (𝓥 = [[-2,-1,0,1,2]]).  1 <= nt <= 16384 (κ is held in LDS).  mioc_conv_eval_device:
  * d_x = K x 1 x nt controls (the DP's input layout), d_J (K, nullable: no value), d_df (K x 1 x nt, nullable: stops
- * after J).  Enqueued.  A restart's J and df do not depend on K or on its position in the batch.  Errors:
- * MIOC_EINVAL (nt out of range, T1 <= T0, NULL pointers, non-finite κ / fvec), MIOC_ESTATE (eval before a successful
- * setup), MIOC_ENOMEM (the v scratch, K x (nt+1) doubles, cannot grow).
+ * after J).  Enqueued.  A restart's J and df do not depend on K or on its position in the batch.  A mioc_conv_setup
+ * that fails validation (MIOC_EINVAL: nt out of range, T1 <= T0 or either not finite, a null input, a non-finite κ or
+ * fvec) returns before it touches the context's convolution problem: the last successful setup stays in force.
+ * Errors: MIOC_EINVAL (the above; eval: K out of range, a null x, the host entry with neither J nor df), MIOC_ESTATE
+ * (eval before a successful setup), MIOC_ENOMEM (the context's scratch cannot grow: K x (nt+1) doubles of v for J
+ * alone, K x (2·nt+17) with a gradient -- v and the rows of w = M·v, nt+16 each; it is kept between calls and
+ * never shrinks).
+ * mioc_conv_tiles_per_wave: which variant of the product kernel an evaluation of K restarts at nt runs -- 1 or 2
+ * column tiles of 16 per wave (two once (K+15)/16 restart tiles x ceil(nt/32) waves give every SIMD one; the results
+ * are the same bit for bit), 0 when nt or K is out of range.  For tests and tools that must know what they exercise;
+ * needs no context.
  */
+int32_t mioc_conv_tiles_per_wave(int64_t nt, int64_t K);
 int32_t mioc_conv_setup(mioc_ctx *ctx, int64_t nt, double T0, double T1, const double *kappa, const double *fvec);
 int32_t mioc_conv_eval_device(mioc_ctx *ctx, int64_t K, const double *d_x, double *d_J, double *d_df);
 /* The same from host arrays (the Julia objective's x / df, K x 1 x nt; J: K), synchronous. */

@@ -258,10 +258,15 @@ hipError_t launch_conv_mm_ns(hipStream_t s, const ConvArgs &C) {
   return hipGetLastError();
 }
 
+// the one place that chooses: waves of two column tiles over the 16-restart tiles of K, against CFILL
+int conv_tiles_per_wave(int64_t nt, int64_t K) {
+  const int64_t waves2 = ((K + 15) / 16) * ((nt + 31) / 32);
+  return waves2 >= CFILL ? 2 : 1;
+}
+
 template <bool ADJ>
 hipError_t launch_conv_mm(hipStream_t s, const ConvArgs &C) {
-  const int64_t waves2 = (int64_t)C.rtiles * ((C.nt + 31) / 32);
-  return waves2 >= CFILL ? launch_conv_mm_ns<ADJ, 2>(s, C) : launch_conv_mm_ns<ADJ, 1>(s, C);
+  return conv_tiles_per_wave(C.nt, C.K) == 2 ? launch_conv_mm_ns<ADJ, 2>(s, C) : launch_conv_mm_ns<ADJ, 1>(s, C);
 }
 
 int conv_fail(mioc_ctx *ctx, int code, const std::string &msg) {
@@ -283,6 +288,11 @@ int conv_upload(mioc_ctx *ctx, DevBuf<double> &dst, const double *src, size_t n,
 using namespace mioc;
 
 extern "C" {
+
+int32_t mioc_conv_tiles_per_wave(int64_t nt, int64_t K) {
+  if (nt < 1 || nt > CMAXNT || K < 1 || K > INT32_MAX) return 0;
+  return conv_tiles_per_wave(nt, K);
+}
 
 int32_t mioc_conv_setup(mioc_ctx *ctx, int64_t nt, double T0, double T1, const double *kappa, const double *fvec) {
   if (!ctx) return MIOC_EINVAL;

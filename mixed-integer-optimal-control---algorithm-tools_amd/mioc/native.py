@@ -51,7 +51,7 @@ EXPORTED = [
     "mioc_pred", "mioc_pred_batch_device", "mioc_tv_device", "mioc_trm_decide_device", "mioc_batch_multi",
     "mioc_ode_eval_device", "mioc_rand_start_device", "mioc_backtrack_batch_budgets_device",
     "mioc_heat_setup", "mioc_heat_eval_device", "mioc_heat_eval",
-    "mioc_conv_setup", "mioc_conv_eval_device", "mioc_conv_eval",
+    "mioc_conv_setup", "mioc_conv_eval_device", "mioc_conv_eval", "mioc_conv_tiles_per_wave",
     "mioc_trm_state_bytes", "mioc_trm_attach", "mioc_trm_outer_begin_device", "mioc_trm_inner_end_device",
     "mioc_trm_poll",
     "mioc_ode_program_create", "mioc_ode_program_destroy", "mioc_ode_program_eval_device",
@@ -137,6 +137,7 @@ def load_library(path=None):
         "mioc_conv_setup": (i32, [vp, i64, dbl, dbl, vp, vp]),
         "mioc_conv_eval_device": (i32, [vp, i64, vp, vp, vp]),
         "mioc_conv_eval": (i32, [vp, i64, vp, vp, vp]),
+        "mioc_conv_tiles_per_wave": (i32, [i64, i64]),
         "mioc_trm_state_bytes": (i64, [i64]),
         "mioc_trm_attach": (i32, [vp, vp]),
         "mioc_trm_outer_begin_device": (i32, [vp, i64, vp, vp, dbl, i64, vp]),
@@ -677,6 +678,14 @@ class Context:
             self.h, K, ctypes.c_void_p(x.data_ptr()),
             ctypes.c_void_p(J.data_ptr()) if J is not None else None,
             ctypes.c_void_p(df.data_ptr()) if df is not None else None))
+
+    def conv_tiles_per_wave(self, nt, K):
+        """1 or 2: the column tiles per wave of the product kernel that K restarts at nt run
+        (mioc_conv_tiles_per_wave)."""
+        n = self.lib.mioc_conv_tiles_per_wave(int(nt), int(K))
+        if n not in (1, 2):
+            raise ValueError("nt or K out of range")
+        return n
 
     def conv_eval(self, xs):
         """Host entry (mioc_conv_eval): xs (K, 1, nt) numpy controls (Julia's per-restart layout) -> J (K,),
