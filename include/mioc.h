@@ -495,6 +495,35 @@ int32_t mioc_ode_eval_device(mioc_ctx *ctx, int32_t problem, int64_t K, const do
  *   ndata == 0.  The two older entries refuse a program with ndata > 0 (MIOC_EINVAL) and work as before on one with
  *   the terminal or the states flag and ndata == 0 (no state output).  Gate, stream and scratch growth as there.
  *
+ * Scenarios.  mioc_ode_program_create_scen(..., flags, scen, ...) lets the restarts of one call solve different
+ * problems: a scenario is one triple (state0, params, data), and a program compiled for scenarios is evaluated with S
+ * of them.  The lane of restart q solves scenario q % S, where q is the restart index k, or j*K + k for the K*R
+ * candidates of a fan: with K a multiple of S, restart k and each of its line-search candidates see scenario k % S,
+ * and K = S*m gives m starts on each of S problems in one call.  The head #defines MIOC_SCEN 1 (scen bit
+ * MIOC_ODE_SCEN) and MIOC_SCEN_DATA 1 (bit MIOC_ODE_SCEN_DATA) behind MIOC_STATES; with scen == 0 the head is
+ * _create_bolza's byte for byte and the skeletons preprocess to the same tokens, so such a program is the program it
+ * was.  mioc_ode_program_create_bolza(...) is _scen(..., scen = 0, ...).
+ *   MIOC_ODE_SCEN       state0 and the parameters are per scenario.  The kernel takes `int S, const double *Y0S, const
+ *              double *PS` in place of the by-value state0 and parameters, device arrays with the scenario index
+ *              fastest, like the state scratch: d_state0[r*S + s] (ny x S doubles), d_params[e*S + s] (nparams x S;
+ *              NULL is allowed with nparams == 0).  Each lane computes s = q % S once and loads its parameters once
+ *              into its own copy of p (NP + ND doubles, the copy that ND > 0 already makes), its state0 at the start of
+ *              the forward sweep and again for row i = 0 of Euler's backward sweep; with S >= 64 the 64 lanes of a
+ *              wave load 64 contiguous doubles.  d_data stays the shared nt x ndata table, read by scalar loads.
+ *   MIOC_ODE_SCEN_DATA  (only with MIOC_ODE_SCEN and ndata > 0) the data rows are per scenario as well:
+ *              d_data[(c*ndata + e)*S + s], nt x ndata x S doubles, and every lane loads its own row of column c
+ *              (ndata vector loads) wherever the shared row was loaded; the columns are those listed under "data".
+ *   The arrays are restrict-qualified: they must not overlap d_J, d_df, d_Y or the context's scratch.  The hook
+ *   signatures, the hook contract, every rounding order above and the generated hooks do not change (p is still never
+ *   differentiated): restart q computes bit for bit what a program without scenarios computes from scenario q % S's
+ *   values.  Row 0 of d_Y[q] is scenario q % S's state0.  The bounds of a mixed control stay shared.
+ *   MIOC_EINVAL from _create_scen (and _source_scen): scen bits outside 3, scen == MIOC_ODE_SCEN_DATA alone,
+ *              MIOC_ODE_SCEN_DATA with ndata == 0 (and every case of _create_bolza).
+ * mioc_ode_program_eval_scen_device is the body of mioc_ode_program_eval_bolza_device (the same nu checks, gate, stream
+ *   and scratch growth) with S and the device arrays above.  MIOC_EINVAL also for S < 1, K not a multiple of S, d_state0
+ *   NULL, d_params NULL with nparams > 0, d_data NULL with ndata > 0, and a program compiled with scen == 0.  The three
+ *   older eval entries refuse a scenario program (MIOC_EINVAL).  A refused call leaves the context usable.
+ *
  * mioc_ode_program_create needs no context and no GPU: it compiles for gfx950 and keeps the code object.  Limits:
  *   1 <= ny <= 8, 1 <= nx <= 8, 0 <= nparams <= 32, source text of at most 1 MiB (else MIOC_EINVAL).  A compile
  *   failure returns MIOC_ECOMPILE; the compiler's log (also the warnings of a successful compile) is copied into
@@ -549,6 +578,16 @@ int32_t mioc_ode_program_create_bolza(const char *hooks, int32_t ny, int32_t nx,
 int64_t mioc_ode_program_source(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
                                 int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t noinline,
                                 char *text, int64_t text_cap);
+/* _create_bolza and _source for a program whose restarts solve different scenarios (see "Scenarios" above); scen == 0
+ * is _create_bolza, and _source's text byte for byte. */
+#define MIOC_ODE_SCEN      1     /* scen: state0 and the parameters per scenario */
+#define MIOC_ODE_SCEN_DATA 2     /* scen: the data rows per scenario as well; only with MIOC_ODE_SCEN and ndata > 0 */
+int32_t mioc_ode_program_create_scen(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
+                                     int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t scen,
+                                     mioc_ode_program **out, char *log, int64_t log_cap);
+int64_t mioc_ode_program_source_scen(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
+                                     int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t scen,
+                                     int32_t noinline, char *text, int64_t text_cap);
 int32_t mioc_ode_program_destroy(mioc_ode_program *prog);
 int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t K, const double *d_x, int64_t nt,
                                      double T0, double T1, const double *state0, const double *params, double *d_J,
@@ -603,6 +642,10 @@ int32_t mioc_ode_program_eval_bolza_device(mioc_ctx *ctx, mioc_ode_program *prog
                                            const double *d_x, int64_t nt, double T0, double T1, const double *state0,
                                            const double *params, const double *d_data, double *d_J, double *d_df,
                                            double *d_Y);
+int32_t mioc_ode_program_eval_scen_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K,
+                                          const double *d_x, int64_t nt, double T0, double T1, int64_t S,
+                                          const double *d_state0, const double *d_params, const double *d_data,
+                                          double *d_J, double *d_df, double *d_Y);
 int32_t mioc_rows_copy_device(mioc_ctx *ctx, int64_t K, int64_t nt, double *d_dst, int64_t dst_nx, int64_t dst_row0,
                               const double *d_src, int64_t src_nx, int64_t src_row0, int64_t nrows);
 int64_t mioc_mixed_state_bytes(int64_t K);

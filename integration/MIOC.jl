@@ -346,6 +346,65 @@ function ode_program_eval_bolza_device!(ctx::Context, prog::Ptr{Cvoid}, nu::Inte
     nothing
 end
 
+# ---- scenarios: restart q of a call solves scenario q % S (include/mioc.h, "Scenarios").  Thin wrappers of the two
+# entries; they have not been run under Julia (none is installed where this was written).
+const MIOC_ODE_SCEN = Int32(1)
+const MIOC_ODE_SCEN_DATA = Int32(2)
+
+"""
+    ode_program_create_scen(hooks, ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen) -> Ptr{Cvoid}
+
+mioc_ode_program_create_scen with the C entry's own integer arguments (`integrator`: a value of `ODE_INTEGRATORS`;
+`scen`: `MIOC_ODE_SCEN`, or `MIOC_ODE_SCEN | MIOC_ODE_SCEN_DATA` with `ndata > 0`; 0 is `ode_program_create_bolza`).
+"""
+function ode_program_create_scen(hooks::String, ny::Integer, nx::Integer, nparams::Integer, ndata::Integer,
+                                 integrator::Integer, substeps::Integer, derive::Integer, flags::Integer,
+                                 scen::Integer)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    log = zeros(UInt8, 1 << 16)
+    rc = ccall((:mioc_ode_program_create_scen, libmioc), Int32,
+               (Cstring, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Ptr{Ptr{Cvoid}}, Ptr{UInt8},
+                Int64), hooks, ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen, r, log, length(log))
+    rc == MIOC_OK || error("mioc_ode_program_create_scen failed with $rc:\n" * unsafe_string(pointer(log)))
+    r[]
+end
+
+"""
+    ode_program_source_scen(hooks, ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen; noinline = false)
+
+The text `ode_program_create_scen` would compile (mioc_ode_program_source_scen), as a String.
+"""
+function ode_program_source_scen(hooks::String, ny::Integer, nx::Integer, nparams::Integer, ndata::Integer,
+                                 integrator::Integer, substeps::Integer, derive::Integer, flags::Integer,
+                                 scen::Integer; noinline::Bool = false)
+    sig = (Cstring, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Ptr{UInt8}, Int64)
+    need = ccall((:mioc_ode_program_source_scen, libmioc), Int64, sig, hooks, ny, nx, nparams, ndata, integrator,
+                 substeps, derive, flags, scen, noinline, C_NULL, 0)
+    need >= 0 || error("mioc_ode_program_source_scen failed with $need")
+    buf = zeros(UInt8, need + 1)
+    ccall((:mioc_ode_program_source_scen, libmioc), Int64, sig, hooks, ny, nx, nparams, ndata, integrator, substeps,
+          derive, flags, scen, noinline, buf, length(buf))
+    unsafe_string(pointer(buf))
+end
+
+"""
+    ode_program_eval_scen_device!(ctx, prog, nu, K, d_x, nt, T0, T1, S, d_state0, d_params, d_data, d_J, d_df, d_Y)
+
+`ode_program_eval_bolza_device!` for a program compiled with scenarios (mioc_ode_program_eval_scen_device): device
+arrays with the scenario index fastest, `d_state0` ny × S, `d_params` nparams × S (C_NULL with nparams = 0), `d_data`
+nt × ndata, or nt × ndata × S with `MIOC_ODE_SCEN_DATA`; K must be a multiple of S.
+"""
+function ode_program_eval_scen_device!(ctx::Context, prog::Ptr{Cvoid}, nu::Integer, K::Integer, d_x::Ptr{Float64},
+                                       nt::Integer, T0::Float64, T1::Float64, S::Integer, d_state0::Ptr{Float64},
+                                       d_params::Ptr{Float64}, d_data::Ptr{Float64}, d_J::Ptr{Float64},
+                                       d_df::Ptr{Float64}, d_Y::Ptr{Float64})
+    check(ctx, ccall((:mioc_ode_program_eval_scen_device, libmioc), Int32,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Float64, Float64, Int64, Ptr{Float64},
+                      Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ctx.ptr, prog, nu, K, d_x,
+                     nt, T0, T1, S, d_state0, d_params, d_data, d_J, d_df, d_Y))
+    nothing
+end
+
 # ---- mixed controls: nu continuous controls in front of the DP's integer ones (include/mioc.h, "Mixed controls").
 # Thin wrappers of the six entries; they have not been run under Julia (none is installed where this was written).
 

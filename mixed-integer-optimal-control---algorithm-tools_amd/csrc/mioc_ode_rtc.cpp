@@ -9,7 +9,8 @@
 // so libmioc.so carries no link-time dependency on it and loads as before where it is absent.
 //
 // The assembled text: the head's #defines (NY, NX, NP; NS, the stage count, for Heun / RK4 or TH, theta, for the
-// implicit schemes; ND, MIOC_TERMINAL, MIOC_STATES and MIOC_DERIVE_* only when asked for), the dual type kAdPrelude
+// implicit schemes; ND, MIOC_TERMINAL, MIOC_STATES, MIOC_SCEN, MIOC_SCEN_DATA and MIOC_DERIVE_* only when asked for),
+// the dual type kAdPrelude
 // (derive != 0), the caller's text, the generated hooks kAdHooks (derive != 0), then kSkeletonHead and the integrator's
 // body: kBodyEuler, kBodyRK (Heun, RK4) or kBodyTheta (backward Euler, implicit midpoint).  A program that does not ask
 // for a feature gets no byte of it in the head, and the skeleton preprocesses to the tokens it has without it.
@@ -125,7 +126,7 @@ std::string without_remarks(const std::string &log) {
 }  // namespace
 
 struct mioc_ode_program {
-  int ny = 0, nx = 0, np = 0, nd = 0, flags = 0;
+  int ny = 0, nx = 0, np = 0, nd = 0, flags = 0, scen = 0;
   int integrator = MIOC_ODE_INT_EULER, substeps = 1;
   std::vector<char> code;  // the gfx950 code object
   struct Loaded {
@@ -141,7 +142,7 @@ namespace {
 
 // What a program is compiled from, besides the caller's text.
 struct ProgramSpec {
-  int ny, nx, np, nd, integrator, substeps, derive, flags;
+  int ny, nx, np, nd, integrator, substeps, derive, flags, scen;
   bool euler() const { return integrator == MIOC_ODE_INT_EULER; }
   bool implicit() const { return integrator == MIOC_ODE_INT_BEULER || integrator == MIOC_ODE_INT_MIDPOINT; }
 };
@@ -155,6 +156,9 @@ int validate(const ProgramSpec &s, const char *hooks, size_t *len) {
   if (s.substeps < 1 || s.substeps > kMaxSubsteps || (s.euler() && s.substeps != 1)) return MIOC_EINVAL;
   if (s.derive & ~(MIOC_ODE_DERIVE_ALL | MIOC_ODE_DERIVE_EY)) return MIOC_EINVAL;
   if ((s.derive & MIOC_ODE_DERIVE_EY) && !(s.flags & MIOC_ODE_TERMINAL)) return MIOC_EINVAL;
+  // per-scenario data need per-scenario state0 and parameters, and data
+  if ((s.scen & ~(MIOC_ODE_SCEN | MIOC_ODE_SCEN_DATA)) || s.scen == MIOC_ODE_SCEN_DATA) return MIOC_EINVAL;
+  if ((s.scen & MIOC_ODE_SCEN_DATA) && s.nd == 0) return MIOC_EINVAL;
   *len = strnlen(hooks, kMaxSource + 1);
   return *len > kMaxSource ? MIOC_EINVAL : MIOC_OK;
 }
@@ -182,6 +186,8 @@ std::string assemble(const ProgramSpec &s, const char *hooks, size_t len, bool n
   if (s.nd > 0) define("ND", std::to_string(s.nd));
   if (s.flags & MIOC_ODE_TERMINAL) define("MIOC_TERMINAL", "1");
   if (s.flags & MIOC_ODE_STATES) define("MIOC_STATES", "1");
+  if (s.scen & MIOC_ODE_SCEN) define("MIOC_SCEN", "1");
+  if (s.scen & MIOC_ODE_SCEN_DATA) define("MIOC_SCEN_DATA", "1");
   if (s.derive) {  // the guard macros and the dual type in front of the caller's text; derive == 0 adds no byte
     if (s.derive & MIOC_ODE_DERIVE_FY) define("MIOC_DERIVE_FY", "1");
     if (s.derive & MIOC_ODE_DERIVE_FU) define("MIOC_DERIVE_FU", "1");
@@ -277,10 +283,17 @@ int32_t mioc_ode_program_create_ad(const char *hooks, int32_t ny, int32_t nx, in
 int32_t mioc_ode_program_create_bolza(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
                                       int32_t integrator, int32_t substeps, int32_t derive, int32_t flags,
                                       mioc_ode_program **out, char *log, int64_t log_cap) {
+  return mioc_ode_program_create_scen(hooks, ny, nx, nparams, ndata, integrator, substeps, derive, flags, 0, out, log,
+                                      log_cap);
+}
+
+int32_t mioc_ode_program_create_scen(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
+                                     int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t scen,
+                                     mioc_ode_program **out, char *log, int64_t log_cap) {
   put_log(log, log_cap, "", 0);
   if (!out) return MIOC_EINVAL;
   *out = nullptr;
-  const ProgramSpec spec{ny, nx, nparams, ndata, integrator, substeps, derive, flags};
+  const ProgramSpec spec{ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen};
   size_t len = 0;
   if (validate(spec, hooks, &len) != MIOC_OK) return MIOC_EINVAL;
   const Rtc &R = rtc();
@@ -293,7 +306,7 @@ int32_t mioc_ode_program_create_bolza(const char *hooks, int32_t ny, int32_t nx,
   // each however many stages call it.
   try {
     std::unique_ptr<mioc_ode_program> p(new mioc_ode_program);
-    p->ny = ny, p->nx = nx, p->np = nparams, p->nd = ndata, p->flags = flags;
+    p->ny = ny, p->nx = nx, p->np = nparams, p->nd = ndata, p->flags = flags, p->scen = scen;
     p->integrator = integrator, p->substeps = substeps;
     bool over = false;
     int ret = compile(assemble(spec, hooks, len, false), derive != 0, "", &p->code, &over, log, log_cap);
@@ -309,8 +322,15 @@ int32_t mioc_ode_program_create_bolza(const char *hooks, int32_t ny, int32_t nx,
 int64_t mioc_ode_program_source(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
                                 int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t noinline,
                                 char *text, int64_t text_cap) {
+  return mioc_ode_program_source_scen(hooks, ny, nx, nparams, ndata, integrator, substeps, derive, flags, 0, noinline,
+                                      text, text_cap);
+}
+
+int64_t mioc_ode_program_source_scen(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
+                                     int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t scen,
+                                     int32_t noinline, char *text, int64_t text_cap) {
   put_log(text, text_cap, "", 0);
-  const ProgramSpec spec{ny, nx, nparams, ndata, integrator, substeps, derive, flags};
+  const ProgramSpec spec{ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen};
   size_t len = 0;
   if (validate(spec, hooks, &len) != MIOC_OK) return MIOC_EINVAL;
   try {
@@ -339,15 +359,21 @@ int32_t mioc_ode_program_destroy(mioc_ode_program *prog) {
   return rc;
 }
 
-// The body of both eval entries.  nu = 0: every control is the DP's (mioc_ode_program_eval_device); nu >= 1: the first
-// nu controls are continuous and the levels describe the other nx - nu (mioc_ode_program_eval_mixed_device).
+// The body of every eval entry.  nu = 0: every control is the DP's (mioc_ode_program_eval_device); nu >= 1: the first
+// nu controls are continuous and the levels describe the other nx - nu (mioc_ode_program_eval_mixed_device).  S = 0:
+// state0 and params are host arrays, passed by value to a program without scenarios; S >= 1: they are the device
+// arrays of S scenarios for a program compiled with them (mioc_ode_program_eval_scen_device).
 static int32_t program_eval(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K, const double *d_x, int64_t nt,
-                            double T0, double T1, const double *state0, const double *params, const double *d_data,
-                            double *d_J, double *d_df, double *d_Y) {
+                            double T0, double T1, int64_t S, const double *state0, const double *params,
+                            const double *d_data, double *d_J, double *d_df, double *d_Y) {
   if (!ctx) return MIOC_EINVAL;
   MIOC_JOIN_BT(ctx);
   if (!prog) return fail(ctx, MIOC_EINVAL, "no ODE program");
   if (K < 1 || nt < 1 || K > INT32_MAX || nt > INT32_MAX || !d_x) return fail(ctx, MIOC_EINVAL, "bad K / nt / x");
+  if (S == 0 && prog->scen)
+    return fail(ctx, MIOC_EINVAL, "the program was compiled with scenarios: use mioc_ode_program_eval_scen_device");
+  if (S != 0 && !prog->scen) return fail(ctx, MIOC_EINVAL, "the program was not compiled with scenarios");
+  if (S < 0 || (S > 0 && K % S != 0)) return fail(ctx, MIOC_EINVAL, "need S >= 1 scenarios and K a multiple of S");
   if (!state0 || (prog->np > 0 && !params)) return fail(ctx, MIOC_EINVAL, "state0 / params missing");
   if (!(T1 > T0)) return fail(ctx, MIOC_EINVAL, "need T1 > T0");
   if (prog->nd > 0 && !d_data) return fail(ctx, MIOC_EINVAL, "the program reads sampled data: d_data missing");
@@ -391,16 +417,26 @@ static int32_t program_eval(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, i
   double t0 = T0, tau = (T1 - T0) / (double)nt;  // ODEObjective.jl: tau = (T1 - T0) / nt
   double h = tau / (double)ms;                   // the substep of every scheme but Euler
   double par[kMaxNY + kMaxNP] = {};              // the skeleton's Par: y0[NY], then p[max(NP, 1)]
-  for (int r = 0; r < prog->ny; ++r) par[r] = state0[r];
-  for (int q = 0; q < prog->np; ++q) par[prog->ny + q] = params[q];
+  if (!prog->scen) {
+    for (int r = 0; r < prog->ny; ++r) par[r] = state0[r];
+    for (int q = 0; q < prog->np; ++q) par[prog->ny + q] = params[q];
+  }
   const double *X = d_x;
   double *ST = ctx->d_ode_state.get();
   const int32_t *gate = ctx->gate;
   // the data pointer and the state output follow the gate, each only in a kernel compiled with it
-  void *args_euler[12] = {&Ki, &nti, &t0, &tau, par, &X, &d_J, &d_df, &ST, &gate};
-  void *args_rk[14] = {&Ki, &nti, &ms, &t0, &tau, &h, par, &X, &d_J, &d_df, &ST, &gate};
+  // a scenario program takes S and the two device arrays where the others take Par
+  int Si = (int)S;
+  void *args_euler[14] = {&Ki, &nti, &t0, &tau};
+  void *args_rk[16] = {&Ki, &nti, &ms, &t0, &tau, &h};
   void **args = euler ? args_euler : args_rk;
-  int na = euler ? 10 : 12;
+  int na = euler ? 4 : 6;
+  if (prog->scen) {
+    args[na++] = &Si, args[na++] = &state0, args[na++] = &params;
+  } else {
+    args[na++] = par;
+  }
+  args[na++] = &X, args[na++] = &d_J, args[na++] = &d_df, args[na++] = &ST, args[na++] = &gate;
   if (prog->nd > 0) args[na++] = &d_data;
   if (prog->flags & MIOC_ODE_STATES) args[na++] = &d_Y;
   const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)((K + 63) / 64), 1, 1, 64, 1, 1, 0, ctx->stream, args, nullptr);
@@ -413,7 +449,7 @@ int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int6
                                      double *d_df) {
   if (ctx && prog && prog->nd > 0)
     return fail(ctx, MIOC_EINVAL, "the program reads sampled data: use mioc_ode_program_eval_bolza_device");
-  return program_eval(ctx, prog, 0, K, d_x, nt, T0, T1, state0, params, nullptr, d_J, d_df, nullptr);
+  return program_eval(ctx, prog, 0, K, d_x, nt, T0, T1, 0, state0, params, nullptr, d_J, d_df, nullptr);
 }
 
 int32_t mioc_ode_program_eval_mixed_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K,
@@ -422,14 +458,22 @@ int32_t mioc_ode_program_eval_mixed_device(mioc_ctx *ctx, mioc_ode_program *prog
   if (ctx && nu < 1) return fail(ctx, MIOC_EINVAL, "need 1 <= nu < the program's nx");
   if (ctx && prog && prog->nd > 0)
     return fail(ctx, MIOC_EINVAL, "the program reads sampled data: use mioc_ode_program_eval_bolza_device");
-  return program_eval(ctx, prog, nu, K, d_x, nt, T0, T1, state0, params, nullptr, d_J, d_df, nullptr);
+  return program_eval(ctx, prog, nu, K, d_x, nt, T0, T1, 0, state0, params, nullptr, d_J, d_df, nullptr);
 }
 
 int32_t mioc_ode_program_eval_bolza_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K,
                                            const double *d_x, int64_t nt, double T0, double T1, const double *state0,
                                            const double *params, const double *d_data, double *d_J, double *d_df,
                                            double *d_Y) {
-  return program_eval(ctx, prog, nu, K, d_x, nt, T0, T1, state0, params, d_data, d_J, d_df, d_Y);
+  return program_eval(ctx, prog, nu, K, d_x, nt, T0, T1, 0, state0, params, d_data, d_J, d_df, d_Y);
+}
+
+int32_t mioc_ode_program_eval_scen_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K,
+                                          const double *d_x, int64_t nt, double T0, double T1, int64_t S,
+                                          const double *d_state0, const double *d_params, const double *d_data,
+                                          double *d_J, double *d_df, double *d_Y) {
+  if (ctx && S < 1) return fail(ctx, MIOC_EINVAL, "need S >= 1 scenarios and K a multiple of S");
+  return program_eval(ctx, prog, nu, K, d_x, nt, T0, T1, S, d_state0, d_params, d_data, d_J, d_df, d_Y);
 }
 
 }  // extern "C"

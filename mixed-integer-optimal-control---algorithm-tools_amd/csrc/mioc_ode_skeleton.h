@@ -7,9 +7,10 @@
 // states go to a scratch laid out [step][r][k]: the 64 lanes of a wave store and load 64 contiguous doubles.  Rounding
 // order (no contraction, no fast-math): see the bodies; kBodyEuler's is k_ode_eval's for NY = 2, NX = 3, Gu = 0.
 //
-// A terminal cost, ND columns of sampled data and the state output are compiled in only when the head #defines
-// MIOC_TERMINAL, ND, MIOC_STATES: without them every macro and helper below preprocesses to the tokens of a program
-// that never had them, and the kernel has neither the data nor the state pointer.
+// A terminal cost, ND columns of sampled data, the state output and scenarios are compiled in only when the head
+// #defines MIOC_TERMINAL, ND, MIOC_STATES, MIOC_SCEN (and MIOC_SCEN_DATA): without them every macro and helper below
+// preprocesses to the tokens of a program that never had them, and the kernel has neither the data nor the state
+// pointer and takes state0 and the parameters by value.
 #pragma once
 
 namespace mioc_kernel_text {
@@ -22,21 +23,50 @@ const char *const kSkeletonHead = R"SKEL(
 #ifndef ND
 #define ND 0
 #endif
+// Scenarios (MIOC_SCEN): the lane of restart q solves scenario sc = q % S, with its own state0 and parameters, read from
+// Y0S[r][sc] and PS[e][sc] (the scenario fastest, like ST: 64 lanes load 64 contiguous doubles when S >= 64) in place
+// of the by-value Par.  p is then always the per-lane copy pe.  With MIOC_SCEN_DATA the data rows are DATA[c][e][sc]
+// and each lane loads its own; without it DATA stays the shared [c][e] table and its loads stay scalar.
+#ifdef MIOC_SCEN
+#define MIOC_PAR_ARG int S, const double *__restrict__ Y0S, const double *__restrict__ PS
+#define MIOC_LANE_SCEN const size_t sc = ku % (unsigned)S;
+#define MIOC_Y0(r) Y0S[(size_t)(r) * S + sc]
+#define MIOC_LANE_PARAMS                                                                    \
+  double pe[NP + ND > 0 ? NP + ND : 1];                                                     \
+  _Pragma("unroll") for (int e = 0; e < NP; ++e) pe[e] = PS[(size_t)e * S + sc];            \
+  const double *p = pe;
+#else
+#define MIOC_PAR_ARG mioc_skeleton::Par P
+#define MIOC_LANE_SCEN
+#define MIOC_Y0(r) P.y0[r]
+#endif
 #if ND > 0  // sampled data: p is a per-lane copy of the parameters with the data row of the current column behind them
 #define MIOC_DATA_ARG , const double *__restrict__ DATA
+#ifdef MIOC_SCEN_DATA
+#define MIOC_DATA_ROW(c)                                                  \
+  {                                                                       \
+    const double *row = DATA + (size_t)(c) * ND * S + sc;                 \
+    _Pragma("unroll") for (int e = 0; e < ND; ++e) pe[NP + e] = row[(size_t)e * S]; \
+  }
+#else
 #define MIOC_DATA_ROW(c)                                \
   {                                                     \
     const double *row = DATA + (size_t)(c) * ND;        \
     _Pragma("unroll") for (int e = 0; e < ND; ++e) pe[NP + e] = row[e]; \
   }
+#endif
+#ifndef MIOC_SCEN
 #define MIOC_LANE_PARAMS                                            \
   double pe[NP + ND];                                               \
   _Pragma("unroll") for (int e = 0; e < NP; ++e) pe[e] = P.p[e];    \
   const double *p = pe;
+#endif
 #else
 #define MIOC_DATA_ARG
 #define MIOC_DATA_ROW(c)
+#ifndef MIOC_SCEN
 #define MIOC_LANE_PARAMS const double *p = P.p;
+#endif
 #endif
 #ifdef MIOC_STATES  // YO: the states at the control-grid points, [k][i][r], i = 0..nt
 #define MIOC_STATES_ARG , double *YO
@@ -59,12 +89,13 @@ const char *const kSkeletonHead = R"SKEL(
   const unsigned ku = blockIdx.x * 64u + threadIdx.x;                                                        \
   if (ku >= (unsigned)K) return;                                                                             \
   const size_t k = ku, KK = (size_t)K;                                                                       \
+  MIOC_LANE_SCEN                                                                                             \
   MIOC_LANE_PARAMS                                                                                           \
   const double *x = X + k * (size_t)nt * NX;
 // The signature of every scheme with substeps (ms of them per control interval, of length h); Euler keeps its own.
 #define MIOC_KERNEL_SUBSTEPS                                                                                    \
   extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(                                     \
-      int K, int nt, int ms, double T0, double tau, double h, mioc_skeleton::Par P, const double *X, double *J, \
+      int K, int nt, int ms, double T0, double tau, double h, MIOC_PAR_ARG, const double *X, double *J,         \
       double *DF, double *ST, const int *gate MIOC_DATA_ARG MIOC_STATES_ARG)
 
 namespace mioc_skeleton {
@@ -109,13 +140,13 @@ struct Par {
 // Explicit Euler with the trapezoid cost, the reference's scheme.  Its kernel has no ms and h.
 const char *const kBodyEuler = R"SKEL(
 extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
-    int K, int nt, double T0, double tau, mioc_skeleton::Par P, const double *X, double *J, double *DF, double *ST,
+    int K, int nt, double T0, double tau, MIOC_PAR_ARG, const double *X, double *J, double *DF, double *ST,
     const int *gate MIOC_DATA_ARG MIOC_STATES_ARG) {
   MIOC_LANE_PROLOGUE
   // ---- forward: explicit Euler, trapezoid cost (ODEObjective.jl:125-150) ----
   double y[NY], f[NY], xc[NX], xn[NX];
 #pragma unroll
-  for (int r = 0; r < NY; ++r) y[r] = P.y0[r];
+  for (int r = 0; r < NY; ++r) y[r] = MIOC_Y0(r);
 #pragma unroll
   for (int m = 0; m < NX; ++m) xc[m] = x[m];
   MIOC_DATA_ROW(0)  // the data row is that of the control column: xc's for F, xn's for G, column nt - 1 at the end
@@ -162,7 +193,7 @@ extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(
     const double t = T0 + (double)i * tau;
     if (i == 0) {
 #pragma unroll
-      for (int r = 0; r < NY; ++r) s[r] = P.y0[r];
+      for (int r = 0; r < NY; ++r) s[r] = MIOC_Y0(r);
     } else {
 #pragma unroll
       for (int r = 0; r < NY; ++r) s[r] = ST[((size_t)(i - 1) * NY + r) * KK + k];
@@ -213,7 +244,7 @@ MIOC_KERNEL_SUBSTEPS {
   // ---- forward: y_{n+1} = y_n + sum_s hb_s k_s, the running cost as the quadrature state q ----
   double y[NY], Y[NY], kk[NS][NY], g[NS], xc[NX];
 #pragma unroll
-  for (int r = 0; r < NY; ++r) y[r] = P.y0[r];
+  for (int r = 0; r < NY; ++r) y[r] = MIOC_Y0(r);
   MIOC_YO_OPEN(y)
   double q = 0.0;
   for (int i = 0; i < nt; ++i) {
@@ -366,7 +397,7 @@ MIOC_KERNEL_SUBSTEPS {
   double y[NY], Y[NY], kv[NY], f[NY], d[NY], xc[NX], fy[NY][NY], A[NY][NY];
 #pragma unroll
   for (int r = 0; r < NY; ++r) {
-    y[r] = P.y0[r];
+    y[r] = MIOC_Y0(r);
 #pragma unroll
     for (int c = 0; c < NY; ++c) fy[r][c] = 0.0;  // zeroed once per evaluation, as in the other bodies
   }

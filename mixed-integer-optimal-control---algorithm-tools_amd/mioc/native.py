@@ -41,6 +41,7 @@ MIOC_ODE_INT_BEULER, MIOC_ODE_INT_MIDPOINT = 16, 17  # the implicit schemes star
 MIOC_ODE_NEWTON_MAX, MIOC_ODE_NEWTON_TOL = 12, 1e-10
 MIOC_ODE_DERIVE_FY, MIOC_ODE_DERIVE_FU, MIOC_ODE_DERIVE_GY, MIOC_ODE_DERIVE_GU, MIOC_ODE_DERIVE_ALL = 1, 2, 4, 8, 15
 MIOC_ODE_TERMINAL, MIOC_ODE_STATES, MIOC_ODE_DERIVE_EY = 1, 2, 16  # flags of _create_bolza; the derive bit of Ey
+MIOC_ODE_SCEN, MIOC_ODE_SCEN_DATA = 1, 2  # scen of _create_scen: state0 and params per scenario; the data rows as well
 
 EXPORTED = [
     "mioc_version", "mioc_create", "mioc_destroy", "mioc_last_error", "mioc_set_option", "mioc_set_levels",
@@ -59,6 +60,7 @@ EXPORTED = [
     "mioc_ode_program_create_bolza", "mioc_ode_program_source", "mioc_ode_program_eval_bolza_device",
     "mioc_ode_program_eval_mixed_device", "mioc_rows_copy_device", "mioc_mixed_state_bytes", "mioc_mixed_fan_device",
     "mioc_mixed_select_device", "mioc_mixed_poll",
+    "mioc_ode_program_create_scen", "mioc_ode_program_source_scen", "mioc_ode_program_eval_scen_device",
 ]
 
 MIXED_FAN_TERMS = 2048  # slope terms per LDS chunk of mioc_mixed_fan_device (kMixedChunk)
@@ -153,6 +155,11 @@ def load_library(path=None):
                                                 ctypes.POINTER(vp), ctypes.c_char_p, i64]),
         "mioc_ode_program_source": (i64, [ctypes.c_char_p, i32, i32, i32, i32, i32, i32, i32, i32, i32, ctypes.c_char_p,
                                           i64]),
+        "mioc_ode_program_create_scen": (i32, [ctypes.c_char_p, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                               ctypes.POINTER(vp), ctypes.c_char_p, i64]),
+        "mioc_ode_program_source_scen": (i64, [ctypes.c_char_p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                               ctypes.c_char_p, i64]),
+        "mioc_ode_program_eval_scen_device": (i32, [vp, vp, i64, i64, vp, i64, dbl, dbl, i64, vp, vp, vp, vp, vp, vp]),
         "mioc_ode_program_destroy": (i32, [vp]),
         "mioc_ode_program_eval_bolza_device": (i32, [vp, vp, i64, i64, vp, i64, dbl, dbl, vp, vp, vp, vp, vp, vp]),
         "mioc_ode_program_eval_device": (i32, [vp, vp, i64, vp, i64, dbl, dbl, vp, vp, vp, vp]),
@@ -512,6 +519,45 @@ class Context:
         tensor of a program with sampled data; Y: a (K, nt + 1, ny) float64 CUDA tensor to receive the states at the
         control-grid points (a program compiled with states=True); with either, mioc_ode_program_eval_bolza_device."""
         self._ode_program_eval(prog, None, x, T0, T1, state0, params, J, df, data, Y)
+
+    def ode_program_eval_scen_tensors(self, prog, nu, x, T0, T1, S, state0, params, data=None, J=None, df=None, Y=None):
+        """ode_program_eval_tensors (nu None or 0) / ode_program_eval_mixed_tensors (nu >= 1) for a program compiled
+        with scenarios (include/mioc.h, "Scenarios"): restart k of the K controls x solves scenario k % S.  state0
+        (ny, S), params (nparams, S; None with nparams == 0) and data ((nt, ndata), or (nt, ndata, S) for a program
+        with per-scenario data) are contiguous float64 CUDA tensors, the scenario index fastest; enqueued
+        (mioc_ode_program_eval_scen_device)."""
+        if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
+            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
+        K, nt, nx = x.shape
+        S, scen = int(S), int(getattr(prog, "scenarios", 0))
+        if nx != prog.nx:
+            raise ValueError(f"x has {nx} controls, the program {prog.nx}")
+        if not scen:
+            raise ValueError("the program was not compiled with scenarios")
+        if S < 1 or K % S:
+            raise ValueError(f"the number of controls, {K}, must be a multiple of the {S} scenarios")
+        if nu is not None and (int(nu) != nu or not 0 <= nu < nx):
+            raise ValueError(f"nu must be an integer in 0..{nx - 1}, not {nu!r}")
+        nd = getattr(prog, "ndata", 0)
+        if (state0 is None) or (params is None and prog.nparams) or (data is None and nd):
+            raise ValueError("state0, params or data missing")
+        for name, t, n in (("J", J, K), ("df", df, x.numel()), ("state0", state0, prog.ny * S),
+                           ("params", params, prog.nparams * S),
+                           ("data", data, nt * nd * (S if scen & MIOC_ODE_SCEN_DATA else 1)),
+                           ("Y", Y, K * (nt + 1) * prog.ny)):
+            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or
+                                  t.numel() != n or t.device != x.device):
+                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries on the device of x")
+        if Y is not None and not getattr(prog, "states", False):
+            raise ValueError("the program was not compiled with states=True")
+        if not prog.h:
+            raise ValueError("the ODE program is closed")
+
+        def ptr(t):
+            return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        self._check(self.lib.mioc_ode_program_eval_scen_device(
+            self.h, prog.h, int(nu or 0), K, ptr(x), nt, float(T0), float(T1), S, ptr(state0), ptr(params), ptr(data),
+            ptr(J), ptr(df), ptr(Y)))
 
     # ---- mixed controls: the continuous step beside the DP (include/mioc.h, "Mixed controls") -----------------
     def ode_program_eval_mixed_tensors(self, prog, nu, x, T0, T1, state0, params, J=None, df=None, data=None, Y=None):

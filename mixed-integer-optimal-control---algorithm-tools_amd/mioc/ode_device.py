@@ -16,6 +16,10 @@ hooks"); ``check_hooks`` uses that to tell which hand-written derivative hook is
 cost, sampled data, state output") adds n columns of sampled data behind the parameters (``p[NP + e]``, the row of the
 hook's control column), a terminal cost ``E`` with ``Ey`` (derivable: ``derive`` takes "Ey"), and the states at the
 control-grid points as an output (``DeviceODEProblem.states``).
+``ODEProgram(..., scenarios=True | "data")`` (mioc_ode_program_create_scen; include/mioc.h, "Scenarios") lets the
+restarts of one call solve different problems: ``DeviceODEProblem`` / ``MixedODEProblem`` then take S initial states
+and parameter vectors (with "data" also S data tables), and restart k of ``TRM_batch`` / ``TRM_mixed_batch`` solves
+scenario k % S; ``best_per_scenario`` picks each scenario's best restart.
 
 ``EXAMPLE_SOURCES`` restates the three built-in problems as hook text, term for term as ``Hooks<...>`` of
 csrc/mioc_ode.hip has them, so each reproduces mioc_ode_eval_device bit for bit; they double as templates.  Parameter
@@ -31,7 +35,8 @@ import weakref
 
 from .native import (MIOC_ECOMPILE, MIOC_ODE_DERIVE_EY, MIOC_ODE_DERIVE_FU, MIOC_ODE_DERIVE_FY, MIOC_ODE_DERIVE_GU,
                      MIOC_ODE_DERIVE_GY, MIOC_ODE_INT_BEULER, MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_MIDPOINT,
-                     MIOC_ODE_INT_RK4, MIOC_ODE_STATES, MIOC_ODE_TERMINAL, MIOC_OK, MiocNativeError, load_library)
+                     MIOC_ODE_INT_RK4, MIOC_ODE_SCEN, MIOC_ODE_SCEN_DATA, MIOC_ODE_STATES, MIOC_ODE_TERMINAL, MIOC_OK,
+                     MiocNativeError, load_library)
 
 
 class MiocCompileError(MiocNativeError):
@@ -81,21 +86,39 @@ def derive_names(derive, terminal=False):
     return tuple(n for n in bits if n in names)
 
 
+def scenario_bits(scenarios, ndata=0):
+    """``scenarios`` (False, True or "data") as the scen argument of mioc_ode_program_create_scen."""
+    if scenarios is False or scenarios is None:
+        return 0
+    if scenarios is True:
+        return MIOC_ODE_SCEN
+    if isinstance(scenarios, str) and scenarios == "data":
+        if not ndata:
+            raise ValueError('scenarios="data" needs ndata > 0')
+        return MIOC_ODE_SCEN | MIOC_ODE_SCEN_DATA
+    raise ValueError(f'scenarios must be False, True or "data", not {scenarios!r}')
+
+
 def program_source(source, ny, nx, nparams, integrator="euler", substeps=1, derive=(), ndata=0, terminal=False,
-                   states=False, noinline=False):
-    """The text the library hands to the compiler for ``ODEProgram(source, ny, ...)`` (mioc_ode_program_source), as a
-    str; nothing is compiled.  noinline: the text of the second compile of derived hooks (include/mioc.h)."""
+                   states=False, noinline=False, scenarios=False):
+    """The text the library hands to the compiler for ``ODEProgram(source, ny, ...)`` (mioc_ode_program_source; with
+    ``scenarios`` mioc_ode_program_source_scen), as a str; nothing is compiled.  noinline: the text of the second
+    compile of derived hooks (include/mioc.h)."""
     lib = load_library()
     text = source.encode() if isinstance(source, str) else source
     mask = sum(DERIVE_BITS_TERMINAL[n] for n in derive_names(derive, terminal))
     flags = (MIOC_ODE_TERMINAL if terminal else 0) | (MIOC_ODE_STATES if states else 0)
-    args = (text, int(ny), int(nx), int(nparams), int(ndata), INTEGRATORS[integrator], int(substeps), mask, flags,
-            int(bool(noinline)))
-    need = lib.mioc_ode_program_source(*args, None, 0)
+    scen = scenario_bits(scenarios, ndata)
+    args = (text, int(ny), int(nx), int(nparams), int(ndata), INTEGRATORS[integrator], int(substeps), mask, flags)
+    if scen:
+        entry, args = lib.mioc_ode_program_source_scen, args + (scen, int(bool(noinline)))
+    else:
+        entry, args = lib.mioc_ode_program_source, args + (int(bool(noinline)),)
+    need = entry(*args, None, 0)
     if need < 0:
         raise MiocNativeError(need, "mioc_ode_program_source: bad arguments")
     buf = ctypes.create_string_buffer(need + 1)
-    lib.mioc_ode_program_source(*args, buf, need + 1)
+    entry(*args, buf, need + 1)
     return buf.value.decode()
 
 
@@ -116,17 +139,23 @@ class ODEProgram:
     ``p[NP] .. p[NP + ndata - 1]`` and every evaluation takes ``data``, an (nt, ndata) tensor.  ``terminal``: the text
     also defines the terminal cost ``E(p, t, y)`` and ``Ey`` (or ``derive`` names "Ey"; "all" then includes it).
     ``states``: evaluations can return the states at the control-grid points (``Y``).  All three: include/mioc.h,
-    "Terminal cost, sampled data, state output"; none asked for: the program is what it was without them."""
+    "Terminal cost, sampled data, state output"; none asked for: the program is what it was without them.
+
+    ``scenarios``: True compiles the program for S scenarios per call, each with its own state0 and parameters; "data"
+    (needs ndata > 0) also with its own data table.  Restart k then solves scenario k % S (include/mioc.h,
+    "Scenarios"); such a program is evaluated through a DeviceODEProblem / MixedODEProblem or
+    Context.ode_program_eval_scen_tensors.  ``ODEProgram.scenarios`` is the C entry's scen argument (0, 1 or 3)."""
 
     LOG_CAP = 1 << 16
 
     def __init__(self, source, ny, nx, nparams, integrator="euler", substeps=1, derive=(), ndata=0, terminal=False,
-                 states=False):
+                 states=False, scenarios=False):
         self.h = None
         self.terminal, self.states = bool(terminal), bool(states)
         if int(ndata) != ndata or not 0 <= ndata <= MAX_NDATA:
             raise ValueError(f"ndata must be an integer in 0..{MAX_NDATA}, not {ndata!r}")
         self.ndata = int(ndata)
+        self.scenarios = scenario_bits(scenarios, self.ndata)
         self.derive = derive_names(derive, self.terminal)
         if integrator not in INTEGRATORS:
             raise ValueError(f"integrator must be one of {sorted(INTEGRATORS)}, not {integrator!r}")
@@ -140,7 +169,13 @@ class ODEProgram:
         h = ctypes.c_void_p()
         log = ctypes.create_string_buffer(self.LOG_CAP)
         text = source.encode() if isinstance(source, str) else source
-        if self.ndata or self.terminal or self.states:
+        if self.scenarios:
+            mask = sum(DERIVE_BITS_TERMINAL[n] for n in self.derive)
+            flags = (MIOC_ODE_TERMINAL if self.terminal else 0) | (MIOC_ODE_STATES if self.states else 0)
+            rc = self.lib.mioc_ode_program_create_scen(text, self.ny, self.nx, self.nparams, self.ndata,
+                                                       INTEGRATORS[integrator], self.substeps, mask, flags,
+                                                       self.scenarios, ctypes.byref(h), log, self.LOG_CAP)
+        elif self.ndata or self.terminal or self.states:
             mask = sum(DERIVE_BITS_TERMINAL[n] for n in self.derive)
             flags = (MIOC_ODE_TERMINAL if self.terminal else 0) | (MIOC_ODE_STATES if self.states else 0)
             rc = self.lib.mioc_ode_program_create_bolza(text, self.ny, self.nx, self.nparams, self.ndata,
@@ -170,7 +205,8 @@ class ODEProgram:
     def source_text(self, noinline=False):
         """The text this program was compiled from (mioc_ode_program_source); noinline: that of the second compile."""
         return program_source(self._source, self.ny, self.nx, self.nparams, self.integrator, self.substeps,
-                              self.derive, self.ndata, self.terminal, self.states, noinline)
+                              self.derive, self.ndata, self.terminal, self.states, noinline,
+                              {0: False, MIOC_ODE_SCEN: True}.get(self.scenarios, "data"))
 
     def close(self):
         if self.h:
@@ -198,30 +234,46 @@ class DeviceODEProblem:
     """An ODE-constrained problem for TRM_batch: a compiled ``ODEProgram`` with the data the Julia objective holds --
     the levels V and their iterator (None: the product grid), [T0, T1], the default number of steps nt, state0 and
     the parameters; ``data``: the (nt, ndata) samples of a program with ndata > 0, which fix nt (uploaded once per
-    device and kept)."""
+    device and kept).
+
+    For a program compiled with ``scenarios``, state0 is (ny,) or (S, ny), params (nparams,) or (S, nparams) and, with
+    scenarios="data", data (nt, ndata) or (S, nt, ndata): ``S`` is the common leading size (1 if there is none), an
+    input without it is shared by all scenarios, and restart k of a call solves scenario k % S.  The problem then keeps
+    state0 (S, ny), params (S, nparams) and data as numpy arrays; ``device_layouts()`` are the arrays uploaded."""
 
     def __init__(self, program, V, iterator, T0, T1, nt, state0, params=(), data=None):
         self.program = program
         self.V = [list(v) for v in V]
         self.iterator = iterator
         self.T0, self.T1, self.nt = float(T0), float(T1), int(nt)
-        self.state0 = [float(v) for v in state0]
-        self.params = [float(v) for v in params]
-        if len(self.V) != program.nx or len(self.state0) != program.ny or len(self.params) != program.nparams:
+        if len(self.V) != program.nx:
             raise ValueError("V, state0 and params must match the program's nx, ny and nparams")
-        if not self.T1 > self.T0 or self.nt < 1:
-            raise ValueError("need T1 > T0 and nt >= 1")
-        self.data = _problem_data(program, self.nt, data)
-        self._device_data = {}
+        _problem_inputs(self, state0, params, data, "V, state0 and params must match the program's nx, ny and nparams")
 
     def eval_tensors(self, ctx, x, J=None, df=None):
+        if self._S:
+            return _eval_scenarios(self, ctx, None, x, J, df, None)
         ctx.ode_program_eval_tensors(self.program, x, self.T0, self.T1, self.state0, self.params, J, df,
                                      data=_data_on(self, x))
 
     def states(self, ctx, x):
         """The states (K, nt + 1, ny) of the controls x (K, nt, nx) at the control-grid points t_i = T0 + i tau; row 0
-        is state0.  The program must have been compiled with states=True.  Synchronises the context."""
+        is state0 (with scenarios: that of scenario k % S).  The program must have been compiled with states=True.
+        Synchronises the context."""
         return _states(self, ctx, x, None)
+
+    @property
+    def S(self):
+        """The number of scenarios (1 for a program without them)."""
+        return self._S or 1
+
+    def device_layouts(self):
+        """_device_layouts(self): the numpy arrays a scenario problem uploads."""
+        return _device_layouts(self)
+
+    def check_restarts(self, K):
+        """ValueError unless K restarts divide evenly among the problem's scenarios."""
+        _check_restarts(self, K)
 
 
 class MixedODEProblem:
@@ -238,16 +290,11 @@ class MixedODEProblem:
         self.V = [list(v) for v in V]
         self.iterator = iterator
         self.T0, self.T1, self.nt = float(T0), float(T1), int(nt)
-        self.state0 = [float(v) for v in state0]
-        self.params = [float(v) for v in params]
         if int(nu) != nu or not 1 <= self.nu < program.nx:
             raise ValueError(f"nu must be an integer in 1..{program.nx - 1} (nu = 0: DeviceODEProblem), not {nu!r}")
         if len(self.V) != program.nx - self.nu:
             raise ValueError("V must have one entry per integer control: the program's nx - nu")
-        if len(self.state0) != program.ny or len(self.params) != program.nparams:
-            raise ValueError("state0 and params must match the program's ny and nparams")
-        if not self.T1 > self.T0 or self.nt < 1:
-            raise ValueError("need T1 > T0 and nt >= 1")
+        _problem_inputs(self, state0, params, data, "state0 and params must match the program's ny and nparams")
 
         def bound(b, name):
             b = np.asarray(b, dtype=np.float64)
@@ -257,16 +304,131 @@ class MixedODEProblem:
         self.lo, self.hi = bound(lo, "lo"), bound(hi, "hi")
         if not np.all(self.lo <= self.hi):  # also refuses a NaN bound
             raise ValueError("need lo <= hi everywhere")
-        self.data = _problem_data(program, self.nt, data)
-        self._device_data = {}
 
     def eval_tensors(self, ctx, x, J=None, df=None):
+        if self._S:
+            return _eval_scenarios(self, ctx, self.nu, x, J, df, None)
         ctx.ode_program_eval_mixed_tensors(self.program, self.nu, x, self.T0, self.T1, self.state0, self.params, J, df,
                                            data=_data_on(self, x))
 
     def states(self, ctx, x):
         """DeviceODEProblem.states for a mixed control."""
         return _states(self, ctx, x, self.nu)
+
+    @property
+    def S(self):
+        """The number of scenarios (1 for a program without them)."""
+        return self._S or 1
+
+    def device_layouts(self):
+        """_device_layouts(self): the numpy arrays a scenario problem uploads."""
+        return _device_layouts(self)
+
+    def check_restarts(self, K):
+        """ValueError unless K restarts divide evenly among the problem's scenarios."""
+        _check_restarts(self, K)
+
+
+def _problem_inputs(problem, state0, params, data, mismatch):
+    """state0, params, data and S of a problem: for a program without scenarios the lists and the (nt, ndata) array they
+    always were and S = 0 (``problem.S`` then reads 1); for a scenario program (S, ny), (S, nparams) and (nt, ndata) or
+    (S, nt, ndata) float64 arrays, inputs without the leading size broadcast."""
+    import numpy as np
+    program, nt = problem.program, problem.nt
+    problem._device_data = {}
+    if not getattr(program, "scenarios", 0):
+        try:
+            problem.state0 = [float(v) for v in state0]
+            problem.params = [float(v) for v in params]
+        except TypeError:  # rows where numbers belong: only a scenario program takes (S, ny) and (S, nparams)
+            raise ValueError(mismatch + "; state0 and params per scenario need a program compiled with scenarios")
+        if len(problem.state0) != program.ny or len(problem.params) != program.nparams:
+            raise ValueError(mismatch)
+        if not problem.T1 > problem.T0 or nt < 1:
+            raise ValueError("need T1 > T0 and nt >= 1")
+        problem.data = _problem_data(program, nt, data)
+        problem._S = 0
+        return
+    if not problem.T1 > problem.T0 or nt < 1:
+        raise ValueError("need T1 > T0 and nt >= 1")
+    nd, per_data = program.ndata, bool(program.scenarios & MIOC_ODE_SCEN_DATA)
+    if (data is None) != (nd == 0):
+        raise ValueError(f"the program reads {nd} columns of sampled data: give data of shape (nt, {nd})" if nd else
+                         "the program reads no sampled data")
+    sizes = {}
+
+    def take(name, a, shape, may_lead=True):
+        a = np.array(a, dtype=np.float64, order="C", copy=True)
+        if a.shape == shape:
+            return a
+        if may_lead and a.ndim == len(shape) + 1 and a.shape[1:] == shape and a.shape[0] >= 1:
+            sizes[name] = a.shape[0]
+            return a
+        lead = f" or (S,) + {shape}" if may_lead else ""
+        raise ValueError(f"{name} must have the shape {shape}{lead}, not {a.shape}")
+    y0 = take("state0", state0, (program.ny,))
+    par = take("params", np.zeros(0) if program.nparams == 0 and np.size(params) == 0 and np.ndim(params) < 2
+               else params, (program.nparams,))
+    dat = None if data is None else take("data", data, (nt, nd), per_data)
+    if len(set(sizes.values())) > 1:
+        raise ValueError(f"the numbers of scenarios disagree: {sizes}")
+    S = next(iter(sizes.values()), 1)
+    problem._S = S
+    problem.state0 = np.array(np.broadcast_to(y0, (S, program.ny)), order="C", copy=True)
+    problem.params = np.array(np.broadcast_to(par, (S, program.nparams)), order="C", copy=True)
+    problem.data = dat if dat is None or not per_data else np.array(np.broadcast_to(dat, (S, nt, nd)), order="C",
+                                                                    copy=True)
+
+
+def _device_layouts(problem):
+    """The numpy arrays a scenario problem uploads, the scenario index fastest (include/mioc.h, "Scenarios"):
+    {"state0": (ny, S), "params": (nparams, S), "data": (nt, ndata), (nt, ndata, S) per scenario, or None}."""
+    import numpy as np
+    if not problem._S:
+        raise ValueError("the program was not compiled with scenarios")
+    data = problem.data
+    if data is not None and data.ndim == 3:
+        data = np.ascontiguousarray(data.transpose(1, 2, 0))
+    return {"state0": np.ascontiguousarray(problem.state0.T), "params": np.ascontiguousarray(problem.params.T),
+            "data": data}
+
+
+def _check_restarts(problem, K):
+    if problem._S and (K is None or int(K) < 1 or int(K) % problem._S):
+        raise ValueError(f"K = {K} restarts do not divide among the problem's S = {problem._S} scenarios: K % S != 0")
+
+
+def _scenarios_on(problem, x):
+    """The problem's scenario arrays on the device of x: uploaded at the first use there, then kept."""
+    if x.shape[1] != problem.nt and problem.data is not None:
+        raise ValueError(f"the problem's data fix nt = {problem.nt}; x has {x.shape[1]} steps")
+    key = str(x.device)
+    if key not in problem._device_data:
+        import torch
+        problem._device_data[key] = {n: None if a is None else torch.tensor(a, dtype=torch.float64, device=x.device)
+                                     for n, a in _device_layouts(problem).items()}
+        torch.cuda.current_stream(x.device).synchronize()  # the upload before the context's stream reads it
+    return problem._device_data[key]
+
+
+def _eval_scenarios(problem, ctx, nu, x, J, df, Y):
+    _check_restarts(problem, x.shape[0])
+    d = _scenarios_on(problem, x)
+    ctx.ode_program_eval_scen_tensors(problem.program, nu, x, problem.T0, problem.T1, problem._S, d["state0"],
+                                      d["params"], d["data"], J, df, Y)
+
+
+def best_per_scenario(values, S):
+    """The index of the best restart of each scenario: values (K,) of K = S*m restarts, restart k having solved
+    scenario k % S, gives an (S,) int array whose entry s is the k with the smallest value among k % S == s (the first
+    such k at a tie; a NaN never wins against a number)."""
+    import numpy as np
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    S = int(S)
+    if S < 1 or v.size == 0 or v.size % S:
+        raise ValueError(f"{v.size} values do not divide among {S} scenarios")
+    v = np.where(np.isnan(v), np.inf, v).reshape(-1, S)
+    return np.argmin(v, axis=0) * S + np.arange(S)
 
 
 def _problem_data(program, nt, data):
@@ -303,7 +465,9 @@ def _states(problem, ctx, x, nu):
     Y = torch.empty(x.shape[0], x.shape[1] + 1, prog.ny, dtype=torch.float64, device=x.device)
     torch.cuda.current_stream(x.device).synchronize()
     args = (x, problem.T0, problem.T1, problem.state0, problem.params)
-    if nu is None:
+    if problem._S:
+        _eval_scenarios(problem, ctx, nu, x, None, None, Y)
+    elif nu is None:
         ctx.ode_program_eval_tensors(prog, *args, data=_data_on(problem, x), Y=Y)
     else:
         ctx.ode_program_eval_mixed_tensors(prog, nu, *args, data=_data_on(problem, x), Y=Y)

@@ -66,6 +66,8 @@ def TRM_batch(problem, par, K=None, x0=None, seed=0, nt=None, device=0, log=None
     from .ode_device import DeviceODEProblem
     if isinstance(problem, str) and problem == "convolution":
         problem = ConvProblem(nt=nt or 2048)
+    if isinstance(problem, DeviceODEProblem):  # a scenario problem: restart k solves scenario k % S, so S divides K
+        problem.check_restarts(K if x0 is None else x0.shape[0])
     ctx = Context(device)
     if isinstance(problem, ConvProblem):  # the signal reconstruction objective (example_convolution.jl:128-141)
         cp = problem

@@ -291,6 +291,7 @@ def TRM_mixed_batch(problem, par=None, cpar=None, K=None, x0=None, seed=0, devic
     if x0 is None and K is None:
         raise ValueError("give K restarts or the starts x0")
     mp = problem
+    mp.check_restarts(K if x0 is None else x0.shape[0])  # a scenario problem: restart k solves scenario k % S
     nu, nx, nt = mp.nu, mp.program.nx, mp.nt
     nv = nx - nu
     beta, D0, sigma, kmax, maxiter = par.beta, par.Delta0, par.sigma, par.kmax, par.maxiter
