@@ -142,12 +142,12 @@ int32_t mioc_set_cost(mioc_ctx *ctx, int32_t p_kind, int64_t p_int, double beta,
  *
  * What a failed call leaves behind (mioc_bellman, mioc_bellman_batch_device and mioc_batch_multi alike):
  *   - A call rejected for its arguments (MIOC_EINVAL for nx, K, nt, B or dt, or a NULL pointer) changes nothing:
- *     the previous DP, its inputs and its last backtrack stay valid, and mioc_backtrack*, mioc_pred* and
- *     mioc_get_argmin_table answer from them exactly as before the call.
+ *     the previous DP, its inputs and its last backtrack stay valid, and mioc_backtrack*, mioc_pred*,
+ *     mioc_get_argmin_table and mioc_get_pinf_tables answer from them exactly as before the call.
  *   - A call that fails after that (MIOC_ENONFINITE, MIOC_EINEXACT, a forced algorithm that does not support the
  *     problem: MIOC_EINVAL from the algorithm's own check, MIOC_ENOMEM, MIOC_EHIP) has given up the previous DP
- *     and holds none: mioc_backtrack*, mioc_pred* and mioc_get_argmin_table return MIOC_ESTATE until a bellman
- *     call succeeds.
+ *     and holds none: mioc_backtrack*, mioc_pred*, mioc_get_argmin_table and mioc_get_pinf_tables return
+ *     MIOC_ESTATE until a bellman call succeeds.
  */
 int32_t mioc_bellman(mioc_ctx *ctx, const double *df, const double *u_old, int64_t nx, int64_t nt, int64_t B,
                      double dt);
@@ -722,7 +722,9 @@ void *mioc_stream(mioc_ctx *ctx);
  * Kernel timing (MIOC_OPT_TIMING=1): HIP events recorded on the context's stream around the
  * launches of each kernel class.  which: 0 = dominant DP kernel of the last bellman call (generic
  * step sweep or p=Inf recursion), 2 = p=Inf class-table prep,
- * 1 = backtrack.  Returns cumulative milliseconds, launch count and the kernel's name.
+ * 1 = backtrack.  Returns cumulative milliseconds, launch count and the kernel's name (p=Inf: the name of the
+ * recursion kernel that took the DP in window 0, k_pinf_recur, _xr, _mcw or _ws, and of the class-table kernel in
+ * window 2, k_pinf_prep, k_pinf_prep_m or k_pinf_prep_small).
  */
 int32_t mioc_kernel_stats(mioc_ctx *ctx, int32_t which, double *total_ms, int64_t *launches,
                           const char **name);
@@ -761,6 +763,29 @@ int32_t mioc_diagnostics(mioc_ctx *ctx, int64_t *counters, int32_t n);
  * (B+1) * prod(counts) entries.  The p=Inf collapse stores class tables instead (MIOC_EINVAL).
  */
 int32_t mioc_get_argmin_table(mioc_ctx *ctx, int64_t k, int64_t step, int32_t *U_out);
+
+/*
+ * Test access to the tables of the p=Inf collapse (MIOC_ALGO_PINF), which keeps these instead of U: the device rows of
+ * subproblem k and step i (0 <= i < nt) of the last bellman call, copied out as they are.
+ * With p = Inf the switching weight is 1.0 for every pair (l, j), so K(l, j) = fl(T1(l) + beta) =: K_l does not
+ * depend on j (the terminal step i = nt-1 holds T1 alone, no beta), and with b~_l = sum_m |nu_lm - u_old_m(i)| the
+ * budget class of level l:
+ *   kmin_out  [BWP]  kmin_i[b]: the minimum of K_l over the levels of class b;
+ *   k2_out    [BWP]  the second-smallest distinct value of K_l in class b (+Inf: none);
+ *   kfirst_out[BWP]  the first rank l attaining kmin_i[b] (-1: the class is empty);
+ *                    classes BW..BWP-1 are padding: +Inf, +Inf, -1;
+ *   kabs_out  [1]    max |K_l| over the levels of classes < BW (the walk's rounding bound);
+ *   R_out     [RP]   the row minima R_i[c] = min_l Phi_i[c, l] = min_b fl(kmin_i[b] + R_{i+1}[c - b]),
+ *                    R_{nt-1}[c] = kmin_{nt-1}[c]; +Inf where no level reaches, and in the rows B+1..RP-1;
+ *   sizes_out [3]    BW (classes tracked: the batch's largest b~ within B, plus one), BWP (BW padded to a power of two
+ *                    >= 8), RP (B + 1 rounded up to a multiple of 64).
+ * Every output pointer may be NULL, so a first call can ask for the sizes alone.  A segmented recursion whose hand-off
+ * wait timed out is redone before its tables are read, as for mioc_get_argmin_table.
+ * MIOC_ESTATE without a DP; MIOC_EINVAL after another algorithm, or for k or step out of range; a rejected call changes
+ * nothing.
+ */
+int32_t mioc_get_pinf_tables(mioc_ctx *ctx, int64_t k, int64_t step, double *R_out, double *kmin_out, double *k2_out,
+                             int32_t *kfirst_out, double *kabs_out, int64_t *sizes_out);
 
 #ifdef __cplusplus
 }

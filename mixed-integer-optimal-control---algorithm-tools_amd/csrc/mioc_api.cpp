@@ -510,8 +510,10 @@ int run_pinf(mioc_ctx *ctx, int bmax) {
   pinf_plan((int)RP, (int)nt, D);
   ctx->pinf_CH = D.CH, ctx->pinf_W = D.W;
   ev_begin(ctx, 2, "k_pinf_prep");
-  HIP_TRY(ctx, launch_pinf_prep(ctx->stream, P, Lv, D));
+  const char *prep_variant = "k_pinf_prep";
+  HIP_TRY(ctx, launch_pinf_prep(ctx->stream, P, Lv, D, &prep_variant));
   ev_end(ctx, 2, 1);
+  ctx->stat_name[2] = prep_variant;  // ... and this window after the class-table kernel
   ev_begin(ctx, 0, "k_pinf_recur");
   // row segments on several CUs need their hand-off flags, cleared by validate_inputs (and a timed-out wait redoes
   // the DP in one workgroup)
@@ -1501,6 +1503,34 @@ int32_t mioc_get_argmin_table(mioc_ctx *ctx, int64_t k, int64_t step, int32_t *U
     }
   }
   std::memcpy(U_out, out.data(), out.size() * sizeof(int32_t));
+  return MIOC_OK;
+}
+
+int32_t mioc_get_pinf_tables(mioc_ctx *ctx, int64_t k, int64_t step, double *R_out, double *kmin_out, double *k2_out,
+                             int32_t *kfirst_out, double *kabs_out, int64_t *sizes_out) {
+  if (!ctx) return MIOC_EINVAL;
+  MIOC_JOIN_BT(ctx);
+  if (!ctx->have_dp) return fail(ctx, MIOC_ESTATE, "no bellman result to read");
+  if (ctx->lay.algo != MIOC_ALGO_PINF)
+    return fail(ctx, MIOC_EINVAL, "only the p=Inf collapse keeps per-budget class tables");
+  if (k < 0 || k >= ctx->K || step < 0 || step >= ctx->nt)
+    return fail(ctx, MIOC_EINVAL, "subproblem or step out of range (0 <= step < nt)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  {
+    const int rcr = check_run(ctx);  // a timed-out segmented recursion is redone before its tables are read
+    if (rcr) return rcr;
+  }
+  const size_t RP = (size_t)ctx->RP, BWP = (size_t)ctx->pinf_BWP, row = (size_t)k * ctx->nt + (size_t)step;
+  const mioc_ctx::Slot &q = ctx->cur();
+  if (R_out) HIP_TRY(ctx, hipMemcpy(R_out, q.R.get() + row * RP, RP * sizeof(double), hipMemcpyDeviceToHost));
+  if (kmin_out)
+    HIP_TRY(ctx, hipMemcpy(kmin_out, q.kmin.get() + row * BWP, BWP * sizeof(double), hipMemcpyDeviceToHost));
+  if (k2_out) HIP_TRY(ctx, hipMemcpy(k2_out, q.k2.get() + row * BWP, BWP * sizeof(double), hipMemcpyDeviceToHost));
+  if (kfirst_out)
+    HIP_TRY(ctx, hipMemcpy(kfirst_out, q.kfirst.get() + row * BWP, BWP * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (kabs_out) HIP_TRY(ctx, hipMemcpy(kabs_out, q.kabs.get() + row, sizeof(double), hipMemcpyDeviceToHost));
+  if (sizes_out) sizes_out[0] = ctx->pinf_BW, sizes_out[1] = ctx->pinf_BWP, sizes_out[2] = ctx->RP;
   return MIOC_OK;
 }
 

@@ -273,7 +273,10 @@ struct PinfDev {
 };
 // the walk's chunk and band for a p = Inf problem (mioc_pinf.hip)
 void pinf_plan(int RP, int nt, PinfDev &D);
-hipError_t launch_pinf_prep(hipStream_t s, const ProblemDev &P, const LevelsDev &Lv, const PinfDev &D);
+// variant (nullable): the name of the class-table kernel launched (k_pinf_prep, k_pinf_prep_m or k_pinf_prep_small),
+// which names timing window 2 (mioc_kernel_stats)
+hipError_t launch_pinf_prep(hipStream_t s, const ProblemDev &P, const LevelsDev &Lv, const PinfDev &D,
+                            const char **variant = nullptr);
 // ncu: the device's CUs; flags (K·ceil((B+1)/32) + 1 zeroed words, or null): lets few subproblems run in row segments
 // on several CUs, *segmented then says so (the caller checks the error word after it, check_run)
 // variant (nullable): the name of the recursion kernel launched (k_pinf_recur_mc, k_pinf_recur_xr or k_pinf_recur),

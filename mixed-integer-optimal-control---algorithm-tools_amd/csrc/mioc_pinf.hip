@@ -267,8 +267,11 @@ __global__ __launch_bounds__(256) void k_pinf_prep_small(ProblemDev P, LevelsDev
   }
 }
 
-hipError_t launch_pinf_prep(hipStream_t s, const ProblemDev &P, const LevelsDev &Lv, const PinfDev &D) {
+hipError_t launch_pinf_prep(hipStream_t s, const ProblemDev &P, const LevelsDev &Lv, const PinfDev &D,
+                            const char **variant) {
+  if (variant) *variant = "k_pinf_prep";
   if (Lv.L <= 64 && D.BWP <= 16) {
+    if (variant) *variant = "k_pinf_prep_small";
     const long long n = (long long)P.K * P.nt;
     const dim3 grid((unsigned)((n + 255) / 256));
     if (D.BWP == 8)
@@ -280,6 +283,7 @@ hipError_t launch_pinf_prep(hipStream_t s, const ProblemDev &P, const LevelsDev 
   dim3 grid(P.nt, P.K);
   size_t lds = (size_t)D.BW * 20 + 16;
   if (PINF_PREP_REGS && Lv.L <= 256 * PREP_PR && P.M >= 2 && P.M <= 4) {
+    if (variant) *variant = "k_pinf_prep_m";
     if (P.M == 4)
       hipLaunchKernelGGL(k_pinf_prep_m<4>, grid, dim3(256), lds, s, P, Lv, D);
     else if (P.M == 3)

@@ -6,6 +6,7 @@ visible, every entry point raises ``MiocNativeError``.
 from __future__ import annotations
 
 import atexit
+import collections
 import ctypes
 import math
 import os
@@ -48,7 +49,7 @@ EXPORTED = [
     "mioc_set_cost", "mioc_bellman", "mioc_backtrack", "mioc_bellman_batch_device",
     "mioc_backtrack_batch_device", "mioc_synchronize", "mioc_stream", "mioc_kernel_stats",
     "mioc_reset_stats", "mioc_last_algo", "mioc_last_sdt_driver", "mioc_diagnostics", "mioc_get_argmin_table",
-    "mioc_get_ranks_device",
+    "mioc_get_pinf_tables", "mioc_get_ranks_device",
     "mioc_pred", "mioc_pred_batch_device", "mioc_tv_device", "mioc_trm_decide_device", "mioc_batch_multi",
     "mioc_ode_eval_device", "mioc_rand_start_device", "mioc_backtrack_batch_budgets_device",
     "mioc_heat_setup", "mioc_heat_eval_device", "mioc_heat_eval",
@@ -70,6 +71,11 @@ def mixed_fan_chunk(nu):
     """Slope terms (elements of the continuous rows) that mioc_mixed_fan_device folds per LDS chunk: an even number of
     time steps of nu terms each, at most MIXED_FAN_TERMS."""
     return ((MIXED_FAN_TERMS // int(nu)) & ~1) * int(nu)
+
+
+# one step of the p = Inf collapse's tables (Context.pinf_tables): R (RP,), kmin, k2 (BWP,) float64, kfirst (BWP,)
+# int32, kabs float, and the sizes BW <= BWP, RP
+PinfTables = collections.namedtuple("PinfTables", "R kmin k2 kfirst kabs BW BWP RP")
 
 
 class MiocNativeError(RuntimeError):
@@ -123,6 +129,7 @@ def load_library(path=None):
         "mioc_last_sdt_driver": (i32, [vp]),
         "mioc_diagnostics": (i32, [vp, vp, i32]),
         "mioc_get_argmin_table": (i32, [vp, i64, i64, vp]),
+        "mioc_get_pinf_tables": (i32, [vp, i64, i64, vp, vp, vp, vp, vp, vp]),
         "mioc_get_ranks_device": (i32, [vp, vp]),
         "mioc_pred": (i32, [vp, ctypes.POINTER(dbl), ctypes.POINTER(dbl), ctypes.POINTER(dbl),
                             ctypes.POINTER(dbl)]),
@@ -787,6 +794,20 @@ class Context:
         out = np.empty((lg, self.B + 1), dtype=np.int32)
         self._check(self.lib.mioc_get_argmin_table(self.h, int(k), int(step), _p(out)))
         return out.T
+
+    def pinf_tables(self, step, k=0):
+        """The p=Inf collapse's device rows of step `step` (0 <= step < nt) of subproblem k, as they are
+        (mioc_get_pinf_tables): a PinfTables of R[0..RP), kmin, k2, kfirst[0..BWP), kabs and (BW, BWP, RP)."""
+        sizes = np.zeros(3, dtype=np.int64)
+        self._check(self.lib.mioc_get_pinf_tables(self.h, int(k), int(step), None, None, None, None, None, _p(sizes)))
+        BW, BWP, RP = (int(x) for x in sizes)
+        R = np.empty(RP, dtype=np.float64)
+        kmin, k2 = np.empty(BWP, dtype=np.float64), np.empty(BWP, dtype=np.float64)
+        kfirst = np.empty(BWP, dtype=np.int32)
+        kabs = np.zeros(1, dtype=np.float64)
+        self._check(self.lib.mioc_get_pinf_tables(self.h, int(k), int(step), _p(R), _p(kmin), _p(k2), _p(kfirst),
+                                                  _p(kabs), None))
+        return PinfTables(R, kmin, k2, kfirst, float(kabs[0]), BW, BWP, RP)
 
     def diagnostics(self):
         """[value-collision targets scanned, multi-level targets scanned, p=Inf walk fallbacks or U-table walk
