@@ -181,8 +181,8 @@ hipError_t launch_expand(hipStream_t s, const ProblemDev &P, const LevelsDev &Lv
 // counters (nullable): [3] += seams a wave's list could not hold (an internal-consistency failure, must stay 0)
 // k_pinf_recur_ws's segment flags: this many 32-bit words apart (packed, one line held all 13 segments' flags of
 // C2 / C3; 128 bytes apart the single-subproblem recursion is 2-3 % faster, profiles/round6_flag_stride.txt); the
-// segmented p = Inf kernels' error word sits at K · pinf_recur_segments · this (k_pinf_recur_mc / _mcw keep their
-// flags packed: spaced out, _mcw was 6 % slower)
+// segmented p = Inf kernels' error word sits at K · pinf_recur_segments · this (k_pinf_recur_mcw keeps its
+// flags packed: spaced out, it was 6 % slower)
 #ifndef PINF_WS_FLAG_STRIDE
 #define PINF_WS_FLAG_STRIDE 32
 #endif
@@ -277,13 +277,14 @@ void pinf_plan(int RP, int nt, PinfDev &D);
 // which names timing window 2 (mioc_kernel_stats)
 hipError_t launch_pinf_prep(hipStream_t s, const ProblemDev &P, const LevelsDev &Lv, const PinfDev &D,
                             const char **variant = nullptr);
-// ncu: the device's CUs; flags (K·ceil((B+1)/32) + 1 zeroed words, or null): lets few subproblems run in row segments
-// on several CUs, *segmented then says so (the caller checks the error word after it, check_run)
-// variant (nullable): the name of the recursion kernel launched (k_pinf_recur_mc, k_pinf_recur_xr or k_pinf_recur),
-// which names the timing window (mioc_kernel_stats)
+// ncu: the device's CUs; flags (K·pinf_recur_segments·PINF_WS_FLAG_STRIDE + 1 zeroed words, or null): lets few
+// subproblems run in row segments on several CUs, *segmented then says so (the caller checks the error word, the last
+// of those words, after it: check_run)
+// variant (nullable): the name of the recursion kernel launched (k_pinf_recur_ws, k_pinf_recur_mcw, k_pinf_recur_xr or
+// k_pinf_recur), which names the timing window (mioc_kernel_stats)
 hipError_t launch_pinf_recur(hipStream_t s, const ProblemDev &P, const PinfDev &D, int ncu, int32_t *flags,
                              unsigned spin_limit, bool *segmented, const char **variant = nullptr);
-int pinf_recur_segments(const ProblemDev &P);  // row segments of k_pinf_recur_mc per subproblem (its error word's offset)
+int pinf_recur_segments(const ProblemDev &P);  // 8-row segments of k_pinf_recur_mcw per subproblem (the error word's offset)
 hipError_t launch_pinf_start(hipStream_t s, const ProblemDev &P, const LevelsDev &Lv, const PinfDev &D, int Bu,
                              Start *start, int32_t *zero2 = nullptr, int32_t *fneed = nullptr);
 hipError_t launch_pinf_walk(hipStream_t s, const ProblemDev &P, const LevelsDev &Lv, const PinfDev &D,

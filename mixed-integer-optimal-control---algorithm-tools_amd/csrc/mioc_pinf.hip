@@ -22,39 +22,11 @@
 #include "mioc_internal.h"
 
 namespace mioc {
-#ifndef PINF_RECUR_SPLIT
-#define PINF_RECUR_SPLIT 1  // few subproblems: G lanes per row pair (A/B builds: 0)
-#endif
-#ifndef PINF_RECUR_MC
-#define PINF_RECUR_MC 1     // few subproblems: row segments on several CUs (k_pinf_recur_mc)
-#endif
-#ifndef PINF_MC_CHUNK
-#define PINF_MC_CHUNK 64       // k_pinf_recur_mc: steps per segment hand-off (C4, 8-row segments: 16: 23.3 ms, 32: 19.9 ms, 64: 19.6 ms)
-#endif
-#ifndef PINF_RECUR_MC_LANES
-#define PINF_RECUR_MC_LANES 8  // k_pinf_recur_mc: lanes per budget row (8: 8 rows per segment; 16: 4 rows, 8 % slower at C4; 4: 16 rows, 11 % slower with the one-step loop; 2: 32)
-#endif
-#ifndef PINF_MC_SPLIT
-#define PINF_MC_SPLIT 1  // k_pinf_recur_mc, 8 lanes per row: classes >= 8 (rows below the segment) off the step chain
-#endif
-#ifndef PINF_MC_HELPERS
-#define PINF_MC_HELPERS 1  // k_pinf_recur_mcw: the off-chain minima of a chunk by three helper waves (A/B builds: 0)
-#endif
-#ifndef PINF_RECUR_XR
-#define PINF_RECUR_XR 1     // C4's B = 256: eight waves and the extra row split by classes (k_pinf_recur_xr)
-#endif
-#ifndef PINF_PREP_REGS
-#define PINF_PREP_REGS 1    // class tables: M a template constant, a thread's levels in registers (A/B builds: 0)
-#endif
-#ifndef PINF_RECUR_G
-#define PINF_RECUR_G 4      // lanes per row pair when split (2 or 4)
-#endif
-#ifndef PINF_RECUR_WS
-#define PINF_RECUR_WS 1     // few subproblems, classes <= 8: 64-row segments, the chain by DPP wave shifts (k_pinf_recur_ws)
-#endif
-#ifndef PINF_WS_CHUNK
-#define PINF_WS_CHUNK 64    // k_pinf_recur_ws: steps per segment hand-off
-#endif
+constexpr int PINF_MC_CHUNK = 64;  // k_pinf_recur_mcw: steps per segment hand-off (C4, 8-row segments: 16: 23.3 ms, 32: 19.9 ms, 64: 19.6 ms)
+constexpr int PINF_WS_CHUNK = 64;  // k_pinf_recur_ws: steps per segment hand-off
+// k_pinf_recur_mcw: rows per segment, eight lanes per budget row (16 lanes, 4 rows: 8 % slower at C4; 4 lanes, 16 rows:
+// 11 % slower)
+constexpr int kPinfMcRows = 8;
 
 __device__ __forceinline__ double p_t1(const double *nuv, const double *dfi, int M, double dt) {
   double t = 0.0;
@@ -282,7 +254,7 @@ hipError_t launch_pinf_prep(hipStream_t s, const ProblemDev &P, const LevelsDev 
   }
   dim3 grid(P.nt, P.K);
   size_t lds = (size_t)D.BW * 20 + 16;
-  if (PINF_PREP_REGS && Lv.L <= 256 * PREP_PR && P.M >= 2 && P.M <= 4) {
+  if (Lv.L <= 256 * PREP_PR && P.M >= 2 && P.M <= 4) {
     if (variant) *variant = "k_pinf_prep_m";
     if (P.M == 4)
       hipLaunchKernelGGL(k_pinf_prep_m<4>, grid, dim3(256), lds, s, P, Lv, D);
@@ -316,34 +288,42 @@ __device__ __forceinline__ const void *pi_uniform(const void *p) {
   return (const void *)(((unsigned long long)hi << 32) | lo);
 }
 typedef unsigned int pi_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned lds_addr(const void *p) {  // an LDS pointer's byte address
+  return (unsigned)(uintptr_t)((__attribute__((address_space(3))) const char *)p);
+}
 
-// glds_copy as inline asm (M0 saved and restored): the compiler does not see these LDS writes, so it does not make
-// every later LDS read wait for ALL outstanding vector-memory operations (the recursions' streamed R stores among
-// them: a store round trip per step); the callers complete them explicitly (vm_drain, then a barrier or, in one
-// wave, program order) before the first read of the copy
+// One LDS-DMA instruction as inline asm (M0 saved and restored): active lane l's 16 bytes at gbase + voff land at LDS
+// byte lds + 16·l.  lds is wave-uniform, gbase a uniform pointer (pi_uniform).  SC1: the bytes come from the agent's
+// coherent level (rows another workgroup stored).  As inline asm the compiler does not see these LDS writes, so it
+// does not make every later LDS read wait for ALL outstanding vector-memory operations (the recursions' streamed R
+// stores among them: a store round trip per step); the callers complete them explicitly (vm_drain or a counted wait,
+// then a barrier or, in one wave, program order) before the first read of the copy
+template <bool SC1>
+__device__ __forceinline__ void glds_dma16(unsigned lds, const void *gbase, unsigned voff) {
+  const unsigned m0 = __builtin_amdgcn_readfirstlane(lds);
+  unsigned keep;
+  if constexpr (SC1)
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 sc1\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(gbase), "s"(m0)
+                 : "memory");
+  else
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(gbase), "s"(m0)
+                 : "memory");
+}
+// glds_copy by glds_dma16
 __device__ __forceinline__ void glds_copy_asm(const void *gsrc_, void *ldst, int bytes, int tid, int nthreads) {
   const int wave = tid >> 6, lane = tid & 63, nw = (nthreads + 63) >> 6;
   const void *gsrc = pi_uniform(gsrc_);
-  const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)ldst);
+  const unsigned lds0 = lds_addr(ldst);
   for (int off = wave * 1024; off < bytes; off += nw * 1024) {
-    if (off + lane * 16 < bytes) {
-      const unsigned m0 = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)off), voff = (unsigned)(off + lane * 16);
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep)
-                   : "v"(voff), "s"(gsrc), "s"(m0)
-                   : "memory");
-    }
+    if (off + lane * 16 < bytes) glds_dma16<false>(lds0 + (unsigned)off, gsrc, (unsigned)(off + lane * 16));
   }
 }
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ double dpp_swap_pair(double x) {  // value of lane ^ 1 (quad_perm [1,0,3,2])
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), 0xB1, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), 0xB1, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
 
 // v_min_f64 without llvm.minnum's operand canonicalisation (inputs are finite or +Inf, never NaN)
 __device__ __forceinline__ double pvmin(double a, double b) {
@@ -380,29 +360,86 @@ __device__ unsigned long long g_pinf_stamps[16][8];
 #define PI_T(v)
 #endif
 
+// The pieces k_pinf_recur and k_pinf_recur_xr share (one workgroup per subproblem, A: [2 parities][AW = RP + BWP]).
+// The terminal row R_{n-1}[c] = Kmin_{n-1}[c] (class minima of T1, no β; kt = Kmin_{n-1}) into R (Rt = R_{n-1}) and
+// into its parity pt of A; every other entry of A (the other parity, the padding in front, rows >= BWP) +Inf
+template <int BWP>
+__device__ __forceinline__ void recur_terminal_row(double *A, int pt, const double *kt, double *Rt, int RP, int B) {
+  const int AW = RP + BWP;
+  for (int q = (int)threadIdx.x; q < 2 * AW; q += (int)blockDim.x) {
+    const int par = q / AW, kk = q % AW, c = kk + 1 - BWP;
+    double v = INFINITY;
+    if (par == pt && c >= 0 && c < BWP) v = kt[c];
+    A[q] = v;
+    if (par == pt && c >= 0 && c < RP) Rt[c] = c <= B ? v : INFINITY;
+  }
+}
+// A row pair's step in two halves (k_pinf_recur's diagnostic stamps, and k_pinf_recur_xr's extra row, sit between).
+// The reads: lane h of the pair's group takes classes b = h·CB + bb (CB = BWP / G).  Row c0 reads R_{i+1}[c0 - b] =
+// Ain[c0 + BWP - 1 - b], a window of CB + 1 values from Ain[c0 + BWP - (h + 1)·CB] (even: 16-byte aligned), so
+//   row c0: R_{i+1}[c0 - b] = w[CB - 1 - bb];   row c0 + 1: R_{i+1}[c0 + 1 - b] = w[CB - bb]
+// Ain is R_{i+1}'s parity of A, Krow the staged class row Kmin_i
+template <int BWP, int G>
+__device__ __forceinline__ void recur_pair_reads(const double *Ain, const double *Krow, int c0, int h,
+                                                 double (&w)[2 * (BWP / G / 2 + 1)], double (&kv)[BWP / G]) {
+  constexpr int CB = BWP / G, NP = CB / 2 + 1;  // classes per lane, 16-byte pieces of its window
+  const double2 *win = reinterpret_cast<const double2 *>(Ain + c0 + BWP - (h + 1) * CB);
+  const double2 *kr = reinterpret_cast<const double2 *>(Krow + h * CB);
+#pragma unroll
+  for (int p2 = 0; p2 < NP; ++p2) {
+    const double2 x = win[p2];
+    w[2 * p2] = x.x;
+    w[2 * p2 + 1] = x.y;
+  }
+#pragma unroll
+  for (int p2 = 0; p2 < CB / 2; ++p2) {
+    const double2 y = kr[p2];
+    kv[2 * p2] = y.x;
+    kv[2 * p2 + 1] = y.y;
+  }
+}
+// The minima: four accumulators per row, each started by its first candidate, then the class parts of the lane group
+// by DPP (quad_perm xor 1, then xor 2); every lane of the group ends with R_i[c0] in r0 and R_i[c0 + 1] in r1
+template <int BWP, int G>
+__device__ __forceinline__ void recur_pair_min(const double (&w)[2 * (BWP / G / 2 + 1)], const double (&kv)[BWP / G],
+                                               double &r0, double &r1) {
+  constexpr int CB = BWP / G;
+  double m0[4], m1[4];
+#pragma unroll
+  for (int b2 = 0; b2 < CB; ++b2) {
+    const double c0 = kv[b2] + w[CB - 1 - b2], c1 = kv[b2] + w[CB - b2];
+    m0[b2 & 3] = b2 < 4 ? c0 : pvmin(m0[b2 & 3], c0);
+    m1[b2 & 3] = b2 < 4 ? c1 : pvmin(m1[b2 & 3], c1);
+  }
+  if constexpr (CB >= 4) {
+    r0 = pvmin(pvmin(m0[0], m0[1]), pvmin(m0[2], m0[3]));
+    r1 = pvmin(pvmin(m1[0], m1[1]), pvmin(m1[2], m1[3]));
+  } else {
+    r0 = pvmin(m0[0], m0[1]);
+    r1 = pvmin(m1[0], m1[1]);
+  }
+  if constexpr (G == 4) {
+    r0 = pvmin(r0, pv_dpp<0xB1>(r0));
+    r1 = pvmin(r1, pv_dpp<0xB1>(r1));
+    r0 = pvmin(r0, pv_dpp<0x4E>(r0));
+    r1 = pvmin(r1, pv_dpp<0x4E>(r1));
+  }
+}
+
 template <int BWP, int G>
 __global__ __launch_bounds__(G == 1 ? 512 : 1024) void k_pinf_recur(ProblemDev P, PinfDev D, int CH) {
   if (redo_skip(P)) return;
   extern __shared__ __attribute__((aligned(16))) double sm[];
   constexpr int CB = BWP / G;     // classes per lane
   constexpr int NP = CB / 2 + 1;  // 16-byte pieces of a lane's window
-  static_assert(G == 1 || ((G == 2 || G == 4) && CB % 2 == 0), "k_pinf_recur: G = 1, 2 or 4");
+  static_assert(G == 1 || (G == 4 && CB % 2 == 0), "k_pinf_recur: G = 1 or 4");
   const int RP = P.RP, B = P.B, nt = P.nt, k = blockIdx.x, nthr = blockDim.x / G;
   const int tid = (int)threadIdx.x / G, h = (int)threadIdx.x % G;  // row pair slot, class quarter
   const int AW = RP + BWP;                     // even: RP is a multiple of 64
   double *A = sm, *Kbuf = sm + 2 * AW;         // A: [2 parities][AW]; Kbuf: [2][CH][BWP]
   const double *kmin = D.kmin + (size_t)k * nt * BWP;
   double *R = D.R + (size_t)k * nt * RP;
-  {
-    const int pt = (nt - 1) & 1;  // terminal row R_{n-1}[c] = Kmin_{n-1}[c] (class minima of T1, no β)
-    for (int q = (int)threadIdx.x; q < 2 * AW; q += (int)blockDim.x) {
-      const int par = q / AW, kk = q % AW, c = kk + 1 - BWP;
-      double v = INFINITY;
-      if (par == pt && c >= 0 && c < BWP) v = kmin[(size_t)(nt - 1) * BWP + c];
-      A[q] = v;
-      if (par == pt && c >= 0 && c < RP) R[(size_t)(nt - 1) * RP + c] = c <= B ? v : INFINITY;
-    }
-  }
+  recur_terminal_row<BWP>(A, (nt - 1) & 1, kmin + (size_t)(nt - 1) * BWP, R + (size_t)(nt - 1) * RP, RP, B);
   if (nt < 2) return;
   int hi = nt - 2, lo = hi - CH + 1 < 0 ? 0 : hi - CH + 1;
   glds_copy_asm(kmin + (size_t)lo * BWP, Kbuf, (hi - lo + 1) * BWP * 8, (int)threadIdx.x, (int)blockDim.x);
@@ -417,53 +454,14 @@ __global__ __launch_bounds__(G == 1 ? 512 : 1024) void k_pinf_recur(ProblemDev P
     for (int i = hi; i >= lo; --i) {
       PI_T(t0);
       for (int c0 = 2 * tid; c0 < RP; c0 += 2 * nthr) {
-        // this lane's classes b = h·CB + bb: row 2t reads R_{i+1}[c0 - b] = A[c0 + BWP - 1 - b], a window of CB + 1
-        // values from A[c0 + BWP - (h + 1)·CB] (even: 16-byte aligned)
-        const double2 *win = reinterpret_cast<const double2 *>(A + (size_t)((i + 1) & 1) * AW + c0 + BWP - (h + 1) * CB);
-        const double2 *kr = reinterpret_cast<const double2 *>(Kc + (size_t)(i - lo) * BWP + h * CB);
-        double w[2 * NP], kv[CB];
-#pragma unroll
-        for (int p2 = 0; p2 < NP; ++p2) {
-          const double2 x = win[p2];
-          w[2 * p2] = x.x;
-          w[2 * p2 + 1] = x.y;
-        }
-#pragma unroll
-        for (int p2 = 0; p2 < CB / 2; ++p2) {
-          const double2 y = kr[p2];
-          kv[2 * p2] = y.x;
-          kv[2 * p2 + 1] = y.y;
-        }
+        double w[2 * NP], kv[CB], r0, r1;
+        recur_pair_reads<BWP, G>(A + (size_t)((i + 1) & 1) * AW, Kc + (size_t)(i - lo) * BWP, c0, h, w, kv);
 #ifdef MIOC_STAMPS
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         PI_T(t1);
         if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && c0 == 2 * tid) g_pinf_stamps[threadIdx.x >> 6][0] += t1 - t0;
 #endif
-        // row 2t:   R_{i+1}[2t - b]   = w[CB - 1 - bb];   row 2t+1: R_{i+1}[2t + 1 - b] = w[CB - bb]
-        // four accumulators per row, each started by its first candidate
-        double m0[4], m1[4];
-#pragma unroll
-        for (int b2 = 0; b2 < CB; ++b2) {
-          const double c0 = kv[b2] + w[CB - 1 - b2], c1 = kv[b2] + w[CB - b2];
-          m0[b2 & 3] = b2 < 4 ? c0 : pvmin(m0[b2 & 3], c0);
-          m1[b2 & 3] = b2 < 4 ? c1 : pvmin(m1[b2 & 3], c1);
-        }
-        double r0, r1;
-        if constexpr (CB >= 4) {
-          r0 = pvmin(pvmin(m0[0], m0[1]), pvmin(m0[2], m0[3]));
-          r1 = pvmin(pvmin(m1[0], m1[1]), pvmin(m1[2], m1[3]));
-        } else {
-          r0 = pvmin(m0[0], m0[1]);
-          r1 = pvmin(m1[0], m1[1]);
-        }
-        if constexpr (G >= 2) {  // the class parts of the lane group (quad_perm xor 1, then xor 2)
-          r0 = pvmin(r0, pv_dpp<0xB1>(r0));
-          r1 = pvmin(r1, pv_dpp<0xB1>(r1));
-        }
-        if constexpr (G == 4) {
-          r0 = pvmin(r0, pv_dpp<0x4E>(r0));
-          r1 = pvmin(r1, pv_dpp<0x4E>(r1));
-        }
+        recur_pair_min<BWP, G>(w, kv, r0, r1);
         double *Aout = A + (size_t)(i & 1) * AW;
         if (G == 1 || h == 0) {
           Aout[c0 + BWP - 1] = r0;
@@ -512,16 +510,7 @@ __global__ __launch_bounds__(NW * 64) void k_pinf_recur_xr(ProblemDev P, PinfDev
   const double *kmin = D.kmin + (size_t)k * nt * BWP;
   double *R = D.R + (size_t)k * nt * RP;
   const int c0 = 2 * tid;
-  {
-    const int pt = (nt - 1) & 1;
-    for (int q = (int)threadIdx.x; q < 2 * AW; q += (int)blockDim.x) {
-      const int par = q / AW, kk = q % AW, c = kk + 1 - BWP;
-      double v = INFINITY;
-      if (par == pt && c >= 0 && c < BWP) v = kmin[(size_t)(nt - 1) * BWP + c];
-      A[q] = v;
-      if (par == pt && c >= 0 && c < RP) R[(size_t)(nt - 1) * RP + c] = c <= B ? v : INFINITY;
-    }
-  }
+  recur_terminal_row<BWP>(A, (nt - 1) & 1, kmin + (size_t)(nt - 1) * BWP, R + (size_t)(nt - 1) * RP, RP, B);
   if (nt < 2) return;
   // R_{i+1}[E] for wave 0's classes (b = 0 reads row E itself): the terminal value first
   double rE = E < BWP ? kmin[(size_t)(nt - 1) * BWP + E] : INFINITY;
@@ -546,21 +535,8 @@ __global__ __launch_bounds__(NW * 64) void k_pinf_recur_xr(ProblemDev P, PinfDev
         rE = m;
         if (lane == 0) R[(size_t)(i + 1) * RP + E] = E <= B ? m : INFINITY;
       }
-      const double2 *win = reinterpret_cast<const double2 *>(Ain + c0 + BWP - (h + 1) * CB);
-      const double2 *kr = reinterpret_cast<const double2 *>(Kc + (size_t)(i - lo) * BWP + h * CB);
-      double wv[2 * NP], kv[CB];
-#pragma unroll
-      for (int p2 = 0; p2 < NP; ++p2) {
-        const double2 x = win[p2];
-        wv[2 * p2] = x.x;
-        wv[2 * p2 + 1] = x.y;
-      }
-#pragma unroll
-      for (int p2 = 0; p2 < CB / 2; ++p2) {
-        const double2 y = kr[p2];
-        kv[2 * p2] = y.x;
-        kv[2 * p2 + 1] = y.y;
-      }
+      double wv[2 * NP], kv[CB], r0, r1;
+      recur_pair_reads<BWP, G>(Ain, Kc + (size_t)(i - lo) * BWP, c0, h, wv, kv);
       // row E, classes [w·CW, (w+1)·CW): R_{i+1}[E - b] (row E itself from rE)
       double pe = INFINITY;
       {
@@ -572,18 +548,7 @@ __global__ __launch_bounds__(NW * 64) void k_pinf_recur_xr(ProblemDev P, PinfDev
           pe = pvmin(pe, ke[bb] + rv);
         }
       }
-      double m0[4] = {INFINITY, INFINITY, INFINITY, INFINITY}, m1[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
-#pragma unroll
-      for (int b2 = 0; b2 < CB; ++b2) {
-        m0[b2 & 3] = pvmin(m0[b2 & 3], kv[b2] + wv[CB - 1 - b2]);
-        m1[b2 & 3] = pvmin(m1[b2 & 3], kv[b2] + wv[CB - b2]);
-      }
-      double r0 = pvmin(pvmin(m0[0], m0[1]), pvmin(m0[2], m0[3]));
-      double r1 = pvmin(pvmin(m1[0], m1[1]), pvmin(m1[2], m1[3]));
-      r0 = pvmin(r0, pv_dpp<0xB1>(r0));
-      r1 = pvmin(r1, pv_dpp<0xB1>(r1));
-      r0 = pvmin(r0, pv_dpp<0x4E>(r0));
-      r1 = pvmin(r1, pv_dpp<0x4E>(r1));
+      recur_pair_min<BWP, G>(wv, kv, r0, r1);
       double *Aout = A + (size_t)(i & 1) * AW;
       if (h == 0) {
         Aout[c0 + BWP - 1] = r0;
@@ -609,230 +574,60 @@ __global__ __launch_bounds__(NW * 64) void k_pinf_recur_xr(ProblemDev P, PinfDev
   }
 }
 
-// Row segments on several CUs (few subproblems, classes <= 32): R_i[c] needs R_{i+1}[c - b] for b < BWP <= 32, i.e.
-// rows c-31 .. c only, so rows split into segments of 32 (one wave, one workgroup each: lane pair per row, each lane
-// half the classes) form a pipeline like k_sdt_run's: segment q runs a step once segment q-1 has published that
-// step's rows below it.  Segments hand over in chunks of CH steps: q-1 stores its rows of R (sc1 buffer stores, the
-// R array the walk reads anyway), drains, and publishes the chunk's last step (relaxed agent flag); q polls that flag
-// one chunk ahead and copies the 32 rows below its own for the next chunk's steps into its LDS ring by LDS-DMA (sc1),
-// then computes the chunk with no further waits (MI355X_MICROARCH.md, the measured-valid hand-off).  A wave needs no
-// barrier: its LDS accesses execute in order.  Every candidate is the same expression and min is exact, so R is
-// bit-identical to k_pinf_recur's.  A wait past the spin limit sets the error word and the host redoes the DP with
-// the one-workgroup kernel (check_run).
-template <int BWP, int LPR>
-__global__ __launch_bounds__(64) void k_pinf_recur_mc(ProblemDev P, PinfDev D, int nseg, int32_t *flags,
-                                                      unsigned spin_limit) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  constexpr int CB = BWP / LPR;      // classes per lane
-  constexpr int RPS = 64 / LPR;      // rows per segment (one wave)
-  constexpr int AS = 32 + RPS;       // step array: the 32 rows below the segment, then its own
-  constexpr int CH = PINF_MC_CHUNK;  // steps per hand-off
-  static_assert(BWP >= 8 && BWP <= 32 && CB >= 2 && CB % 2 == 0 && (LPR == 2 || LPR == 4 || LPR == 8 || LPR == 16),
-                "k_pinf_recur_mc shape");
-  const int RP = P.RP, B = P.B, nt = P.nt, K = P.K;
-  const int k = (int)blockIdx.x / nseg, q = (int)blockIdx.x - k * nseg;
-  const int lane = (int)threadIdx.x, r = lane / LPR, h = lane % LPR, c = RPS * q + r, u = r + 32;
-  constexpr int NS = 2 * CH;                     // ring of step arrays
-  double *A = sm, *Kbuf = sm + (size_t)NS * AS;  // Kbuf: [2][CH][BWP]
-  const double *kmin = D.kmin + (size_t)k * nt * BWP;
-  double *R = D.R + (size_t)k * nt * RP;
-  // segments' flags packed; the error word where every segmented p = Inf kernel keeps it
-  constexpr int FS = 1;
-  int32_t *done = flags + (size_t)k * nseg * FS, *err = flags + (size_t)K * nseg * PINF_WS_FLAG_STRIDE;
-  const __amdgpu_buffer_rsrc_t Rr = __builtin_amdgcn_make_buffer_rsrc(R, 0, (int)((size_t)nt * RP * 8), 0x00020000);
-  auto slot = [&](int s) { return A + (size_t)(s % NS) * AS; };
-  // terminal row R_{n-1}[c'] = Kmin_{n-1}[c'] (c' < BWP), the rows below included (a function of kmin: no hand-off)
-  for (int e = lane; e < NS * AS; e += 64) A[e] = INFINITY;
-  for (int e = lane; e < AS; e += 64) {
-    const int cc = RPS * q - 32 + e;
-    slot(nt - 1)[e] = cc >= 0 && cc < BWP ? kmin[(size_t)(nt - 1) * BWP + cc] : INFINITY;
+// ---------------------------------------------------------------------------------------------
+// The hand-off between row segments on different CUs (k_pinf_recur_mcw, k_pinf_recur_ws).  A segment stores its rows
+// of R with sc1 buffer stores (the R array the walk reads anyway), waits until they have landed (vm_drain, or a counted
+// wait that covers them) and publishes the token nt-1-s of the last step s they cover: a relaxed agent-scope store to
+// its `done` word.  The segment above polls that word for the token it needs, then copies the rows below its own out
+// of R into its LDS by LDS-DMA (sc1), a whole chunk of steps at a time, and computes the chunk with no further waits
+// (MI355X_MICROARCH.md, the measured-valid hand-off).  A wait past the spin limit sets the error word, which stops
+// every other segment's wait too, and the host redoes the DP with the one-workgroup kernel (check_run).
+// ---------------------------------------------------------------------------------------------
+// wait until *done >= need; false (the error word set) once the error word is set or after spin_limit polls
+__device__ __forceinline__ bool pinf_wait_token(int32_t *done, int need, int32_t *err, unsigned spin_limit) {
+  unsigned spins = 0;
+  while (__hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
+    if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || ++spins > spin_limit) {
+      __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return false;
+    }
+    __builtin_amdgcn_s_sleep(2);
   }
-  if (h == 0) R[(size_t)(nt - 1) * RP + c] = c <= B && c < BWP ? kmin[(size_t)(nt - 1) * BWP + c] : INFINITY;
-  if (nt < 2) return;
-  bool stop = false;
-  // the segments whose rows lie within 32 below this one (q-1, and q-2 for 16-row segments) have published step s
-  // (token nt-1-s); false past the spin limit (err set)
-  auto wait_below = [&](int s) {
-    const int need = nt - 1 - s;
-    for (int d = 1; d * RPS <= 32 && q - d >= 0; ++d) {
-      unsigned spins = 0;
-      while (__hip_atomic_load(done + (q - d) * FS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-        if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || ++spins > spin_limit) {
-          __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          return false;
-        }
-        __builtin_amdgcn_s_sleep(2);
-      }
-    }
-    return true;
-  };
-  // the 32 rows below the segment (R_s[RPS·q-32 .. RPS·q-1], rows < 0 stay +Inf) for steps s in [s0, s1] into their
-  // ring slots: lane l moves rows RPS·q-32+2l, +1 (16 bytes, LDS-DMA, sc1)
-  auto halo = [&](int s0, int s1) {
-    if (q == 0) return;
-    const int row = RPS * q - 32 + 2 * lane;
-    for (int s = s0; s <= s1; ++s) {
-      if (lane < 16 && row >= 0) {
-        const void *g = pi_uniform(R + (size_t)s * RP);
-        const unsigned m0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)slot(s)));
-        const unsigned voff = 8u * (unsigned)row;
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 sc1\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(voff), "s"(g), "s"(m0)
-                     : "memory");
-      }
-    }
-  };
-  int hi = nt - 2, lo = hi - CH + 1 < 0 ? 0 : hi - CH + 1;
-  glds_copy_asm(kmin + (size_t)lo * BWP, Kbuf, (hi - lo + 1) * BWP * 8, lane, 64);
-  if (lo + 1 <= nt - 2) {  // the first chunk's rows below (step nt-1's are computed above)
-    stop = !wait_below(lo + 1);
-    halo(lo + 1, nt - 2);
-  }
-  vm_drain();
-  for (int qq = 0; hi >= 0 && !stop; ++qq) {
-    const double *Kc = Kbuf + (size_t)(qq & 1) * CH * BWP;
-    const int nhi = lo - 1, nlo = nhi - CH + 1 < 0 ? 0 : nhi - CH + 1;
-    if (nhi >= 0) {  // the next chunk: its class rows, and (once the segments below have them) its rows below
-      glds_copy_asm(kmin + (size_t)nlo * BWP, Kbuf + (size_t)((qq + 1) & 1) * CH * BWP, (nhi - nlo + 1) * BWP * 8, lane, 64);
-      if (!wait_below(nlo + 1)) {
-        stop = true;
-        break;
-      }
-      halo(nlo + 1, nhi + 1);
-    }
-    // this lane's class values of a step (read one step ahead: they are not on the recursion's chain)
-    auto kload = [&](double (&kv)[CB], int i) {
-      const double2 *kr = reinterpret_cast<const double2 *>(Kc + (size_t)(i - lo) * BWP + CB * h);
-#pragma unroll
-      for (int t = 0; t < CB / 2; ++t) {
-        const double2 y = kr[t];
-        kv[2 * t] = y.x;
-        kv[2 * t + 1] = y.y;
-      }
-    };
-    // one step: the class values kv of step i (loaded a step earlier), kn <- those of step i-1
-    auto step = [&](int i, const double (&kv)[CB], double (&kn)[CB]) {
-      asm volatile("" ::: "memory");
-      if (i > lo) kload(kn, i - 1);
-      const double *Ain = slot(i + 1) + u - CB * h - (CB - 1);  // R_{i+1}[c - CB·h - (CB-1) .. c - CB·h]
-      double wv[CB];
-#pragma unroll
-      for (int t = 0; t < CB; ++t) wv[t] = Ain[t];
-      double m[4];  // four accumulators, each started by its first candidate
-#pragma unroll
-      for (int bb = 0; bb < CB; ++bb) {
-        const double cand = kv[bb] + wv[CB - 1 - bb];
-        m[bb & 3] = bb < 4 ? cand : pvmin(m[bb & 3], cand);
-      }
-      double rv;
-      if constexpr (CB >= 4)
-        rv = pvmin(pvmin(m[0], m[1]), pvmin(m[2], m[3]));
-      else
-        rv = pvmin(m[0], m[1]);
-      rv = pvmin(rv, pv_dpp<0xB1>(rv));                      // the lane group's other class parts
-      if constexpr (LPR >= 4) rv = pvmin(rv, pv_dpp<0x4E>(rv));
-      if constexpr (LPR >= 8) rv = pvmin(rv, pv_dpp<0x141>(rv));  // row_half_mirror: lane i <-> 7 - i, the other quad
-      if constexpr (LPR == 16) rv = pvmin(rv, pv_dpp<0x140>(rv));  // row_mirror: lane i <-> 15 - i, the other half
-      // every lane of the row group holds rv: all of them store it (one address per group, so the same lines and
-      // bytes move), with no exec-mask switch on the chain (one lane storing: 16.1 ms at C4, all of them: 15.1 ms)
-      // (rows above B of the top segment store their finite value too: k_pinf_rfill sets them to +Inf after the
-      // launch, and no segment's window reads them)
-      slot(i)[u] = rv;
-      __builtin_amdgcn_raw_buffer_store_b64((pi_u32x2){(unsigned)__double2loint(rv), (unsigned)__double2hiint(rv)},
-                                            Rr, (unsigned)(((size_t)i * RP + c) * 8), 0, 16);
-    };
-    if constexpr (PINF_MC_SPLIT && LPR == 8) {
-      // The chain split in two.  Row c = 8q + r reads R_{i+1}[c - b]: a class b < 8 may read one of the segment's
-      // own rows, which the previous step wrote (the step-to-step chain); a class b >= 8 reads only rows below the
-      // segment, staged for the whole chunk, so their minimum P_i is computed one step ahead, off the chain.  On the
-      // chain, lane h of a row group takes classes 2(h&3) and 2(h&3)+1 (lanes h and h+4 the same two): two DPP
-      // steps and the min with P_i, where the one-part form above has three DPP steps after the class sums.  min is
-      // exact, so the grouping changes no bit.
-      constexpr int CO = (BWP - 8) / 8;  // off-chain classes per lane: 8 + CO·h .. 8 + CO·h + CO - 1
-      const int b0 = 2 * (h & 3);
-      // class values of step i (reads below the chunk's first step land in the LDS in front of Kc, unused)
-      auto kl = [&](double (&kc)[2], double (&kf)[CO], int i) {
-        const double *kr = Kc + (i - lo) * BWP;
-        const double2 y = *reinterpret_cast<const double2 *>(kr + b0);
-        kc[0] = y.x;
-        kc[1] = y.y;
-#pragma unroll
-        for (int t = 0; t < CO; ++t) kf[t] = kr[8 + CO * h + t];
-      };
-      // the off-chain part from the window R_{i+1}[c - 8 - CO·h - (CO-1) .. c - 8 - CO·h] (wf) and K_i (kf)
-      auto offc = [&](const double (&kf)[CO], const double (&wf)[CO]) {
-        double p = kf[0] + wf[CO - 1];
-#pragma unroll
-        for (int t = 1; t < CO; ++t) p = pvmin(p, kf[t] + wf[CO - 1 - t]);
-        p = pvmin(p, pv_dpp<0xB1>(p));
-        p = pvmin(p, pv_dpp<0x4E>(p));
-        return pvmin(p, pv_dpp<0x141>(p));
-      };
-      auto wload = [&](double (&wf)[CO], int i) {  // R_{i+1} below the segment, for step i's off-chain part
-        const double *Af = slot(i + 1) + u - 8 - CO * h - (CO - 1);
-#pragma unroll
-        for (int t = 0; t < CO; ++t) wf[t] = Af[t];
-      };
-      // one step: the chain's reads of step i issued first, then the off-chain reads and class values of step i-1
-      // (at the chunk's last step they read rows and values the chunk does not use), then P_i from the registers
-      // the previous step loaded -- its VALU work fills the wait for the chain's reads -- then the chain
-      auto st = [&](int i, const double (&kc)[2], const double (&kf)[CO], const double (&wf)[CO], double (&kcn)[2],
-                    double (&kfn)[CO], double (&wfn)[CO]) {
-        asm volatile("" ::: "memory");
-        const double *Ain = slot(i + 1) + u - b0 - 1;  // R_{i+1}[c - b0 - 1], R_{i+1}[c - b0]
-        const double w0 = Ain[0], w1 = Ain[1];
-        wload(wfn, i - 1);
-        kl(kcn, kfn, i - 1);
-        const double P = offc(kf, wf);
-        double rv = pvmin(kc[0] + w1, kc[1] + w0);
-        rv = pvmin(rv, pv_dpp<0xB1>(rv));
-        rv = pvmin(rv, pv_dpp<0x4E>(rv));
-        rv = pvmin(rv, P);
-        slot(i)[u] = rv;
-        __builtin_amdgcn_raw_buffer_store_b64((pi_u32x2){(unsigned)__double2loint(rv), (unsigned)__double2hiint(rv)},
-                                              Rr, (unsigned)(((size_t)i * RP + c) * 8), 0, 16);
-      };
-      double kca[2], kcb[2], kfa[CO], kfb[CO], wa[CO], wb[CO];
-      kl(kca, kfa, hi);
-      wload(wa, hi);
-      for (int i = hi; i >= lo; i -= 2) {
-        st(i, kca, kfa, wa, kcb, kfb, wb);
-        if (i - 1 >= lo) st(i - 1, kcb, kfb, wb, kca, kfa, wa);
-      }
-    } else {
-      // two steps per trip, the class-value registers alternating (no copies between steps)
-      double ka[CB], kb[CB];
-      kload(ka, hi);
-      for (int i = hi; i >= lo; i -= 2) {
-        step(i, ka, kb);
-        if (i - 1 >= lo) step(i - 1, kb, ka);
-      }
-    }
-    // this chunk's rows have landed: publish its last step for the segments above
-    vm_drain();
-    if (lane == 0) __hip_atomic_store(done + q * FS, nt - 1 - lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    hi = nhi;
-    lo = nlo;
-  }
+  return true;
+}
+// publish a token (one lane; the caller has waited for the stores the token covers)
+__device__ __forceinline__ void pinf_publish_token(int32_t *done, int token) {
+  __hip_atomic_store(done, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// one double to R through the buffer resource Rr, sc1 (visible to the other CUs' sc1 reads once it has landed)
+__device__ __forceinline__ void pinf_store_r(__amdgpu_buffer_rsrc_t Rr, unsigned byte_off, double v) {
+  __builtin_amdgcn_raw_buffer_store_b64((pi_u32x2){(unsigned)__double2loint(v), (unsigned)__double2hiint(v)}, Rr,
+                                        byte_off, 0, 16);
 }
 
-// k_pinf_recur_mc with helper waves (8 lanes per row, 8-row segments, classes 16 or 32): the chain of a step only
-// involves the classes b < 8 -- rows of the segment itself, which the previous step wrote; every class b >= 8 reads a
-// row below the segment, staged for the whole chunk before the chunk starts.  So the off-chain minima
+// Row segments on several CUs (few subproblems, classes 16 or 32): R_i[c] needs R_{i+1}[c - b] for b < BWP <= 32, i.e.
+// rows c-31 .. c only, so rows split into segments of 8 (one workgroup each; in wave 0 eight lanes per row) form a
+// pipeline like k_sdt_run's: segment q runs a step once the segments within 32 rows below it (q-1 .. q-4) have
+// published that step's rows.  Segments hand over in chunks of CH steps (the protocol above): the 32 rows below the
+// segment for a whole chunk's steps sit in an LDS ring of 2·CH step arrays before the chunk starts.
+// The chain of a step only involves the classes b < 8 -- rows of the segment itself, which the previous step wrote;
+// every class b >= 8 reads a row below the segment.  So the off-chain minima
 //   P_i[c] = min_{8 <= b < BWP} fl(Kmin_i[b] + R_{i+1}[c - b])
 // of a whole chunk are computed ahead, by three helper waves, while wave 0 runs the previous chunk's chain; they also
 // wait for the segments below, copy the chunk's rows below (LDS-DMA, sc1) and its class rows.  Wave 0's step is then
-// the on-chain part only (lane h of a row group: classes 2(h&3), 2(h&3)+1, two DPP steps) and one min with P_i from
-// the LDS.  min is exact, so R is bit-identical to k_pinf_recur's.  A workgroup barrier per chunk; a failed wait (spin
+// the on-chain part only (lane h of a row group: classes 2(h&3), 2(h&3)+1, lanes h and h+4 the same two; two DPP
+// steps) and one min with P_i from the LDS; a wave needs no barrier for its own LDS accesses: they execute in order.
+// Every candidate is the same expression fl(Kmin_i[b] + R_{i+1}[c - b]) as k_pinf_recur's and min is exact, so the
+// grouping changes no bit: R is bit-identical to k_pinf_recur's.  A workgroup barrier per chunk; a failed wait (spin
 // limit) stops every wave after it.
 template <int BWP>
 __global__ __launch_bounds__(256) void k_pinf_recur_mcw(ProblemDev P, PinfDev D, int nseg, int32_t *flags,
                                                        unsigned spin_limit) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   __shared__ int s_stop, s_hsync;
-  constexpr int RPS = 8, AS = 32 + RPS, CH = PINF_MC_CHUNK, NS = 2 * CH;
+  // rows per segment; step array: the 32 rows below the segment, then its own; steps per hand-off; ring of step arrays
+  constexpr int RPS = kPinfMcRows, AS = 32 + RPS, CH = PINF_MC_CHUNK, NS = 2 * CH;
+  static_assert(RPS == 8, "k_pinf_recur_mcw: eight lanes per row in wave 0");
   static_assert(BWP == 16 || BWP == 32, "k_pinf_recur_mcw: classes 16 or 32");
   const int RP = P.RP, B = P.B, nt = P.nt, K = P.K;
   const int k = (int)blockIdx.x / nseg, q = (int)blockIdx.x - k * nseg;
@@ -880,31 +675,16 @@ __global__ __launch_bounds__(256) void k_pinf_recur_mcw(ProblemDev P, PinfDev D,
       // the segments within 32 rows below (q-1 .. q-4) have published step clo+1 (token nt-2-clo)
       const int need = nt - 1 - (clo + 1);
       for (int d = 1; d * RPS <= 32 && q - d >= 0 && ok; ++d) {
-        unsigned spins = 0;
-        while (__hip_atomic_load(done + (q - d) * FS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-          if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || ++spins > spin_limit) {
-            __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (lane == 0) s_stop = 1;
-            ok = false;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(2);
+        if (!pinf_wait_token(done + (q - d) * FS, need, err, spin_limit)) {
+          if (lane == 0) s_stop = 1;
+          ok = false;
         }
       }
       if (ok) {  // lane l of a helper wave moves rows RPS·q-32+2l, +1 of one step (16 bytes, LDS-DMA, sc1)
         const int row = RPS * q - 32 + 2 * lane;
         for (int s = clo + 1 + (w - 1); s <= s1; s += 3) {
-          if (lane < 16 && row >= 0) {
-            const void *g = pi_uniform(R + (size_t)s * RP);
-            const unsigned m0 =
-                __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)slot(s)));
-            const unsigned voff = 8u * (unsigned)row;
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 sc1\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(voff), "s"(g), "s"(m0)
-                         : "memory");
-          }
+          if (lane < 16 && row >= 0)
+            glds_dma16<true>(lds_addr(slot(s)), pi_uniform(R + (size_t)s * RP), 8u * (unsigned)row);
         }
       }
     }
@@ -953,9 +733,12 @@ __global__ __launch_bounds__(256) void k_pinf_recur_mcw(ProblemDev P, PinfDev D,
         rv = pvmin(rv, pv_dpp<0xB1>(rv));
         rv = pvmin(rv, pv_dpp<0x4E>(rv));
         rv = pvmin(rv, pv);
+        // every lane of the row group holds rv: all of them store it (one address per group, so the same lines and
+        // bytes move), with no exec-mask switch on the chain (one lane storing: 16.1 ms at C4, all of them: 15.1 ms)
+        // (rows above B of the top segment store their finite value too: k_pinf_rfill sets them to +Inf after the
+        // launch, and no segment's window reads them)
         slot(i)[u] = rv;
-        __builtin_amdgcn_raw_buffer_store_b64((pi_u32x2){(unsigned)__double2loint(rv), (unsigned)__double2hiint(rv)},
-                                              Rr, (unsigned)(((size_t)i * RP + c) * 8), 0, 16);
+        pinf_store_r(Rr, (unsigned)(((size_t)i * RP + c) * 8), rv);
       };
       double ka[2], kb[2], pa, pb;
       ld(ka, pa, hi);
@@ -965,7 +748,7 @@ __global__ __launch_bounds__(256) void k_pinf_recur_mcw(ProblemDev P, PinfDev D,
       }
       // this chunk's rows have landed: publish its last step for the segments above
       vm_drain();
-      if (lane == 0) __hip_atomic_store(done + q * FS, nt - 1 - lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (lane == 0) pinf_publish_token(done + q * FS, nt - 1 - lo);
     } else if (nhi >= 0) {
       prepare(nlo, nhi, (qq + 1) & 1);
     }
@@ -981,7 +764,7 @@ __global__ __launch_bounds__(256) void k_pinf_recur_mcw(ProblemDev P, PinfDev D,
 // Row c = 64q + l needs R_{i+1}[c - b] for b < CB <= 8 only: inside the segment that is lane l - b's register, reached
 // by b chained DPP `wave_shr:1` moves whose lane 0 is filled from the segment below (rows 64q - b, staged for the step
 // in the LDS); so a step is CB-1 shifts, CB sums and CB-1 minima on registers, and one R store, with no LDS round trip
-// and no barrier on the chain.  The hand-off between segments is k_pinf_recur_mc's (chunks of CH steps: the segment
+// and no barrier on the chain.  The hand-off between segments is the one above (chunks of CH steps: the segment
 // below stores its rows, drains, publishes the chunk's last step; this one polls a chunk ahead and copies the 8 rows
 // below it for the chunk's steps by LDS-DMA).  Same candidates fl(Kmin_i[b] + R_{i+1}[c - b]), and min is exact: R is
 // bit-identical to k_pinf_recur's.  A wait past the spin limit sets the error word (flags[errw]) and the host redoes
@@ -1020,15 +803,7 @@ __global__ __launch_bounds__(64) void k_pinf_recur_ws(ProblemDev P, PinfDev D, i
   auto wait_below = [&](int s) {  // segment q-1 has published step s (token nt-1-s); false past the spin limit
     if (q == 0) return true;
     const int need = nt - 1 - s;
-    unsigned spins = 0;
-    while (__hip_atomic_load(done + (q - 1) * FS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-      if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || ++spins > spin_limit) {
-        __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return false;
-      }
-      __builtin_amdgcn_s_sleep(2);
-    }
-    return true;
+    return pinf_wait_token(done + (q - 1) * FS, need, err, spin_limit);
   };
   // rows 64q-8 .. 64q-1 of R_s for steps s in [s0, s1] into entries s - s0 of `dst` (LDS-DMA, sc1): lane j of
   // instruction t moves 16 bytes of step s0 + 16t + j/4, so one instruction covers 16 steps
@@ -1037,16 +812,9 @@ __global__ __launch_bounds__(64) void k_pinf_recur_ws(ProblemDev P, PinfDev D, i
     if (q == 0) return;
     for (int t = 0; s0 + 16 * t <= s1; ++t) {
       const int s = s0 + 16 * t + (lane >> 2);
-      if (s <= s1) {
-        const unsigned m0 = __builtin_amdgcn_readfirstlane(
-            (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)(dst + (size_t)16 * HB * t)));
-        const unsigned voff = 8u * (unsigned)((size_t)s * RP + 64 * q - HB + 2 * (lane & 3));
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 sc1\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(voff), "s"(Rg), "s"(m0)
-                     : "memory");
-      }
+      if (s <= s1)
+        glds_dma16<true>(lds_addr(dst + (size_t)16 * HB * t), Rg,
+                         8u * (unsigned)((size_t)s * RP + 64 * q - HB + 2 * (lane & 3)));
     }
   };
   auto kdst = [&](int par) { return Kbuf + (size_t)par * CE * BWP + EP * BWP; };
@@ -1079,7 +847,7 @@ __global__ __launch_bounds__(64) void k_pinf_recur_ws(ProblemDev P, PinfDev D, i
           asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // S: every store but this chunk's first S
         else
           vm_drain();
-        if (lane == 0) __hip_atomic_store(done + q * FS, nt - 1 - prev_lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 0) pinf_publish_token(done + q * FS, nt - 1 - prev_lo);
       }
       if (nhi >= 0) {  // (the poll first: its wait would otherwise also wait for the DMAs)
         if (!wait_below(nlo + 1)) {
@@ -1116,8 +884,7 @@ __global__ __launch_bounds__(64) void k_pinf_recur_ws(ProblemDev P, PinfDev D, i
         m = pvmin(m, o.kv[b] + sft);
       }
       r = m;
-      __builtin_amdgcn_raw_buffer_store_b64((pi_u32x2){(unsigned)__double2loint(r), (unsigned)__double2hiint(r)}, Rr,
-                                            (unsigned)(((size_t)i * RP + c) * 8), 0, 16);
+      pinf_store_r(Rr, (unsigned)(((size_t)i * RP + c) * 8), r);
     };
     Op o0, o1, o2, o3;
     opnd(o0, hi);
@@ -1159,11 +926,10 @@ __global__ __launch_bounds__(64) void k_pinf_recur_ws(ProblemDev P, PinfDev D, i
   }
   // the last chunk's rows have landed: publish it (segments above wait for it)
   vm_drain();
-  if (!stop && prev_lo >= 0 && lane == 0)
-    __hip_atomic_store(done + q * FS, nt - 1 - prev_lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!stop && prev_lo >= 0 && lane == 0) pinf_publish_token(done + q * FS, nt - 1 - prev_lo);
 }
 
-// rows c_from .. RP-1 of R (beyond the rows k_pinf_recur_xr / _mc compute, all above B): +Inf for every step
+// rows c_from .. RP-1 of R (beyond the rows k_pinf_recur_xr / _mcw / _ws compute, all above B): +Inf for every step
 __global__ void k_pinf_rfill(ProblemDev P, PinfDev D, int c_from) {
   if (P.redo_gate && *P.redo_gate == 0) return;
   const int k = blockIdx.y, RP = P.RP, nt = P.nt, n = RP - c_from;
@@ -1174,31 +940,17 @@ __global__ void k_pinf_rfill(ProblemDev P, PinfDev D, int c_from) {
 
 int pinf_chunk_recur(int BWP) { return BWP <= 16 ? 64 : 32; }
 
-namespace {
-// k_pinf_recur_mc for one class width: false where the width leaves a lane fewer than two classes
-template <int BWP, int LPR>
-bool launch_pinf_mc(hipStream_t s, const ProblemDev &P, const PinfDev &D, int nseg, int32_t *flags,
-                    unsigned spin_limit, size_t lds) {
-  if constexpr (BWP >= 2 * LPR) {
-    hipLaunchKernelGGL((k_pinf_recur_mc<BWP, LPR>), dim3(P.K * nseg), dim3(64), lds, s, P, D, nseg, flags, spin_limit);
-    return true;
-  } else {
-    return false;
-  }
-}
-}  // namespace
-
-int pinf_recur_segments(const ProblemDev &P) { return (P.B + 1 + 64 / PINF_RECUR_MC_LANES - 1) / (64 / PINF_RECUR_MC_LANES); }
+int pinf_recur_segments(const ProblemDev &P) { return (P.B + 1 + kPinfMcRows - 1) / kPinfMcRows; }
 
 hipError_t launch_pinf_recur(hipStream_t s, const ProblemDev &P, const PinfDev &D, int ncu, int32_t *flags,
                              unsigned spin_limit, bool *segmented, const char **variant) {
   if (segmented) *segmented = false;
   if (variant) *variant = "k_pinf_recur";
   // few subproblems, classes <= 8, two or more 64-row segments: k_pinf_recur_ws (its error word where the host reads
-  // k_pinf_recur_mc's: flags[K·pinf_recur_segments])
+  // k_pinf_recur_mcw's: flags[K·pinf_recur_segments·PINF_WS_FLAG_STRIDE])
   {
     const int nseg = (P.B + 1 + 63) / 64;
-    if (PINF_RECUR_WS && flags && segmented && D.BW >= 1 && D.BW <= 8 && D.BWP == 8 && nseg >= 2 &&
+    if (flags && segmented && D.BW >= 1 && D.BW <= 8 && D.BWP == 8 && nseg >= 2 &&
         P.K * nseg <= ncu && 64 * nseg <= P.RP && (size_t)P.nt * P.RP * 8 < (1ull << 31)) {
       const int errw = P.K * pinf_recur_segments(P) * PINF_WS_FLAG_STRIDE;
       const size_t lds = (size_t)2 * (PINF_WS_CHUNK + 4) * (8 + D.BWP) * sizeof(double);  // Hbuf, Kbuf
@@ -1219,44 +971,33 @@ hipError_t launch_pinf_recur(hipStream_t s, const ProblemDev &P, const PinfDev &
       return hipGetLastError();
     }
   }
-  // few subproblems, classes <= 32, tall enough: row segments of 32 on several CUs (k_pinf_recur_mc); the flags
+  // few subproblems, classes 16 or 32, three or more 8-row segments: k_pinf_recur_mcw on several CUs; the flags
   // (K·nseg·PINF_WS_FLAG_STRIDE + 1 words, zeroed by the caller) carry the hand-off (packed) and, last, the error word
   {
-    constexpr int LPR = PINF_RECUR_MC_LANES, RPS = 64 / LPR;  // lanes per row, rows per segment
-    const int nseg = (P.B + 1 + RPS - 1) / RPS;
-    if (PINF_RECUR_MC && flags && segmented && D.BWP >= 2 * LPR && D.BWP <= 32 && nseg >= 3 && P.K * nseg <= ncu &&
-        RPS * nseg <= P.RP && (size_t)P.nt * P.RP * 8 < (1ull << 31)) {
-      constexpr int CH = PINF_MC_CHUNK;
-      const bool helpers = PINF_MC_HELPERS && LPR == 8 && (D.BWP == 16 || D.BWP == 32);
-      const size_t lds = (size_t)(2 * CH * (32 + RPS) + 2 * CH * D.BWP + (helpers ? 2 * CH * RPS : 0)) * sizeof(double);
-      bool ok = true;
-      if (helpers) {
-        if (D.BWP == 16)
-          hipLaunchKernelGGL((k_pinf_recur_mcw<16>), dim3(P.K * nseg), dim3(256), lds, s, P, D, nseg, flags, spin_limit);
-        else
-          hipLaunchKernelGGL((k_pinf_recur_mcw<32>), dim3(P.K * nseg), dim3(256), lds, s, P, D, nseg, flags, spin_limit);
-      } else {
-        ok = D.BWP == 8    ? launch_pinf_mc<8, LPR>(s, P, D, nseg, flags, spin_limit, lds)
-             : D.BWP == 16 ? launch_pinf_mc<16, LPR>(s, P, D, nseg, flags, spin_limit, lds)
-                           : launch_pinf_mc<32, LPR>(s, P, D, nseg, flags, spin_limit, lds);
-      }
-      if (ok) {
-        // rows above B (the top segment's finite values, and the rows no segment computes): +Inf, after the launch
-        if (P.B + 1 < P.RP) hipLaunchKernelGGL(k_pinf_rfill, dim3(64, P.K), dim3(256), 0, s, P, D, P.B + 1);
-        *segmented = true;
-        if (variant) *variant = helpers ? "k_pinf_recur_mcw" : "k_pinf_recur_mc";
-        return hipGetLastError();
-      }
+    constexpr int RPS = kPinfMcRows, CH = PINF_MC_CHUNK;
+    const int nseg = pinf_recur_segments(P);
+    if (flags && segmented && (D.BWP == 16 || D.BWP == 32) && nseg >= 3 && P.K * nseg <= ncu && RPS * nseg <= P.RP &&
+        (size_t)P.nt * P.RP * 8 < (1ull << 31)) {
+      const size_t lds = (size_t)(2 * CH * (32 + RPS) + 2 * CH * D.BWP + 2 * CH * RPS) * sizeof(double);  // A, Kbuf, Pbuf
+      if (D.BWP == 16)
+        hipLaunchKernelGGL((k_pinf_recur_mcw<16>), dim3(P.K * nseg), dim3(256), lds, s, P, D, nseg, flags, spin_limit);
+      else
+        hipLaunchKernelGGL((k_pinf_recur_mcw<32>), dim3(P.K * nseg), dim3(256), lds, s, P, D, nseg, flags, spin_limit);
+      // rows above B (the top segment's finite values, and the rows no segment computes): +Inf, after the launch
+      if (P.B + 1 < P.RP) hipLaunchKernelGGL(k_pinf_rfill, dim3(64, P.K), dim3(256), 0, s, P, D, P.B + 1);
+      *segmented = true;
+      if (variant) *variant = "k_pinf_recur_mcw";
+      return hipGetLastError();
     }
   }
   int pairs = ((P.RP / 2 + 63) / 64) * 64;  // one thread (G = 1) or lane quad (G = 4) per two budget rows
   if (pairs > 512) pairs = 512;
   // few subproblems (fewer workgroups than a quarter of the CUs): four lanes per row pair; a batch keeps one lane
   // (its workgroups already fill the CUs, and the recursion is then bound by the R stores)
-  const int G = PINF_RECUR_SPLIT && P.K * 4 <= ncu && D.BWP >= 8 ? PINF_RECUR_G : 1;
+  const int G = P.K * 4 <= ncu && D.BWP >= 8 ? 4 : 1;
   const int CH = pinf_chunk_recur(D.BWP);
   // ... and with B + 1 = 32·8 + 1 (C4), eight waves of row pairs and the extra row split by classes (k_pinf_recur_xr)
-  if (PINF_RECUR_XR && G == 4 && D.BWP == 32 && P.B + 1 == 32 * 8 + 1 && 32 * 8 + 1 <= P.RP) {
+  if (G == 4 && D.BWP == 32 && P.B + 1 == 32 * 8 + 1 && 32 * 8 + 1 <= P.RP) {
     const size_t lds = (size_t)(2 * (D.BWP + P.RP) + 2 * CH * D.BWP + 2 * 8) * sizeof(double);
     if (32 * 8 + 1 < P.RP) hipLaunchKernelGGL(k_pinf_rfill, dim3(64, P.K), dim3(256), 0, s, P, D, 32 * 8 + 1);
     hipLaunchKernelGGL((k_pinf_recur_xr<32, 8>), dim3(P.K), dim3(512), lds, s, P, D, CH);
@@ -1269,8 +1010,6 @@ hipError_t launch_pinf_recur(hipStream_t s, const ProblemDev &P, const PinfDev &
 #define PINF_RECUR(BW)                                                                                    \
   if (G == 4)                                                                                             \
     hipLaunchKernelGGL((k_pinf_recur<BW, 4>), dim3(P.K), dim3(threads), lds, s, P, D, CH);                \
-  else if (G == 2)                                                                                        \
-    hipLaunchKernelGGL((k_pinf_recur<BW, 2>), dim3(P.K), dim3(threads), lds, s, P, D, CH);                \
   else                                                                                                    \
     hipLaunchKernelGGL((k_pinf_recur<BW, 1>), dim3(P.K), dim3(threads), lds, s, P, D, CH);
   switch (D.BWP) {

@@ -1,7 +1,7 @@
 """Generate tests/golden/hashed/c4_4096lv_pinf_nt200.npz: the BASELINE roofline shape (C4: 8^4 = 4096 levels, B = 256,
 seeded inputs of mioc.synth) at p = Inf, truncated to nt = 200, solved by the C oracle (the restatement of
 HelpFunctions.jl:20-124; at p = Inf every transition costs beta, HelpFunctions.jl:63-67).  199 recursion steps: more
-than three of k_pinf_recur_mc's 64-step hand-off chunks and a wrap of its 128-slot LDS ring.  Stored: the inputs, and
+than three of k_pinf_recur_mcw's 64-step hand-off chunks and a wrap of its 128-slot LDS ring.  Stored: the inputs, and
 u / Φ* for B' in BPS (the backtrack walks every step's argmin along its path).
 Run:  python tests/golden/make_c4_pinf_fixture.py   (a few minutes on 8 cores: OpenMP over the target levels of each
 step, bit-identical to the single-threaded oracle)

@@ -10,8 +10,9 @@ restatement to the C oracle on the CPU.  Then u and Φ* equal the oracle at the 
 The dispatch conditions are written in the device's CU count (256 on an MI355X): K is computed from it, and a case
 whose condition another count cannot meet is skipped, never asserted against another kernel.
 
-k_pinf_recur_mc, the row-segment kernel without helper waves, is not reachable in the default build (PINF_MC_HELPERS
-is 1, so 16 and 32 classes take k_pinf_recur_mcw and 8 classes fail its BWP >= 16); no case names it.
+The row-segment kernel is k_pinf_recur_mcw (8-row segments, 64-step hand-off chunks, a 128-slot LDS ring of step
+arrays) at 16 and 32 classes; 8 classes take k_pinf_recur_ws or k_pinf_recur.  Its predecessor without helper waves,
+k_pinf_recur_mc, which no input could reach, has been removed.
 
 The walks: the segmented walk at its segment-count boundaries and at one step, the serial walk's exact scan (whole rows
 staged, and inside a band), and the serial walk around its staged chunk.

@@ -165,7 +165,7 @@ def _c4_pinf_fixture():
 @pytest.mark.parametrize("spin", [0, 1], ids=["run", "timeout_redo"])
 def test_c4_pinf_nt200_fixture(walk, spin):
     """C4 at p = Inf (4096 levels, B = 256) over 199 recursion steps against the C oracle's fixture
-    (tests/golden/make_c4_pinf_fixture.py): the row-segment recursion k_pinf_recur_mc across more than three of its
+    (tests/golden/make_c4_pinf_fixture.py): the row-segment recursion k_pinf_recur_mcw across more than three of its
     64-step hand-off chunks and a wrap of its 128-slot ring, then u and Φ* at five budgets.  spin = 1: a spin limit of
     one poll abandons the segmented launch at its first unmet wait, and the one-workgroup recursion, launched behind it
     gated by its error word, redoes the DP on the device (diagnostics [6]) before anything reads the tables -- the same
