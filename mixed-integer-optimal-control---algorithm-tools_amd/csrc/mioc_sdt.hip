@@ -13,7 +13,9 @@
 //   - each finite Ψ_j becomes V_j = base + (Ψ_j - Ψmin)/β, truncated to the grid g = 2^18 ulp(base), with
 //     the source rank j in mantissa bits 6..17 and a near-tie count in bits 0..5 (the payload);
 //   - a unit step costs exactly 1.0 (a multiple of g), so every sum is exact and keeps its payload, and
-//     v_min_f64 carries the winner's rank through every pass for free;
+//     v_min_f64 carries the winner's rank through every pass for free; the first (non-counting) transform steps by
+//     1.0 + ulp, which also counts the steps in payload bits 0..5: an output carries d(l, j*) beside j* (two values
+//     that differ in their value part or rank are ordered as before: the count never decides between two sources);
 //   - every merge of two disjoint candidate sets whose values differ by <= tol adds one to the count of its result
 //     (one v_addc on the low word: a value passes at most 14 merges per pass, 56 in all, so the count never reaches
 //     the rank bits); a nonzero count is the "near tie" flag.
@@ -297,12 +299,15 @@ struct SdtShared {
   int redj[SD_COOP * NW];
   double rmn[NW], rmx[NW];
   int rnv[NW];
-  // by row parity (sdt_body's `par`): targets listed for the exact scan, and whether a near tie was met anywhere in
-  // the row's first (non-counting) transform.  Each row resets the other parity's slots after its first barrier: the
-  // row before has read them before that barrier, the row after writes them after its own first barrier.
-  int nlist[2];
-  int redo[2];
-  int stop;  // persistent kernel: a dependency wait timed out
+  // the row's control words, one 16-byte record by row parity (sdt_body's `par`), which every wave reads with one LDS
+  // read behind the winners' barrier: whether a near tie was met anywhere in the row's first (non-counting) transform,
+  // the targets listed for the exact scan, and (persistent kernel) whether a dependency wait timed out.  Each row
+  // resets the other parity's redo and nlist after its first barrier: the row before has read them before that
+  // barrier, the row after writes them after its own first barrier.  `stop` is set in both records and never reset
+  // (it lies between the two, so that the reset stays two 4-byte stores).
+  struct alignas(16) Ctl {
+    int redo, stop, nlist, pad;
+  } ctl[2];
   unsigned long long stamp[16];  // diagnostic build: phase clocks of the current row
   int nsp;   // sparse rows: the finite sources (rank, Ψ)
   int spj[SD_SPARSE];
@@ -509,7 +514,7 @@ __device__ __forceinline__ unsigned sdt_stats(const ProblemDev &P, const PyrGeom
 //            (publish `loaded`, issue the polls); h.go() after the first barrier (check the polls, issue the next row's
 //            loads, the next step's sphere order and df / u_old); h.late_drain() before the barrier after the winners
 //            (this wave's stores of the previous row have landed), h.publish() after it (the previous row is done).  A
-//            timed-out wait sets sh.stop, which the driver reads after the row; h.tail(empty, outv) once the row's
+//            timed-out wait sets `stop` in sh.ctl, which publish() is handed; h.tail(empty, outv) once the row's
 //            outputs are final, before its stores (the persistent driver runs the next row's sdt_stats there);
 //            h.store16(Sout, e, lo, hi): elements e, e + 1 of the output row (the persistent driver forms the row's
 //            address from its byte offset in the region, Sout unused).
@@ -572,6 +577,10 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
 #pragma unroll
   for (int m = 0; m < M; ++m) qa += fabs(a[m]) * (double)max(abs(lb[m]), abs(lb[m] + 7));
   double ref, base, g, tol;
+  // the unit step of the first (non-counting) transform: 1.0 plus one ulp of the binade, so that every step also
+  // advances payload bits 0..5 (SD_CNT, zero in every stamp) by one: an output V_j* + d·unit carries d(l, j*) there
+  // (d <= 7·M < 64: no carry into the rank bits), and the winners read it instead of recomputing the stamp
+  double unit;
   bool scale_ok;
   auto scale = [&](double lo, double hi) {
     const double rs = (hi - lo) * inv + (double)Smax;              // scaled range of every transform value
@@ -579,6 +588,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
     const int E = ilogb(fmin(rs, 0x1p31) * (1.0 + 0x1p-20) + 1.0) + 2;  // 2^E >= 2·rs (E <= SD_GRID: g <= 1)
     base = ldexp(1.0, E);
     g = ldexp(1.0, E - SD_GRID);
+    unit = 1.0 + ldexp(1.0, E - 52);
     // 2 × stamping error (< g) + 2 × the reference's rounding (<= 4u·qmax per candidate), in units of β
     tol = 3.0 * g + 0x1p-49 * (qa + fmax(fabs(lo), fabs(hi))) * inv;
     ref = lo;
@@ -625,7 +635,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
 #pragma unroll
       for (int x = 6; x >= 0; --x) o[x] = sd_merge(o[x], o[x + 1] + 1.0, tol);
     } else {
-      sd_sweeps(o, dmin);  // both sweeps, |a - b| of every merge folded into dmin
+      sd_sweeps(o, dmin, unit);  // both sweeps, |a - b| of every merge folded into dmin
     }
     if (m + 1 < M) {
 #pragma unroll
@@ -664,9 +674,11 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
       // finite distance, so every o[x] is finite here -- only the trust region decides
       const bool fin = ALL || (valid >> x & 1) != 0;
       const bool flg = FLAG && (__double2loint(o[x]) & SD_CNT) != 0;
-      // d(l, j*) exactly: an unflagged finite o[x] is V_j* + d with V_j* = the stamp of Ψ_j* (the same expression
-      // as the stamping above, payload j*), every term exact in the binade (garbage, unused, otherwise)
-      const double dd = o[x] - stamp(pv[x], j);
+      // d(l, j*) exactly.  The first transform counts its steps in payload bits 0..5 (`unit`).  The counting
+      // transform keeps its near-tie count there: an unflagged finite o[x] is V_j* + d with V_j* = the stamp of Ψ_j*
+      // (the same expression as the stamping above, payload j*), every term exact in the binade (garbage, unused,
+      // otherwise)
+      const double dd = FLAG ? o[x] - stamp(pv[x], j) : (double)(__double2loint(o[x]) & SD_CNT);
       const double t1 = pre + a[M - 1] * (double)(lb[M - 1] + x);
       const double val = (t1 + beta * dd) + pv[x];  // R(l, j*), HelpFunctions.jl:63-71
       if constexpr (FLAG) {
@@ -682,7 +694,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
   };
   auto list_targets = [&](unsigned listed) {
     if (listed) {
-      int e = atomicAdd(&sh.nlist[par], __popc(listed));
+      int e = atomicAdd(&sh.ctl[par].nlist, __popc(listed));
 #pragma unroll
       for (int x = 0; x < 8; ++x)
         if (listed >> x & 1) {
@@ -707,7 +719,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
   {
     double pmn, pmx;
     sd_bar();  // every wave's row statistics (sdt_stats) are in sh, its Ψ in the LDS: the loads of S_{i+1} are consumed
-    if (tid == 0) sh.nlist[par ^ 1] = sh.redo[par ^ 1] = 0;  // the next row's slots
+    if (tid == 0) sh.ctl[par ^ 1].nlist = sh.ctl[par ^ 1].redo = 0;  // the next row's slots
     h.early();
     {
       // every wave's statistics in one batch of LDS reads and one wait (the compiler interleaved them with the
@@ -757,7 +769,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
     empty = __builtin_amdgcn_readfirstlane((int)(nv == 0 || !(pmn < INFINITY))) != 0;  // uniform
     // a one-target row is direct whatever the range of its sources: it uses nothing of the binade
     if (is_one()) {
-      ref = base = g = tol = 0.0;
+      ref = base = g = tol = unit = 0.0;
       scale_ok = true;
     } else {
       scale(pmn, pmx);
@@ -841,7 +853,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
         winners(std::false_type{}, std::true_type{});
       else
         winners(std::false_type{}, std::false_type{});
-      if (__any(dmin <= tol) && lane == 0) sh.redo[par] = 1;
+      if (__any(dmin <= tol) && lane == 0) sh.ctl[par].redo = 1;
     } else {
 #pragma unroll
       for (int x = 0; x < 8; ++x) {
@@ -877,8 +889,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
     }
     list_targets(listed);
     // the listed targets' exact scans (the caller's next barrier publishes their results)
-    auto scans = [&]() {
-      const int nl = sh.nlist[par];
+    auto scans = [&](int nl) {
       if (nl) {  // uniform
         if (nl <= SD_COOP)
           sd_scan<M, true>(list, nl, psi, a, lb, beta, uu, outv, sh.redv, sh.redj);
@@ -898,19 +909,24 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
     const bool scan_first = PERSIST && direct && !is_one();  // uniform (the one-target item has scanned already)
     if (scan_first) {
       sd_bar();  // the list is complete, every lane's placeholder outputs are written
-      scans();
+      scans(sh.ctl[par].nlist);
     }
     h.late_drain();  // this wave's stores of the previous row have landed (late: they have had the whole row)
     sd_bar();
-    h.publish();     // ... so have every wave's: the previous row is done
+    // the row's control words in one LDS read and one wait, directly behind the barrier (one round trip where reading
+    // stop, redo and nlist one after the other took three, on every item's critical path): x redo, y stop, z nlist
+    const int4 cw = *reinterpret_cast<const int4 *>(&sh.ctl[par]);
+    h.publish(cw.y);  // ... so have every wave's: the previous row is done
     SD_STAMP(7);
-    if (transform && sh.redo[par]) {  // uniform, rare: a near tie somewhere in the row -- the certified transform
+    int nl = cw.z;
+    if (transform && cw.x) {  // uniform, rare: a near tie somewhere in the row -- the certified transform
       passes(std::true_type{});
       list_targets(winners(std::true_type{}, std::false_type{}));
       sd_bar();
       if (tid == 0) ++sh.cnt[3];
+      nl = sh.ctl[par].nlist;  // the redo's list
     }
-    if (!scan_first && !is_one() && scans()) sd_bar();
+    if (!scan_first && !is_one() && scans(nl)) sd_bar();
   }
   if (empty) {  // uniform: the row is +Inf, U unwritten -- through LDS, so that the stores below take one path
 #pragma unroll
@@ -918,7 +934,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
     reinterpret_cast<ulonglong2 *>(uu)[tid] = make_ulonglong2(~0ull, ~0ull);
     h.late_drain();
     sd_bar();
-    h.publish();
+    h.publish(sh.ctl[par].stop);
   }
   SD_STAMP(8);
   // ---- Φ_i row c' in the sphere order of u_old(i), and the U row, both 16 bytes per lane: gathered from the LDS
@@ -1190,7 +1206,7 @@ struct SdHooksNone {
   __device__ __forceinline__ void early() {}
   __device__ __forceinline__ void go() {}
   __device__ __forceinline__ void late_drain() {}
-  __device__ __forceinline__ void publish() {}
+  __device__ __forceinline__ void publish(int) {}
   __device__ __forceinline__ void tail(bool, const double *) {}
   __device__ __forceinline__ void store16(double *Sout, int e, unsigned long long lo, unsigned long long hi) {
     sd_store16<false>(Sout, 0, e, lo, hi);
@@ -1301,7 +1317,7 @@ __global__ __launch_bounds__(1 << (3 * M - 3)) void k_sdt_step(ProblemDev P, Lev
   const int k = (int)blockIdx.y, tid = threadIdx.x;
   if (tid == 0) {
     sh.cnt[0] = sh.cnt[1] = sh.cnt[3] = 0;
-    sh.nlist[0] = sh.redo[0] = 0;
+    sh.ctl[0].nlist = sh.ctl[0].redo = 0;
   }
   // B >= 1: block 0 takes rows 0 and B together, block x the row x (B workgroups, one per CU at B = 256)
   if (blockIdx.x == 0 && P.B >= 1) {
@@ -1660,7 +1676,7 @@ struct SdPipe {
   int whole;  // one row per workgroup (hi - lo == 1)
   unsigned nbo;     // byte offset of the next row's input buffer, (ni + 1) % NB (kept by the driver: no division)
   unsigned sob;     // byte offset of this row's output row in the region (buffer i % NB, row cp)
-  bool stop_seen;   // sh.stop as read after the row's barrier 3 (publish)
+  bool stop_seen;   // sh.ctl's stop as read after the row's barrier 3 (publish)
 
   // every wave polls its own dependency flags (lanes 0-31 RAW for the next row, 32-63 WAR for this row's stores; a
   // lane without one polls a flag that always passes -- every lane loads, no branch), once every wave has consumed
@@ -1703,7 +1719,7 @@ struct SdPipe {
       if (sd_flag_poll(err) || ++spins > spin_limit) {
         if ((tid & 63) == 0) {
           __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          sh->stop = 1;  // read by the driver after the row's next barrier: the launch is abandoned
+          sh->ctl[0].stop = sh->ctl[1].stop = 1;  // read after the row's next barrier: the launch is abandoned
         }
         break;
       }
@@ -1742,12 +1758,13 @@ struct SdPipe {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     SD_TL_AT(g0, i, nt, 5);
   }
-  __device__ __forceinline__ void publish() {
+  __device__ __forceinline__ void publish(int stopped) {
     if (sd_tid() == 0 && pcp >= 0)
       __hip_atomic_store(dk + pcp * SDT_FLAG_STRIDE, nt - 1 - pi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // a timed-out wait of this row (go(), before this barrier) set sh.stop: read here, where every wave reads the same
-    // value, so that the driver's exit test after the row needs no LDS round trip of its own
-    stop_seen = sh->stop != 0;
+    // a timed-out wait of this row (go(), before this barrier) set `stop` in the row's control words, which the row
+    // body read behind this barrier, where every wave reads the same value: the driver's exit test after the row needs
+    // no LDS round trip of its own
+    stop_seen = stopped != 0;
     pcp = cp;
     pi = i;
   }
@@ -1827,9 +1844,9 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P_ar
   h.reg = reg;
   h.pcp = -1, h.pi = 0;
   if (tid == 0) {
-    sh.stop = 0;
+    sh.ctl[0].stop = sh.ctl[1].stop = 0;
     sh.cnt[0] = sh.cnt[1] = sh.cnt[2] = sh.cnt[3] = 0;
-    sh.nlist[0] = sh.nlist[1] = sh.redo[0] = sh.redo[1] = 0;
+    sh.ctl[0].nlist = sh.ctl[1].nlist = sh.ctl[0].redo = sh.ctl[1].redo = 0;
   }
   // prologue: both sphere orders of the first step, df / u_old, and the first row's loads (the terminal row was
   // written by an earlier launch)
@@ -1985,7 +2002,7 @@ struct SdPipe1 {
       if (sd_flag_poll(err) || ++spins > spin_limit) {
         if ((tid & 63) == 0) {
           __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          sh->stop = 1;
+          sh->ctl[0].stop = sh->ctl[1].stop = 1;
         }
         break;
       }
@@ -2021,10 +2038,10 @@ struct SdPipe1 {
     SD_TL_AT(g0, i, nt, 5);
   }
   // the previous item (cp, i + 1) is done: token(i + 1)
-  __device__ __forceinline__ void publish() {
+  __device__ __forceinline__ void publish(int stopped) {
     if (sd_tid() == 0 && i != nt - 2)
       __hip_atomic_store(dflag, nt - 2 - i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    stop_seen = sh->stop != 0;
+    stop_seen = stopped != 0;
   }
   __device__ __forceinline__ void store16(double *, int e, unsigned long long lo, unsigned long long hi) {
     sd_store16<true>(reg + sob / 8, L * 8, e, lo, hi);
@@ -2099,9 +2116,9 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run1(ProblemDev P_a
   asm volatile("" : "+v"(h.r0b));
   h.reg = reg;
   if (tid == 0) {
-    sh.stop = 0;
+    sh.ctl[0].stop = sh.ctl[1].stop = 0;
     sh.cnt[0] = sh.cnt[1] = sh.cnt[2] = sh.cnt[3] = 0;
-    sh.nlist[0] = sh.nlist[1] = sh.redo[0] = sh.redo[1] = 0;
+    sh.ctl[0].nlist = sh.ctl[1].nlist = sh.ctl[0].redo = sh.ctl[1].redo = 0;
   }
   // prologue (as k_sdt_run): both sphere orders of the first step, df / u_old, the first item's loads
   sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 1) * L, h.lds_slot(nt - 1));

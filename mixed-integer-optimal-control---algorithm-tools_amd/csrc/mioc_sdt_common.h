@@ -36,23 +36,25 @@ __device__ __forceinline__ double sd_max(double a, double b) {
   return r;
 }
 
-// One pass's forward and backward sweep over a line of eight values (unit step 1.0) as ONE asm statement: per merge of
-// o[x] with its neighbour o[y] + 1, `t = o[y] + 1; d = o[x] - t; o[x] = min(o[x], t); dmin = min(dmin, |d|)` -- the
+// One pass's forward and backward sweep over a line of eight values (unit step `c`, a register: 1.0 plus one ulp of the
+// row's binade, so that payload bits 0..5 count the steps -- sdt_body's scale()) as ONE asm statement: per merge of
+// o[x] with its neighbour o[y] + c, `t = o[y] + c; d = o[x] - t; o[x] = min(o[x], t); dmin = min(dmin, |d|)` -- the
 // operations and operand order of sd_min(a, b) / sd_min_abs(dmin, a - b), 14 merges.  As separate asm statements every
 // v_min_f64 pair drew the compiler's boundary wait state (`s_nop 0`) before the next merge's v_add_f64, which no
 // hardware rule asks for between these instructions; inside one statement nothing is padded.  The fold into dmin sits
 // behind the value's own min, off the value chain; +Inf - +Inf is NaN, which v_min_f64 ignores.
 #define SD_MG(X, Y)                      \
-  "v_add_f64 %9, %" #Y ", 1.0\n\t"       \
+  "v_add_f64 %9, %" #Y ", %11\n\t"       \
   "v_add_f64 %10, %" #X ", -%9\n\t"      \
   "v_min_f64 %" #X ", %" #X ", %9\n\t"   \
   "v_min_f64 %8, %8, |%10|\n\t"
-__device__ __forceinline__ void sd_sweeps(double (&o)[8], double &dmin) {
+__device__ __forceinline__ void sd_sweeps(double (&o)[8], double &dmin, double c) {
   double t, d;
   asm(SD_MG(1, 0) SD_MG(2, 1) SD_MG(3, 2) SD_MG(4, 3) SD_MG(5, 4) SD_MG(6, 5) SD_MG(7, 6)
       SD_MG(6, 7) SD_MG(5, 6) SD_MG(4, 5) SD_MG(3, 4) SD_MG(2, 3) SD_MG(1, 2) SD_MG(0, 1)
       : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]), "+v"(o[4]), "+v"(o[5]), "+v"(o[6]), "+v"(o[7]), "+v"(dmin),
-        "=&v"(t), "=&v"(d));
+        "=&v"(t), "=&v"(d)
+      : "v"(c));
 }
 #undef SD_MG
 
