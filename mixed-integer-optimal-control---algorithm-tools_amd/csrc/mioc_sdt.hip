@@ -26,8 +26,10 @@
 // rows with very few targets and rows whose scale does not fit the binade are resolved by an exact scan
 // of the reference loop.  Results are bit-identical to the reference in every case.
 //
-// Two drivers: one launch per step (k_sdt_step), or the whole DP as one persistent launch (k_sdt_run) whose
-// workgroups hand rows to each other through per-row flags.
+// Drivers: one launch per step (k_sdt_step), or the whole DP as one persistent launch whose workgroups hand rows to
+// each other through per-row flags: k_sdt_run for any number of rows per workgroup, k_sdt_run1 where every workgroup
+// owns one row.  The two persistent drivers share the hand-off: their pipeline hooks (SdPipe, SdPipe1) derive from
+// SdPipeBase, both start through sd_pipe_setup, and all three drivers flush their diagnostics through sd_add_counters.
 //
 // Layout: the staging layout of the pyramid (mioc_pyramid.hip): S_i[c'][pos_i(l)] = Φ_i[l, c' + b̃_l(i)]
 // (+Inf where c' + b̃_l > B) in the sphere order of u_old(i), UU_i[c'][l] = U_i[l, c' + b̃_l(i)] (uint16
@@ -69,15 +71,6 @@ __device__ unsigned long long g_sdt_stamps[4096][16];
     if (threadIdx.x == 0)                                                                    \
       for (int _q = 0; _q < 16; ++_q) g_sdt_stamps[blockIdx.x][_q] = sh.stamp[_q];           \
   } while (0)
-#define SD_TL(k) \
-  do {           \
-  } while (0)
-#define SD_TL_AT(gg, ii, ntt, k) \
-  do {                           \
-  } while (0)
-#define SD_TL_FLUSH(gg) \
-  do {                  \
-  } while (0)
 #elif defined(MIOC_STAMPS)
 // persistent-kernel timeline (diagnostic build, make stamps_tl): per workgroup (its chunk's first row) and for the 64
 // steps from nt/2 down, s_memrealtime (100 MHz) at 7 points of a row: 0 start, 1 loads consumed (h.early), 2 drain
@@ -98,34 +91,17 @@ __shared__ unsigned long long sd_tl_lds[64][8];
       for (int _j = 0; _j < 64; ++_j)                                                                     \
         for (int _q = 0; _q < 8; ++_q) g_sdt_tl[gg][_j][_q] = sd_tl_lds[_j][_q];                           \
   } while (0)
-#define SD_STAMP(k) \
-  do {              \
-  } while (0)
-#define SD_RSTAMP(k) \
-  do {               \
-  } while (0)
-#define SD_FLUSH() \
-  do {             \
-  } while (0)
-#else
-#define SD_TL(k) \
-  do {           \
-  } while (0)
-#define SD_TL_AT(gg, ii, ntt, k) \
-  do {                           \
-  } while (0)
-#define SD_TL_FLUSH(gg) \
-  do {                  \
-  } while (0)
-#define SD_STAMP(k) \
-  do {              \
-  } while (0)
-#define SD_RSTAMP(k) \
-  do {               \
-  } while (0)
-#define SD_FLUSH() \
-  do {             \
-  } while (0)
+#endif
+// what a build does not define is a no-op
+#ifndef SD_STAMP
+#define SD_STAMP(k) ((void)0)
+#define SD_RSTAMP(k) ((void)0)
+#define SD_FLUSH() ((void)0)
+#endif
+#ifndef SD_TL_AT
+#define SD_TL(k) ((void)0)
+#define SD_TL_AT(gg, ii, ntt, k) ((void)0)
+#define SD_TL_FLUSH(gg) ((void)0)
 #endif
 
 
@@ -317,12 +293,22 @@ struct SdtShared {
   // whose transform met a near tie and was redone counting them, flushed to [5]
   int cnt[4];
 };
+// The end of a launch (one lane): the workgroup's sh.cnt into the global counters.  `armed`: the driver's count for [4]
+// (k_sdt_run counts it in sh.cnt[2] -- by reference, read in its turn --, k_sdt_run1 forms it from nt, NB and the exit
+// step, the per-step driver has none).
+template <int NW>
+__device__ __forceinline__ void sd_add_counters(const SdtShared<NW> &sh, int32_t *counters, const int &armed) {
+  if (sh.cnt[0]) atomicAdd(&counters[0], sh.cnt[0]);
+  if (sh.cnt[1]) atomicAdd(&counters[1], sh.cnt[1]);
+  if (armed) atomicAdd(&counters[4], armed);
+  if (sh.cnt[3]) atomicAdd(&counters[5], sh.cnt[3]);
+}
 
 template <int M>
 __host__ __device__ constexpr size_t sd_slot_offset() {  // the two sphere-order slots follow the row body's arrays
   return ((size_t)1 << (3 * M)) * (2 * sizeof(double) + sizeof(uint16_t)) + SD_LCAP * sizeof(uint16_t);
 }
-// per wave: df(:, i) and u_old(:, i) (2M doubles), then one int32 flag (sphere-order reuse, SdPipe::go), padded to 16 B
+// per wave: df(:, i) and u_old(:, i) (2M doubles), then one int32 flag (sphere-order reuse, order_kept()), padded to 16 B
 template <int M>
 __host__ __device__ constexpr size_t sd_dfuo_stride() {
   return (2 * M + 2) * sizeof(double);
@@ -966,7 +952,7 @@ __device__ __forceinline__ int sdt_body(const ProblemDev &P, const LevelsDev &Lv
     for (int x = 0; x < 8; ++x) go[x] = INFINITY;
     if (tid == 0) {
       if (fin) go[0] = bv;
-      outv[l0] = go[0];  // a one-row workgroup's next item takes its distance-0 source from here (SdPipe::tail)
+      outv[l0] = go[0];  // a one-row workgroup's next item takes its distance-0 source from here (SdPipeBase::tail)
       sh.cnt[1] += 1;
     }
     const bool mine = fin && tid == (l0 >> 3);
@@ -1344,11 +1330,7 @@ __global__ __launch_bounds__(1 << (3 * M - 3)) void k_sdt_step(ProblemDev P, Lev
     sdt_body<M, false>(P, Lv, G, k, cp, i, valid, ein, slot, slot + L, Sout_all + (size_t)k * s_stride + (size_t)cp * L,
                        UU_all + (size_t)k * uu_stride_k + (size_t)i * ((size_t)(P.B + 1) * L) + (size_t)cp * L, sh,
                        sds, hooks, P.df, P.uold, 0);
-    if (tid == 0) {
-      if (sh.cnt[0]) atomicAdd(&counters[0], sh.cnt[0]);
-      if (sh.cnt[1]) atomicAdd(&counters[1], sh.cnt[1]);
-      if (sh.cnt[3]) atomicAdd(&counters[5], sh.cnt[3]);
-    }
+    if (tid == 0) sd_add_counters(sh, counters, 0);
   }
   SD_FLUSH();
 }
@@ -1630,20 +1612,23 @@ __device__ __forceinline__ int sd_flag_poll(const int32_t *p) {
                            __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The pipeline hooks of the persistent driver (the row body calls them, see sdt_body).
-template <int M>
-struct SdPipe {
+// The pipeline hooks of the persistent drivers (the row body calls them, see sdt_body).  SdPipeBase is what k_sdt_run
+// and k_sdt_run1 share: the launch's constants, the state carried from item to item, and every hook that does not
+// depend on which row comes next -- the hand-off (sc1 loads and stores, the late drain, the barrier, one lane's flag
+// store, the polling wave) is one piece of code for both.  D is the driver's own struct (SdPipe, SdPipe1): it adds
+// start(), early(), publish() and a go() that strings await_polls(), the next item's loads and issue_dma() together, and
+// names the next item -- next_cp(), next_i(), whole_row() (the next item reads this item's own row), loaded_flag() (this
+// row's `loaded`), lowc(), kOutOrderRegs and kRowClass.
+template <int M, class D>
+struct SdPipeBase {
   static constexpr int L = 1 << (3 * M);
-  static constexpr bool kOutOrderRegs = false;  // (see SdPipe1)
-  static constexpr bool kRowClass = false;      // (see SdPipe1)
-  // the current row (cp, step i) and the next one (ncp, step ni)
-  int cp, i, ncp, ni;
+  __device__ __forceinline__ const D &d() const { return *static_cast<const D *>(this); }
+  int cp, i;  // the current item: row cp of step i
   bool has_next;
   // constants of the launch
-  int lo, hi, B, nt, k, g0;
-  int war;  // nt - i - NB = token(i + NB - 1): the token this step's write-after-read waits need (stepped with i)
+  int nt, k, g0;
   unsigned spin_limit, rowb, bufb, r0b;
-  int32_t *dk, *lk, *err;
+  int32_t *dk, *lk, *err;  // the subproblem's `done` and `loaded` flags, the launch's error word
   const uint32_t *pk;
   uint32_t *slot;
   __amdgpu_buffer_rsrc_t rs;
@@ -1655,29 +1640,126 @@ struct SdPipe {
   uint16_t *sslot;     // (sd_strad) the two slots' seam lists in LDS
   unsigned char *sds;
   unsigned ldsb;  // sd_lds_addr(sds)
+  double *reg;    // the subproblem's region
+  SdtShared<(1 << (3 * M - 3)) / 64> *sh;
+  const ProblemDev *Pp;  // (for the next item's statistics phase, tail)
+  const PyrGeom *Gp;
+  // carried from item to item: this wave's polls, the next item's loads in flight
+  int32_t *fp;
+  int need, val;
+  SdRaw raw;
+  SdNext nx;  // the next item's sphere-order entries and seam (sd_read_next)
+  unsigned valid_next;  // the next item's statistics phase, run at the end of this one (tail): its result for sdt_body
+  unsigned nbo;     // byte offset of the next item's input buffer, (next_i() + 1) % NB (kept by the driver: no division)
+  unsigned sob;     // byte offset of this item's output row in the region (buffer i % NB, row cp)
+  bool stop_seen;   // sh.ctl's stop as read after the row's barrier 3 (publish)
+
   __device__ __forceinline__ unsigned lds_slot(int step) const {  // the sphere-order slot of `step`
     return ldsb + (unsigned)sd_slot_offset<M>() + (unsigned)(step & 1) * (unsigned)(L * sizeof(uint32_t));
   }
   __device__ __forceinline__ unsigned lds_sslot(int step) const {  // its seam lists
     return ldsb + (unsigned)sd_strad_offset<M>() + (unsigned)(step & 1) * (unsigned)(8 * SD_STRAD_N * sizeof(uint16_t));
   }
-  SdtShared<(1 << (3 * M - 3)) / 64> *sh;
-  // carried from row to row: the previous row (its `done` is published at this row's publish()), this wave's polls,
-  // the next row's loads in flight
-  int pcp, pi;
-  int32_t *fp;
-  int need, val;
-  SdRaw raw;
-  SdNext nx;  // the next row's sphere-order entries and seam (sd_read_next)
-  // the next row's statistics phase, run at the end of this row (tail): its result for the next sdt_body
-  const ProblemDev *Pp;
-  const PyrGeom *Gp;
-  unsigned valid_next;
-  int whole;  // one row per workgroup (hi - lo == 1)
-  unsigned nbo;     // byte offset of the next row's input buffer, (ni + 1) % NB (kept by the driver: no division)
-  unsigned sob;     // byte offset of this row's output row in the region (buffer i % NB, row cp)
-  bool stop_seen;   // sh.ctl's stop as read after the row's barrier 3 (publish)
+  // the head of go(), after the row's first barrier (every wave has consumed this row's loads): publish `loaded`; this
+  // wave waits until its polls match (re-polling), and only then does go() issue the next row's loads -- the
+  // measured-valid consumer form: the polling wave loads only after its own poll matched
+  __device__ __forceinline__ void await_polls() {
+    SD_TL_AT(g0, i, nt, 2);
+    const int tid = sd_tid();
+    // evaluated before the flag store below: the compiler's wait for `val` would otherwise cover that store
+    bool ready = __all(val >= need);
+    if (tid == 0) __hip_atomic_store(d().loaded_flag(), nt - 1 - i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned spins = 0;
+    while (!ready) {
+      if (sd_flag_poll(err) || ++spins > spin_limit) {
+        if ((tid & 63) == 0) {
+          __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          sh->ctl[0].stop = sh->ctl[1].stop = 1;  // read after the row's next barrier: the launch is abandoned
+        }
+        break;
+      }
+      __builtin_amdgcn_s_sleep(1);
+      val = sd_flag_poll(fp);
+      ready = __all(val >= need);
+    }
+    SD_TL_AT(g0, i, nt, 3);
+  }
+  // the reuse flag of the slot of step i+1: same2[i-1] = (u_old(i-1) == u_old(i+1)), copied with this step's df / u_old
+  // (the slot already holds the order of step i-1 then: the order is a function of u_old alone, k_pyr_order, and by
+  // induction every slot holds the order of the last step assigned to it)
+  // (an LDS load: through the generic pointer it was a flat load, whose vmcnt(0) wait made wave 0 wait for its own
+  // `loaded` flag store above to complete before issuing the next row's loads)
+  __device__ __forceinline__ int order_kept() const {
+    return *(const volatile __attribute__((address_space(3))) int32_t *)(
+        sds + sd_dfuo_offset<M>() + (threadIdx.x >> 6) * sd_dfuo_stride<M>() + 16 * M);
+  }
+  // behind the next row's loads (LDS-DMA, after them so that they do not wait for it): step ni's sphere order into the
+  // slot of step i+1 where the step is a new one and the slot does not hold it (`fresh`; every wave is past its last
+  // read of the slot: the barrier before go()), and the next row's df / u_old; all of it is older than this row's five
+  // stores, so the counted wait at the next row's start covers it
+  // (ni by reference: k_sdt_run passes its field, read at each use as when this block stood in its go(); as one value
+  // the compiler adds the LDS base to the seam-list address per item instead of once per launch)
+  __device__ __forceinline__ void issue_dma(const int &ni, bool fresh) {
+    if (fresh) {
+      sd_perm_dma_asm<M>(pk + (size_t)ni * L, lds_slot(ni));
+      if constexpr (sd_strad<M>()) sd_strad_dma(sk + (size_t)ni * 8 * SD_STRAD_N, lds_sslot(ni));
+    }
+    sd_dfuo_dma<M>(dfuo0 + (size_t)((unsigned)ni * dfuo_st), ni >= 1, ldsb);
+  }
+  // late in the row, before the barrier after the winners: this wave's stores of the previous row have landed (they
+  // have had the whole row: no wait), so after that barrier the previous row can be published
+  __device__ __forceinline__ void late_drain() {
+#ifdef SD_TL_DRAIN  // timeline builds: stamp 7 = the drain's start (instead of "loads taken" at the row start)
+    SD_TL_AT(g0, i, nt, 7);
+#endif
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    SD_TL_AT(g0, i, nt, 5);
+  }
+  // the row's `sc1` stores, through a resource of the row's own, formed here from the row's byte offset (the row's
+  // 64-bit address is not kept live across the body).  Stored through the region's resource `rs` with the offset as
+  // the instruction's scalar offset, rows were read stale by the rows above (DESIGN §3.5, round 7): not kept.
+  __device__ __forceinline__ void store16(double *, int e, unsigned long long lo, unsigned long long hi) {
+    sd_store16<true>(reg + sob / 8, L * 8, e, lo, hi);
+  }
+  // the next row's statistics phase (its loads landed at this row's late drain): after this row's outputs are final,
+  // before its stores.  Where the next item reads this item's own row (whole_row(): a one-row workgroup), that row's stores
+  // are not issued yet: the sphere-0 source at distance 0 (u_old(i) on the level grid: position 0 with b̃ = 0, lane 0 of
+  // wave 0) is this row's output, from the LDS (an off-grid u_old has b̃ >= 1 everywhere and no such source).
+  __device__ __forceinline__ void tail(bool empty, const double *outv) {
+    if (!has_next) return;
+    double v[8];
+    sd_take<M, D::kRowClass>(v, raw, d().lowc());
+    if (d().whole_row() && (sd_tid() & 63) == 0 && (raw.e[0].x >> 16) == 0)
+      v[0] = empty ? INFINITY : outv[raw.e[0].x & 0xFFFFu];
+    const double xs = __hiloint2double((int)raw.sv.y, (int)raw.sv.x);
+    valid_next = sdt_stats<M, true>(*Pp, *Gp, k, d().next_cp(), d().next_i(), v, raw.e, *sh, sds, nullptr, nullptr,
+                                    raw.srank, xs);
+  }
+};
 
+// k_sdt_run's hooks: any number of rows per workgroup, the next item re-derived per item from "which row is this"
+template <int M>
+struct SdPipe : SdPipeBase<M, SdPipe<M>> {
+  using Base = SdPipeBase<M, SdPipe<M>>;
+  using Base::cp, Base::i, Base::has_next, Base::nt, Base::g0, Base::dk, Base::lk, Base::sh, Base::fp, Base::need,
+      Base::val, Base::stop_seen, Base::L, Base::nx, Base::raw, Base::rs, Base::slot, Base::sslot, Base::nbo, Base::r0b,
+      Base::rowb;
+  static constexpr bool kOutOrderRegs = false;  // (see SdPipe1)
+  static constexpr bool kRowClass = false;      // (see SdPipe1)
+  __device__ __forceinline__ bool lowc() const { return true; }  // (not known per launch: the general form)
+  int ncp, ni;  // the next row (ncp, step ni)
+  int lo, hi, B;
+  int war;    // nt - i - NB = token(i + NB - 1): the token this step's write-after-read waits need (stepped with i)
+  int whole;  // one row per workgroup (hi - lo == 1)
+  int pcp, pi;  // the previous row (its `done` is published at this row's publish())
+  __device__ __forceinline__ int next_cp() const { return ncp; }
+  __device__ __forceinline__ int next_i() const { return ni; }
+  __device__ __forceinline__ bool whole_row() const { return whole != 0; }
+  __device__ __forceinline__ int32_t *loaded_flag() const { return lk + cp * SDT_FLAG_STRIDE; }
+
+  // (sd_pipe_setup's call) the write-after-read token only ever meets per-lane operands, the poll predicates: a vector
+  // register
+  __device__ __forceinline__ void start(int, int) { asm volatile("" : "+v"(war)); }
   // every wave polls its own dependency flags (lanes 0-31 RAW for the next row, 32-63 WAR for this row's stores; a
   // lane without one polls a flag that always passes -- every lane loads, no branch), once every wave has consumed
   // this row's loads (early()); checked in go()
@@ -1705,58 +1787,16 @@ struct SdPipe {
     // diagnostics [4]: this row reuses a staging buffer that a row above may still read (some WAR lane armed above)
     if (tid == 0 && war > 0 && min(cp + 7 * M, B) >= max(cp + 1, hi)) ++sh->cnt[2];
   }
-  // after the row's first barrier (every wave has consumed this row's loads): publish `loaded`; this wave waits until
-  // its polls match (re-polling), then issues the next row's loads -- the measured-valid consumer form: the polling
-  // wave loads only after its own poll matched
+  // the next row's loads (from the slot and the buffer of step ni + 1), then the DMAs
   __device__ __forceinline__ void go() {
-    SD_TL_AT(g0, i, nt, 2);
-    const int tid = sd_tid();
-    // evaluated before the flag store below: the compiler's wait for `val` would otherwise cover that store
-    bool ready = __all(val >= need);
-    if (tid == 0) __hip_atomic_store(lk + cp * SDT_FLAG_STRIDE, nt - 1 - i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned spins = 0;
-    while (!ready) {
-      if (sd_flag_poll(err) || ++spins > spin_limit) {
-        if ((tid & 63) == 0) {
-          __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          sh->ctl[0].stop = sh->ctl[1].stop = 1;  // read after the row's next barrier: the launch is abandoned
-        }
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-      val = sd_flag_poll(fp);
-      ready = __all(val >= need);
-    }
-    SD_TL_AT(g0, i, nt, 3);
-    // the next row's loads; then (LDS-DMA, after them so that they do not wait for it) the next step's sphere order
-    // into the slot of step i+1 (every wave is past its last read of it: the barrier before go()) and the next row's
-    // df / u_old; all of it is older than this row's five stores, so the counted wait at the next row's start covers it
+    this->await_polls();
     if (has_next) {
-      // the reuse flag of the slot: same2[i-1] = (u_old(i-1) == u_old(i+1)), copied with this step's df / u_old (the
-      // slot of step i+1 already holds the order of step ni = i-1 then: the order is a function of u_old alone,
-      // k_pyr_order, and by induction every slot holds the order of the last step assigned to it)
-      // (an LDS load: through the generic pointer it was a flat load, whose vmcnt(0) wait made wave 0 wait for its own
-      // `loaded` flag store above to complete before issuing the next row's loads)
-      const int same = *(const volatile __attribute__((address_space(3))) int32_t *)(
-          sds + sd_dfuo_offset<M>() + (threadIdx.x >> 6) * sd_dfuo_stride<M>() + 16 * M);
+      const int same = this->order_kept();
       sd_read_next<M>(nx, slot + ((ni + 1) & 1) * L, sslot + ((ni + 1) & 1) * 8 * SD_STRAD_N);
       sd_issue_pipe<M>(raw, rs, nx, ncp, nbo, r0b + (unsigned)(ni + 1) * rowb, rowb);
-      if (ni != i && !same) {
-        sd_perm_dma_asm<M>(pk + (size_t)ni * L, lds_slot(ni));
-        if constexpr (sd_strad<M>()) sd_strad_dma(sk + (size_t)ni * 8 * SD_STRAD_N, lds_sslot(ni));
-      }
-      sd_dfuo_dma<M>(dfuo0 + (size_t)((unsigned)ni * dfuo_st), ni >= 1, ldsb);
+      this->issue_dma(ni, ni != i && !same);
     }
     SD_TL_AT(g0, i, nt, 4);
-  }
-  // late in the row, before the barrier after the winners: this wave's stores of the previous row have landed (they
-  // have had the whole row: no wait), so after that barrier the previous row can be published
-  __device__ __forceinline__ void late_drain() {
-#ifdef SD_TL_DRAIN  // timeline builds: stamp 7 = the drain's start (instead of "loads taken" at the row start)
-    SD_TL_AT(g0, i, nt, 7);
-#endif
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    SD_TL_AT(g0, i, nt, 5);
   }
   __device__ __forceinline__ void publish(int stopped) {
     if (sd_tid() == 0 && pcp >= 0)
@@ -1768,26 +1808,69 @@ struct SdPipe {
     pcp = cp;
     pi = i;
   }
-  // the row's `sc1` stores, through a resource of the row's own, formed here from the row's byte offset (the row's
-  // 64-bit address is not kept live across the body).  Stored through the region's resource `rs` with the offset as
-  // the instruction's scalar offset, rows were read stale by the rows above (DESIGN §3.5, round 7): not kept.
-  __device__ __forceinline__ void store16(double *, int e, unsigned long long lo, unsigned long long hi) {
-    sd_store16<true>(reg + sob / 8, L * 8, e, lo, hi);
-  }
-  double *reg;  // the subproblem's region
-  // the next row's statistics phase (its loads landed at this row's late drain): after this row's outputs are final,
-  // before its stores.  A one-row workgroup's next row reads its own row of this step, whose stores are not issued yet:
-  // the sphere-0 source at distance 0 (u_old(i) on the level grid: position 0 with b̃ = 0, lane 0 of wave 0) is this
-  // row's output, from the LDS (an off-grid u_old has b̃ >= 1 everywhere and no such source).
-  __device__ __forceinline__ void tail(bool empty, const double *outv) {
-    if (!has_next) return;
-    double v[8];
-    sd_take<M>(v, raw);
-    if (whole && (sd_tid() & 63) == 0 && (raw.e[0].x >> 16) == 0) v[0] = empty ? INFINITY : outv[raw.e[0].x & 0xFFFFu];
-    const double xs = __hiloint2double((int)raw.sv.y, (int)raw.sv.x);
-    valid_next = sdt_stats<M, true>(*Pp, *Gp, k, ncp, ni, v, raw.e, *sh, sds, nullptr, nullptr, raw.srank, xs);
-  }
 };
+
+// What both persistent kernels do before their item loop, for subproblem k and the workgroup's first row cp0: the
+// launch's constants into the hooks, both sphere orders of the first step, df / u_old, the first item's loads (the
+// terminal row was written by an earlier launch) and its statistics phase (later items': the previous item's tail).
+template <int M, class H>
+__device__ __forceinline__ void sd_pipe_setup(H &h, const ProblemDev &P, const PyrGeom &G, int k, int cp0,
+                                              const uint32_t *perm_all, double *S_all, size_t kstride, int NB,
+                                              int32_t *flags, unsigned spin_limit, const double *df_all,
+                                              const double *uo_all, const int32_t *same2, const uint16_t *strad,
+                                              unsigned char *sds, SdtShared<(1 << (3 * M - 3)) / 64> &sh) {
+  constexpr int L = 1 << (3 * M);
+  const int R = P.B + 1, nt = P.nt;
+  // (each flag SDT_FLAG_STRIDE words apart)
+  const int FR = R * SDT_FLAG_STRIDE;
+  int32_t *done = flags, *loaded = flags + P.K * FR, *err = flags + 2 * P.K * FR;
+  uint32_t *slot = reinterpret_cast<uint32_t *>(sds + sd_slot_offset<M>());
+  // this subproblem's region: NB staging buffers of R rows, then row 0 of every step (k_sdt_row0); one buffer
+  // resource over all of it (the host checks it is below 4 GiB)
+  double *reg = S_all + (size_t)k * kstride;
+  h.cp = cp0, h.nt = nt, h.k = k, h.g0 = k * R + cp0;
+  h.spin_limit = spin_limit, h.rowb = (unsigned)L * 8u, h.bufb = (unsigned)R * h.rowb, h.r0b = (unsigned)NB * h.bufb;
+  asm volatile("" : "+v"(err));  // (only the timeout path reads it: a vector register)
+  h.dk = done + (size_t)k * FR, h.lk = loaded + (size_t)k * FR, h.err = err;
+  h.pk = perm_all + (size_t)k * nt * L, h.slot = slot;
+  h.rs = __builtin_amdgcn_make_buffer_rsrc(reg, 0, (int)(h.r0b + (unsigned)nt * h.rowb), 0x00020000);
+  h.dfuo0 = sd_dfuo_src<M>(df_all + (size_t)k * nt * M, uo_all + (size_t)k * nt * M, same2 + (size_t)k * nt - 1);
+  h.dfuo_st = sd_dfuo_step<M>();
+  h.sds = sds, h.ldsb = sd_lds_addr(sds), h.sh = &sh;
+  h.sk = strad ? strad + (size_t)k * nt * 8 * SD_STRAD_N : nullptr;
+  h.sslot = reinterpret_cast<uint16_t *>(sds + sd_strad_offset<M>());
+  // only ever added to per-lane offsets (the LDS-DMA sources; the flags a lane polls or stores)
+  asm volatile("" : "+v"(h.pk), "+v"(h.sk), "+v"(h.dk), "+v"(h.lk));
+  // likewise the row-0 array's offset in the load addressing, which only ever meets per-lane operands
+  asm volatile("" : "+v"(h.r0b));
+  h.start(P.B, NB);  // the driver's own part
+  h.reg = reg;
+  if (threadIdx.x == 0) {
+    sh.ctl[0].stop = sh.ctl[1].stop = 0;
+    sh.cnt[0] = sh.cnt[1] = sh.cnt[2] = sh.cnt[3] = 0;
+    sh.ctl[0].nlist = sh.ctl[1].nlist = sh.ctl[0].redo = sh.ctl[1].redo = 0;
+  }
+  sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 1) * L, h.lds_slot(nt - 1));
+  sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 2) * L, h.lds_slot(nt - 2));
+  if constexpr (sd_strad<M>()) {
+    sd_strad_dma(h.sk + (size_t)(nt - 1) * 8 * SD_STRAD_N, h.lds_sslot(nt - 1));
+    sd_strad_dma(h.sk + (size_t)(nt - 2) * 8 * SD_STRAD_N, h.lds_sslot(nt - 2));
+  }
+  sd_dfuo_dma<M>(h.dfuo0 + (size_t)((unsigned)(nt - 2) * h.dfuo_st), nt >= 3, h.ldsb);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  sd_bar();
+  sd_read_next<M>(h.nx, h.slot + ((nt - 1) & 1) * L, h.sslot + ((nt - 1) & 1) * 8 * SD_STRAD_N);
+  sd_issue_pipe<M, H::kRowClass>(h.raw, h.rs, h.nx, cp0, (unsigned)((nt - 1) % NB) * h.bufb,
+                                 h.r0b + (unsigned)(nt - 1) * h.rowb, h.rowb, h.lowc());
+  // a wait the compiler sees (vmcnt(0), other counters untouched): entering the loop with these loads pending would
+  // make it assume, at the loop head, that nothing younger can be outstanding, and wait for every store there
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  h.Pp = &P, h.Gp = &G;
+  double v[8];
+  sd_take<M, H::kRowClass>(v, h.raw, h.lowc());
+  const double xs = __hiloint2double((int)h.raw.sv.y, (int)h.raw.sv.x);
+  h.valid_next = sdt_stats<M, true>(P, G, k, cp0, nt - 2, v, h.raw.e, sh, sds, df_all, uo_all, h.raw.srank, xs);
+}
 
 template <int M>
 __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P_arg, LevelsDev Lv_arg, PyrGeom G,
@@ -1802,83 +1885,34 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P_ar
   constexpr int L = 1 << (3 * M);
   extern __shared__ __attribute__((aligned(16))) unsigned char sds[];
   __shared__ SdtShared<(1 << (3 * M - 3)) / 64> sh;
-  // Δt, β and 1/β are read by double-precision VALU instructions only: held in vector registers across the row loop
-  // (the loop's scalar registers are all taken; as scalars these six were spilled to lanes and read back every row)
   ProblemDev P = P_arg;
   LevelsDev Lv = Lv_arg;
+  // Δt, β and 1/β are read by double-precision VALU instructions only: held in vector registers across the row loop
+  // (the loop's scalar registers are all taken; as scalars these six were spilled to lanes and read back every row)
   asm volatile("" : "+v"(P.dt), "+v"(Lv.beta), "+v"(Lv.inv_beta));
-  // likewise what only the timeout path and the epilogue read: the error word, the spin limit, the counters
+  // likewise what only the timeout path and the epilogue read: the spin limit, the counters (the error word:
+  // sd_pipe_setup).  Both stand before the early return: below it they changed the item loop's code
   asm volatile("" : "+v"(counters), "+v"(spin_limit));
-  const int B = P.B, R = B + 1, nt = P.nt, tid = threadIdx.x;
-  // (each flag SDT_FLAG_STRIDE words apart)
-  const int FR = R * SDT_FLAG_STRIDE;
-  int32_t *done = flags, *loaded = flags + P.K * FR, *err = flags + 2 * P.K * FR;
+  const int B = P.B, R = B + 1, nt = P.nt;
   const int W = nwg / P.K;  // workgroups per subproblem (the host guarantees 1 <= W <= B)
   const int k = (int)blockIdx.x / W, wl = (int)blockIdx.x - k * W;
   if (k >= P.K) return;
   const int base = B / W, extra = B - base * W;  // rows 1..B, the longer chunks highest
   const int lo = 1 + wl * base + max(0, wl - (W - extra)), hi = lo + base + (wl >= W - extra ? 1 : 0);
   __builtin_assume(lo < hi);  // W <= B: every chunk has a row
-  uint32_t *slot = reinterpret_cast<uint32_t *>(sds + sd_slot_offset<M>());
-  auto pslot = [&](int step) { return slot + (step & 1) * L; };  // sphere order of `step`
-  // this subproblem's region: NB staging buffers of R rows, then row 0 of every step (k_sdt_row0); one buffer
-  // resource over all of it (the host checks it is below 4 GiB)
-  double *reg = S_all + (size_t)k * kstride;
   SdPipe<M> h;
-  h.lo = lo, h.hi = hi, h.B = B, h.war = 2 - NB, h.nt = nt, h.k = k, h.g0 = k * R + lo;
-  h.spin_limit = spin_limit, h.rowb = (unsigned)L * 8u, h.bufb = (unsigned)R * h.rowb, h.r0b = (unsigned)NB * h.bufb;
-  asm volatile("" : "+v"(err));
-  h.dk = done + (size_t)k * FR, h.lk = loaded + (size_t)k * FR, h.err = err;
-  h.pk = perm_all + (size_t)k * nt * L, h.slot = slot;
-  h.rs = __builtin_amdgcn_make_buffer_rsrc(reg, 0, (int)(h.r0b + (unsigned)nt * h.rowb), 0x00020000);
-  h.dfuo0 = sd_dfuo_src<M>(df_all + (size_t)k * nt * M, uo_all + (size_t)k * nt * M, same2 + (size_t)k * nt - 1);
-  h.dfuo_st = sd_dfuo_step<M>();
-  h.sds = sds, h.ldsb = sd_lds_addr(sds), h.sh = &sh;
-  h.sk = strad ? strad + (size_t)k * nt * 8 * SD_STRAD_N : nullptr;
-  h.sslot = reinterpret_cast<uint16_t *>(sds + sd_strad_offset<M>());
-  // only ever added to per-lane offsets (the LDS-DMA sources; the flags a lane polls or stores)
-  asm volatile("" : "+v"(h.pk), "+v"(h.sk), "+v"(h.dk), "+v"(h.lk));
-  // likewise two values that only ever meet per-lane operands (the row-0 array's offset in the load addressing, the
-  // write-after-read token in the poll predicates)
-  asm volatile("" : "+v"(h.r0b), "+v"(h.war));
-  h.reg = reg;
+  h.lo = lo, h.hi = hi, h.B = B, h.war = 2 - NB, h.whole = hi - lo == 1;
   h.pcp = -1, h.pi = 0;
-  if (tid == 0) {
-    sh.ctl[0].stop = sh.ctl[1].stop = 0;
-    sh.cnt[0] = sh.cnt[1] = sh.cnt[2] = sh.cnt[3] = 0;
-    sh.ctl[0].nlist = sh.ctl[1].nlist = sh.ctl[0].redo = sh.ctl[1].redo = 0;
-  }
-  // prologue: both sphere orders of the first step, df / u_old, and the first row's loads (the terminal row was
-  // written by an earlier launch)
-  sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 1) * L, h.lds_slot(nt - 1));
-  sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 2) * L, h.lds_slot(nt - 2));
-  if constexpr (sd_strad<M>()) {
-    sd_strad_dma(h.sk + (size_t)(nt - 1) * 8 * SD_STRAD_N, h.lds_sslot(nt - 1));
-    sd_strad_dma(h.sk + (size_t)(nt - 2) * 8 * SD_STRAD_N, h.lds_sslot(nt - 2));
-  }
-  sd_dfuo_dma<M>(h.dfuo0 + (size_t)((unsigned)(nt - 2) * h.dfuo_st), nt >= 3, h.ldsb);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  sd_bar();
-  sd_read_next<M>(h.nx, pslot(nt - 1), h.sslot + ((nt - 1) & 1) * 8 * SD_STRAD_N);
-  sd_issue_pipe<M>(h.raw, h.rs, h.nx, lo, (unsigned)((nt - 1) % NB) * h.bufb, h.r0b + (unsigned)(nt - 1) * h.rowb,
-                   h.rowb);
-  // a wait the compiler sees (vmcnt(0), other counters untouched): entering the loop with these loads pending would
-  // make it assume, at the loop head, that nothing younger can be outstanding, and wait for every store there
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  h.Pp = &P, h.Gp = &G, h.whole = hi - lo == 1;
-  {  // the first row's statistics phase (later rows': the previous row's tail)
-    double v[8];
-    sd_take<M>(v, h.raw);
-    const double xs = __hiloint2double((int)h.raw.sv.y, (int)h.raw.sv.x);
-    h.valid_next = sdt_stats<M, true>(P, G, k, lo, nt - 2, v, h.raw.e, sh, sds, df_all, uo_all, h.raw.srank, xs);
-  }
+  sd_pipe_setup<M>(h, P, G, k, lo, perm_all, S_all, kstride, NB, flags, spin_limit, df_all, uo_all, same2, strad, sds,
+                   sh);
+  auto pslot = [&](int step) { return h.slot + (step & 1) * L; };  // sphere order of `step`
   int par = 0;     // the row's parity (sdt_body's LDS slots)
   bool stop = false;
   // the staging buffers of steps i and i + 1 (i % NB, (i + 1) % NB), stepped down with i instead of divided per row
   int bi = (nt - 2) % NB, bi1 = (nt - 1) % NB;
   // the U rows of step i (stepped down with i: R·L < 2^28 elements, the host bounds a staging buffer below 2^31 bytes)
   uint16_t *uu_i = UU_all + (size_t)k * uu_stride_k + (size_t)(nt - 2) * ((size_t)R * L);
-  asm volatile("" : "+v"(uu_i));  // (only ever added to a lane's offset: a vector register pair, as h.pk above)
+  asm volatile("" : "+v"(uu_i));  // (only ever added to a lane's offset: a vector register pair, as h.pk)
 #pragma nounroll
   for (int i = nt - 2; i >= 0 && !stop; --i) {
 #pragma nounroll
@@ -1915,20 +1949,14 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P_ar
     uu_i = reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(uu_i) - rows * (unsigned)(L * sizeof(uint16_t)));
     ++h.war;
   }
-  if (sd_tid() == 0) {
-    if (sh.cnt[0]) atomicAdd(&counters[0], sh.cnt[0]);
-    if (sh.cnt[1]) atomicAdd(&counters[1], sh.cnt[1]);
-    if (sh.cnt[2]) atomicAdd(&counters[4], sh.cnt[2]);
-    if (sh.cnt[3]) atomicAdd(&counters[5], sh.cnt[3]);
-  }
+  if (sd_tid() == 0) sd_add_counters(sh, counters, sh.cnt[2]);
   SD_FLUSH();
   SD_TL_FLUSH(h.g0);
 }
 
 // ---- the one-row driver ----------------------------------------------------------------------------------
 // The persistent driver for W = B: every workgroup owns one row c' for the whole launch (the headline shape, B rows on
-// at least B CUs).  The hand-off is k_sdt_run's, instruction for instruction (sc1 loads and stores, the late drain, the
-// barrier, one lane's flag store, the polling wave, the counted row start); what differs is what k_sdt_run re-derives
+// at least B CUs).  The hand-off is k_sdt_run's (SdPipeBase, sd_pipe_setup); what differs is what k_sdt_run re-derives
 // per item from "which row is this": with c' fixed the next item is always (c', i - 1), so
 //   * each lane's poll address is fixed and its token steps by one per item (early() is "step the token, poll");
 //     diagnostics [4] -- items whose write-after-read wait was armed -- is arithmetic in nt and NB, formed at exit;
@@ -1940,50 +1968,38 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run(ProblemDev P_ar
 //     derives the same per item from per-lane data: the load offsets and sd_take (lowc), the one-target test and the
 //     winners' `valid` (highc).  One loop, one row start; the loads and stores sit behind the branches, not in them.
 template <int M>
-struct SdPipe1 {
-  static constexpr int L = 1 << (3 * M);
+struct SdPipe1 : SdPipeBase<M, SdPipe1<M>> {
+  using Base = SdPipeBase<M, SdPipe1<M>>;
+  using Base::cp, Base::i, Base::has_next, Base::nt, Base::g0, Base::fp, Base::need, Base::val, Base::stop_seen,
+      Base::L, Base::nx, Base::raw, Base::rs, Base::slot, Base::sslot, Base::nbo, Base::r0b, Base::rowb;
   static constexpr bool kOutOrderRegs = true;
   // the row's class is fixed for the launch: the row body and the loads branch on it (workgroup-uniform scalar compares
   // on c' and B) instead of deriving it per item from per-lane data
   static constexpr bool kRowClass = true;
   __device__ __forceinline__ bool lowc() const { return cp <= 7 * M; }  // a source row c' - b̃ may be below 0
-  int cp, i;  // the row (fixed) and the current step; the next item is (cp, i - 1)
-  bool has_next;
-  int nt, k, g0;
-  unsigned spin_limit, rowb, r0b;
-  int32_t *lflag, *dflag, *err;  // loaded[k][cp], done[k][cp], the launch's error word
-  const uint32_t *pk;
-  uint32_t *slot;
-  __amdgpu_buffer_rsrc_t rs;
-  const char *dfuo0;
-  unsigned dfuo_st;
-  const uint16_t *sk;
-  uint16_t *sslot;
-  unsigned char *sds;
-  unsigned ldsb;
-  __device__ __forceinline__ unsigned lds_slot(int step) const {
-    return ldsb + (unsigned)sd_slot_offset<M>() + (unsigned)(step & 1) * (unsigned)(L * sizeof(uint32_t));
-  }
-  __device__ __forceinline__ unsigned lds_sslot(int step) const {
-    return ldsb + (unsigned)sd_strad_offset<M>() + (unsigned)(step & 1) * (unsigned)(8 * SD_STRAD_N * sizeof(uint16_t));
-  }
-  SdtShared<(1 << (3 * M - 3)) / 64> *sh;
+  int32_t *lflag, *dflag;  // loaded[k][cp], done[k][cp]
+  // the row is fixed: the next item is (cp, i - 1), which reads this item's own row
+  __device__ __forceinline__ int next_cp() const { return cp; }
+  __device__ __forceinline__ int next_i() const { return i - 1; }
+  __device__ __forceinline__ bool whole_row() const { return true; }
+  __device__ __forceinline__ int32_t *loaded_flag() const { return lflag; }
+
   // this lane's poll, set up once (lanes 0-31: done[cp - s], token(i) = nt - 1 - i, armed while there is a next item;
   // lanes 32-63: loaded[cp + s], token(i + NB - 1) -- not positive until the ring wraps, and every flag is >= 0, so it
   // needs no arming; a lane without a neighbour polls the row's own `loaded` against INT32_MIN, which a step per item
-  // leaves far below zero)
-  int32_t *fp;
-  int need, val;
-  SdRaw raw;
-  SdNext nx;
-  const ProblemDev *Pp;
-  const PyrGeom *Gp;
-  unsigned valid_next;
-  unsigned nbo;  // byte offset of buffer i % NB: this item's output buffer and the next item's input buffer
-  unsigned sob;  // byte offset of this row's output row in the region
-  bool stop_seen;
-  double *reg;
-
+  // leaves far below zero): fp and its token before the first item, which early() steps
+  __device__ __forceinline__ void start(int B, int NB) {
+    const int lane = threadIdx.x & 63, s = lane < 32 ? lane + 1 : lane - 31;
+    lflag = this->lk + cp * SDT_FLAG_STRIDE, dflag = this->dk + cp * SDT_FLAG_STRIDE;
+    fp = lflag;
+    need = INT32_MIN;
+    if (lane < 32) {
+      if (s <= 7 * M && cp - s >= 1) fp = this->dk + (cp - s) * SDT_FLAG_STRIDE, need = 0;  // token(nt - 2) - 1
+    } else {
+      if (s <= 7 * M && cp + s <= B) fp = this->lk + (cp + s) * SDT_FLAG_STRIDE, need = 1 - NB;  // token(nt + NB - 3) - 1
+    }
+    asm volatile("" : "+v"(lflag), "+v"(dflag));
+  }
   // step the token, poll
   __device__ __forceinline__ void early() {
     SD_TL_AT(g0, i, nt, 1);
@@ -1992,68 +2008,26 @@ struct SdPipe1 {
     val = sd_flag_poll(fp);
   }
   __device__ __forceinline__ void go() {
-    SD_TL_AT(g0, i, nt, 2);
-    const int tid = sd_tid();
-    // evaluated before the flag store below: the compiler's wait for `val` would otherwise cover that store
-    bool ready = __all(val >= need);
-    if (tid == 0) __hip_atomic_store(lflag, nt - 1 - i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned spins = 0;
-    while (!ready) {
-      if (sd_flag_poll(err) || ++spins > spin_limit) {
-        if ((tid & 63) == 0) {
-          __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          sh->ctl[0].stop = sh->ctl[1].stop = 1;
-        }
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-      val = sd_flag_poll(fp);
-      ready = __all(val >= need);
-    }
-    SD_TL_AT(g0, i, nt, 3);
+    this->await_polls();
     // this lane's entries of slot(i): the next item's input order and this item's output order (the gather reads them
     // from raw.e), so they are read on the last item too
     sd_read_next<M>(nx, slot + (i & 1) * L, sslot + (i & 1) * 8 * SD_STRAD_N);
     if (has_next) {
-      const int ni = i - 1;
-      const int same = *(const volatile __attribute__((address_space(3))) int32_t *)(
-          sds + sd_dfuo_offset<M>() + (threadIdx.x >> 6) * sd_dfuo_stride<M>() + 16 * M);
+      const int same = this->order_kept();
       sd_issue_pipe<M, true>(raw, rs, nx, cp, nbo, r0b + (unsigned)i * rowb, rowb, lowc());
-      if (!same) {
-        sd_perm_dma_asm<M>(pk + (size_t)ni * L, lds_slot(ni));
-        if constexpr (sd_strad<M>()) sd_strad_dma(sk + (size_t)ni * 8 * SD_STRAD_N, lds_sslot(ni));
-      }
-      sd_dfuo_dma<M>(dfuo0 + (size_t)((unsigned)ni * dfuo_st), ni >= 1, ldsb);
+      const int ni = i - 1;  // always a new step
+      this->issue_dma(ni, !same);
     } else {
 #pragma unroll
       for (int q = 0; q < 4; ++q) raw.e[q] = nx.e[q];
     }
     SD_TL_AT(g0, i, nt, 4);
   }
-  __device__ __forceinline__ void late_drain() {
-#ifdef SD_TL_DRAIN
-    SD_TL_AT(g0, i, nt, 7);
-#endif
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    SD_TL_AT(g0, i, nt, 5);
-  }
   // the previous item (cp, i + 1) is done: token(i + 1)
   __device__ __forceinline__ void publish(int stopped) {
     if (sd_tid() == 0 && i != nt - 2)
       __hip_atomic_store(dflag, nt - 2 - i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    stop_seen = stopped != 0;
-  }
-  __device__ __forceinline__ void store16(double *, int e, unsigned long long lo, unsigned long long hi) {
-    sd_store16<true>(reg + sob / 8, L * 8, e, lo, hi);
-  }
-  // as SdPipe::tail for a one-row workgroup
-  __device__ __forceinline__ void tail(bool empty, const double *outv) {
-    if (!has_next) return;
-    double v[8];
-    sd_take<M, true>(v, raw, lowc());
-    if ((sd_tid() & 63) == 0 && (raw.e[0].x >> 16) == 0) v[0] = empty ? INFINITY : outv[raw.e[0].x & 0xFFFFu];
-    const double xs = __hiloint2double((int)raw.sv.y, (int)raw.sv.x);
-    valid_next = sdt_stats<M, true>(*Pp, *Gp, k, cp, i - 1, v, raw.e, *sh, sds, nullptr, nullptr, raw.srank, xs);
+    stop_seen = stopped != 0;  // (see SdPipe::publish)
   }
 };
 
@@ -2071,79 +2045,21 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run1(ProblemDev P_a
   constexpr int L = 1 << (3 * M);
   extern __shared__ __attribute__((aligned(16))) unsigned char sds[];
   __shared__ SdtShared<(1 << (3 * M - 3)) / 64> sh;
-  // (vector registers for what only meets per-lane or double-precision operands: as k_sdt_run)
   ProblemDev P = P_arg;
   LevelsDev Lv = Lv_arg;
+  // (vector registers for what only meets per-lane or double-precision operands: as k_sdt_run)
   asm volatile("" : "+v"(P.dt), "+v"(Lv.beta), "+v"(Lv.inv_beta));
   asm volatile("" : "+v"(counters), "+v"(spin_limit));
-  const int B = P.B, R = B + 1, nt = P.nt, tid = threadIdx.x;
-  const int FR = R * SDT_FLAG_STRIDE;
-  int32_t *done = flags, *loaded = flags + P.K * FR, *err = flags + 2 * P.K * FR;
+  const int B = P.B, R = B + 1, nt = P.nt;
   const int k = (int)blockIdx.x / B, cp = 1 + (int)blockIdx.x - k * B;  // nwg = K·B: one row per workgroup
   if (k >= P.K) return;
-  (void)nwg;
-  uint32_t *slot = reinterpret_cast<uint32_t *>(sds + sd_slot_offset<M>());
-  auto pslot = [&](int step) { return slot + (step & 1) * L; };
-  double *reg = S_all + (size_t)k * kstride;
   SdPipe1<M> h;
-  h.cp = cp, h.nt = nt, h.k = k, h.g0 = k * R + cp;
-  h.spin_limit = spin_limit, h.rowb = (unsigned)L * 8u;
-  const unsigned bufb = (unsigned)R * h.rowb;
-  h.r0b = (unsigned)NB * bufb;
-  asm volatile("" : "+v"(err));
-  h.err = err;
-  h.pk = perm_all + (size_t)k * nt * L, h.slot = slot;
-  h.rs = __builtin_amdgcn_make_buffer_rsrc(reg, 0, (int)(h.r0b + (unsigned)nt * h.rowb), 0x00020000);
-  h.dfuo0 = sd_dfuo_src<M>(df_all + (size_t)k * nt * M, uo_all + (size_t)k * nt * M, same2 + (size_t)k * nt - 1);
-  h.dfuo_st = sd_dfuo_step<M>();
-  h.sds = sds, h.ldsb = sd_lds_addr(sds), h.sh = &sh;
-  h.sk = strad ? strad + (size_t)k * nt * 8 * SD_STRAD_N : nullptr;
-  h.sslot = reinterpret_cast<uint16_t *>(sds + sd_strad_offset<M>());
-  {  // the polls, once: this lane's flag and its token before the first item (early() steps it)
-    int32_t *dk = done + (size_t)k * FR, *lk = loaded + (size_t)k * FR;
-    h.lflag = lk + cp * SDT_FLAG_STRIDE, h.dflag = dk + cp * SDT_FLAG_STRIDE;
-    const int lane = tid & 63, s = lane < 32 ? lane + 1 : lane - 31;
-    h.fp = h.lflag;
-    h.need = INT32_MIN;
-    if (lane < 32) {
-      if (s <= 7 * M && cp - s >= 1) h.fp = dk + (cp - s) * SDT_FLAG_STRIDE, h.need = 0;  // token(nt - 2) - 1
-    } else {
-      if (s <= 7 * M && cp + s <= B) h.fp = lk + (cp + s) * SDT_FLAG_STRIDE, h.need = 1 - NB;  // token(nt + NB - 3) - 1
-    }
-    asm volatile("" : "+v"(h.lflag), "+v"(h.dflag));
-  }
-  asm volatile("" : "+v"(h.pk), "+v"(h.sk));
-  asm volatile("" : "+v"(h.r0b));
-  h.reg = reg;
-  if (tid == 0) {
-    sh.ctl[0].stop = sh.ctl[1].stop = 0;
-    sh.cnt[0] = sh.cnt[1] = sh.cnt[2] = sh.cnt[3] = 0;
-    sh.ctl[0].nlist = sh.ctl[1].nlist = sh.ctl[0].redo = sh.ctl[1].redo = 0;
-  }
-  // prologue (as k_sdt_run): both sphere orders of the first step, df / u_old, the first item's loads
-  sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 1) * L, h.lds_slot(nt - 1));
-  sd_perm_dma_asm<M>(h.pk + (size_t)(nt - 2) * L, h.lds_slot(nt - 2));
-  if constexpr (sd_strad<M>()) {
-    sd_strad_dma(h.sk + (size_t)(nt - 1) * 8 * SD_STRAD_N, h.lds_sslot(nt - 1));
-    sd_strad_dma(h.sk + (size_t)(nt - 2) * 8 * SD_STRAD_N, h.lds_sslot(nt - 2));
-  }
-  sd_dfuo_dma<M>(h.dfuo0 + (size_t)((unsigned)(nt - 2) * h.dfuo_st), nt >= 3, h.ldsb);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  sd_bar();
-  sd_read_next<M>(h.nx, pslot(nt - 1), h.sslot + ((nt - 1) & 1) * 8 * SD_STRAD_N);
-  sd_issue_pipe<M, true>(h.raw, h.rs, h.nx, cp, (unsigned)((nt - 1) % NB) * bufb,
-                         h.r0b + (unsigned)(nt - 1) * h.rowb, h.rowb, h.lowc());
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // (vmcnt(0), seen by the compiler: see k_sdt_run)
-  h.Pp = &P, h.Gp = &G;
-  {
-    double v[8];
-    sd_take<M, true>(v, h.raw, h.lowc());
-    const double xs = __hiloint2double((int)h.raw.sv.y, (int)h.raw.sv.x);
-    h.valid_next = sdt_stats<M, true>(P, G, k, cp, nt - 2, v, h.raw.e, sh, sds, df_all, uo_all, h.raw.srank, xs);
-  }
+  sd_pipe_setup<M>(h, P, G, k, cp, perm_all, S_all, kstride, NB, flags, spin_limit, df_all, uo_all, same2, strad, sds,
+                   sh);
+  auto pslot = [&](int step) { return h.slot + (step & 1) * L; };
   // buffer i % NB's byte offset and the row's U row of step i, stepped down with i
-  const unsigned cprow = (unsigned)cp * h.rowb, wrapb = (unsigned)(NB - 1) * bufb;
-  h.nbo = (unsigned)((nt - 2) % NB) * bufb;
+  const unsigned cprow = (unsigned)cp * h.rowb, wrapb = (unsigned)(NB - 1) * h.bufb;
+  h.nbo = (unsigned)((nt - 2) % NB) * h.bufb;
   uint16_t *uu_i = UU_all + (size_t)k * uu_stride_k + (size_t)(nt - 2) * ((size_t)R * L) + (size_t)cp * L;
   asm volatile("" : "+v"(uu_i));
   int par = 0;
@@ -2170,23 +2086,18 @@ __global__ __launch_bounds__(1 << (3 * M - 3), 2) void k_sdt_run1(ProblemDev P_a
     par ^= 1;
     SD_TL(6);
     stop = h.stop_seen;
-    h.nbo = h.nbo == 0 ? wrapb : h.nbo - bufb;
+    h.nbo = h.nbo == 0 ? wrapb : h.nbo - h.bufb;
     unsigned rows = (unsigned)R;
     asm volatile("" : "+s"(rows));
     uu_i = reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(uu_i) - rows * (unsigned)(L * sizeof(uint16_t)));
   }
-  if (sd_tid() == 0) {
-    if (sh.cnt[0]) atomicAdd(&counters[0], sh.cnt[0]);
-    if (sh.cnt[1]) atomicAdd(&counters[1], sh.cnt[1]);
-    // diagnostics [4]: the items run (steps above i) whose write-after-read wait was armed: token(i' + NB - 1) > 0, i.e.
-    // i' < nt - NB, on a row with a row above it
-    const int armed = cp < B ? max(nt - NB - 1 - i, 0) : 0;
-    if (armed) atomicAdd(&counters[4], armed);
-    if (sh.cnt[3]) atomicAdd(&counters[5], sh.cnt[3]);
-  }
+  // diagnostics [4]: the items run (steps above i) whose write-after-read wait was armed: token(i' + NB - 1) > 0, i.e.
+  // i' < nt - NB, on a row with a row above it
+  if (sd_tid() == 0) sd_add_counters(sh, counters, cp < B ? max(nt - NB - 1 - i, 0) : 0);
   SD_FLUSH();
   SD_TL_FLUSH(h.g0);
 }
+
 
 bool sdt_seam_lists(const PyrGeom &G) { return G.M == 4 && sd_strad<4>(); }
 
