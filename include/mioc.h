@@ -663,6 +663,9 @@ int32_t mioc_mixed_poll(mioc_ctx *ctx, void *d_mstate, void *d_trm_state, int32_
  * (the reference's 2..nt) and a uniformly random admissible level per segment.  jumps < 0: floor(nt / 10), the
  * reference's default.  The stream is counter-based (seed, restart, draw), so a seed reproduces its controls on
  * any device; it is not Julia's MersenneTwister stream (not reproducible outside Julia).  Enqueued.
+ * 1 <= nt <= 516096: the kernel keeps one bit per step and 256 counts in LDS, ((nt + 31)/32 + 256) * 4 bytes, and
+ * 516096 is the largest nt for which that fits the 64 KB a launch gets; a larger nt, like jumps > nt - 1, is
+ * MIOC_EINVAL before anything is launched.
  */
 int32_t mioc_rand_start_device(mioc_ctx *ctx, int64_t K, int64_t nt, int64_t jumps, uint64_t seed, double *d_u_out);
 

@@ -1087,7 +1087,9 @@ int32_t mioc_rand_start_device(mioc_ctx *ctx, int64_t K, int64_t nt, int64_t jum
   if (!ctx) return MIOC_EINVAL;
   MIOC_JOIN_BT(ctx);
   if (!ctx->have_levels) return fail(ctx, MIOC_ESTATE, "levels must be set first");
-  if (K < 1 || K > INT32_MAX || nt < 1 || nt > (1 << 24) || !d_u_out) return fail(ctx, MIOC_EINVAL, "bad K / nt / u");
+  if (K < 1 || K > INT32_MAX || nt < 1 || !d_u_out) return fail(ctx, MIOC_EINVAL, "bad K / nt / u");
+  // k_rand_start keeps one bit per step and 256 counts in LDS: the 64 KB a launch gets without asking for more
+  if (nt > kRandStartMaxNt) return fail(ctx, MIOC_EINVAL, "nt > 516096: the jump-time bitmap does not fit 64 KB of LDS");
   if (jumps < 0) jumps = nt / 10;
   if (jumps > nt - 1) return fail(ctx, MIOC_EINVAL, "jumps > nt - 1 (the reference's sample would throw)");
   HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -319,6 +319,10 @@ hipError_t launch_trm_decide(hipStream_t s, int K, const double *J_old, const do
                              const double *tv_new, const double *pred, double beta, double sigma, double *ared,
                              int32_t *decision);
 
+// dynamic LDS of k_rand_start: one bit per step in 32-bit words, then one count per thread of its 256
+constexpr size_t rand_start_lds(int64_t nt) { return ((size_t)(nt + 31) / 32 + 256) * sizeof(uint32_t); }
+constexpr int64_t kRandStartMaxNt = (65536 / 4 - 256) * 32;  // the largest nt with rand_start_lds(nt) <= 64 KB
+static_assert(rand_start_lds(kRandStartMaxNt) == 65536 && rand_start_lds(kRandStartMaxNt + 1) > 65536, "LDS bound");
 hipError_t launch_rand_start(hipStream_t s, int K, int nt, int jumps, uint64_t seed, const LevelsDev &Lv, double *U);
 // device-resident TRM control (mioc_trm.hip): the state block's layout and flag bits, shared with the mixed control
 // (mioc_mixed.hip), which reads and clears the stop flag

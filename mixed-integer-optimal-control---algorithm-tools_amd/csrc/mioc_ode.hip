@@ -250,7 +250,8 @@ __global__ __launch_bounds__(256) void k_rand_start(int nt, int jumps, uint64_t 
 }  // namespace
 
 hipError_t launch_rand_start(hipStream_t s, int K, int nt, int jumps, uint64_t seed, const LevelsDev &Lv, double *U) {
-  const size_t lds = ((size_t)(nt + 31) / 32 + 256) * sizeof(uint32_t);
+  if (nt > kRandStartMaxNt) return hipErrorInvalidValue;  // the entry rejects these: more LDS than a launch gets
+  const size_t lds = rand_start_lds(nt);
   hipLaunchKernelGGL(k_rand_start, dim3(K), dim3(256), lds, s, nt, jumps, seed, Lv, U);
   return hipGetLastError();
 }

@@ -132,33 +132,7 @@ def test_device_trust_region_iteration_equals_host():
 
 
 # ---- rand_func_int on the device (HelpFunctions.jl:204-225) -------------------------------------------------------
-_M64 = (1 << 64) - 1
-
-
-def _mix(z):
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    return z ^ (z >> 31)
-
-
-def _uniform(key, stream, idx, n):
-    v = _mix(key ^ ((stream << 56) & _M64) ^ idx)
-    return ((v >> 32) * n) >> 32
-
-
-def _rand_start_host(levels, nt, jumps, seed, k):
-    """Host restatement of k_rand_start's stream (test-only): Floyd's sample of the jump times, a level per segment."""
-    key = _mix((seed + 0x9E3779B97F4A7C15 * (k + 1)) & _M64)
-    N, S = nt - 1, set()
-    for q, j in enumerate(range(N - jumps + 1, N + 1)):
-        t = 1 + _uniform(key, 1, q, j)
-        S.add(j if t in S else t)
-    u = np.zeros((levels.M, nt))
-    seg = 0
-    for i in range(nt):
-        seg += i in S
-        u[:, i] = levels.nuval[_uniform(key, 2, seg, levels.L)]
-    return u, S
+from ode_cases import rand_start_host as _rand_start_host  # noqa: E402  (the host restatement of the stream)
 
 
 @pytest.mark.parametrize("shape", ["sos1", "c5", "c4"])

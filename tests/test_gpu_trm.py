@@ -164,6 +164,106 @@ def test_decide_edge_cases():
     ctx.close()
 
 
+# ---- pred on the table kinds: TV(u_old) through trm_rank / the key sum, TV(u) through ranks[] and nuval -------------
+_PRED_NU = [[-1, 0, 2, 3], [0, 1, 2]]   # a product grid whose first list has a hole at 1
+_PRED_B, _PRED_DT, _PRED_BETA, _PRED_K = 6, 0.01, 1e-3, 3
+
+
+def _pred_inputs(nt, k, hole):
+    """Restart k: Gaussian df, u_old on the grid; hole: the middle step (and the last, from nt = 3) of u_old's first
+    control is 1 -- integral, off the grid, and at most 2 from every level of its list."""
+    lt = LevelTable(_PRED_NU, product_iterator(_PRED_NU))
+    rng = np.random.default_rng(7919 * nt + k)
+    df = rng.standard_normal((2, nt))
+    uo = np.ascontiguousarray(lt.nuval[rng.integers(0, lt.L, size=nt)].T, dtype=np.float64)
+    if hole:
+        uo[0, nt // 2] = 1.0
+        if nt >= 3:
+            uo[0, nt - 1] = 1.0
+    return lt, df, uo
+
+
+def _pred_expect(lt, pk, pint, tab, df, uo, u, fma):
+    eto = tv_p_kind(uo, pk, pint, tab, _olv(lt))
+    etn = tv_p_kind(u, pk, pint, tab, _olv(lt))
+    eiv, epr = pred_py(df, uo, u, _PRED_DT, _PRED_BETA, eto, etn, fma=fma)
+    return eiv, eto, etn, epr
+
+
+@pytest.mark.parametrize("nt", [1, 2, 2047, 2048, 2049])
+@pytest.mark.parametrize("p", [2, 3, 1.5])
+def test_pred_paths_at_table_kinds(p, nt):
+    """mioc_pred and mioc_pred_batch_device (K = 3 different inputs) after bellman / backtrack at B and B // 2, with
+    MIOC_OPT_PRED_FMA 0 and 1, under MIOC_P_INTLUT (p = 2, 3) and MIOC_P_TABLE (p = 1.5): all four outputs bit for bit
+    as tv_p_kind / pred_py.  nt = 1: no TV term; 2047 / 2048 / 2049: around the 2048-step LDS chunk of the fold (and
+    2047 = 8 * 255 + 7 leaves the unrolled fold a tail).  For the integer p, u_old passes through the hole of the first
+    list: off the grid, inside the weight table."""
+    import torch
+    lt = LevelTable(_PRED_NU, product_iterator(_PRED_NU))
+    pk, pint, tab = native.cost_spec(p, levels=lt)
+    assert pk == (P_TABLE if p == 1.5 else P_INTLUT)
+    data = [_pred_inputs(nt, k, hole=pk == P_INTLUT)[1:] for k in range(_PRED_K)]
+    if pk == P_INTLUT:
+        assert all(np.any(uo[0] == 1.0) for _, uo in data)
+    ctx = native.Context(0)
+    ctx.set_levels(lt)
+    ctx.set_cost(p, _PRED_BETA)
+    # the single-subproblem entry on restart 0
+    df, uo = data[0]
+    ctx.bellman(df, uo, _PRED_B, _PRED_DT)
+    moved = 0
+    for Bu in (_PRED_B, _PRED_B // 2):
+        u, _, _ = ctx.backtrack(Bu)
+        moved += int(np.any(u != uo))
+        for fma in (0, 1):
+            ctx.set_option(native.MIOC_OPT_PRED_FMA, fma)
+            assert ctx.pred() == _pred_expect(lt, pk, pint, tab, df, uo, u, bool(fma)), (Bu, fma)
+    assert moved == 2, "the trial equals u_old: int_val would be an empty sum"
+    # the batch entry on all three
+    ddf = torch.tensor(np.ascontiguousarray(np.stack([d.T for d, _ in data])), dtype=torch.float64, device="cuda")
+    duo = torch.tensor(np.ascontiguousarray(np.stack([o.T for _, o in data])), dtype=torch.float64, device="cuda")
+    ctx.bellman_batch_tensors(ddf, duo, _PRED_B, _PRED_DT)
+    du = torch.empty_like(ddf)
+    for Bu in (_PRED_B, _PRED_B // 2):
+        ctx.backtrack_batch_tensors(Bu, du)
+        for fma in (0, 1):
+            ctx.set_option(native.MIOC_OPT_PRED_FMA, fma)
+            outs = [torch.full((_PRED_K,), math.nan, dtype=torch.float64, device="cuda") for _ in range(4)]
+            ctx.pred_batch_tensors(*outs)
+            ctx.synchronize()
+            got = [o.cpu().numpy() for o in outs]
+            u = du.cpu().numpy()
+            for k, (df, uo) in enumerate(data):
+                want = _pred_expect(lt, pk, pint, tab, df, uo, u[k].T, bool(fma))
+                assert tuple(float(g[k]) for g in got) == want, (Bu, fma, k)
+    ctx.close()
+
+
+def test_pred_table_kind_rejects_off_grid_u_old():
+    """p = 1.5 (MIOC_P_TABLE) with the u_old that the integer p accept: bellman and backtrack admit it (u_old is
+    integral), TV(u_old) has no table entry for it -- the TV_p error from pred, from the batch entry at the next
+    synchronize, and a KeyError from the oracle's restatement."""
+    import torch
+    lt, df, uo = _pred_inputs(64, 0, hole=True)
+    pk, pint, tab = native.cost_spec(1.5, levels=lt)
+    with pytest.raises(KeyError):
+        tv_p_kind(uo, pk, pint, tab, _olv(lt))
+    ctx = native.Context(0)
+    ctx.set_levels(lt)
+    ctx.set_cost(1.5, _PRED_BETA)
+    ctx.bellman(df, uo, _PRED_B, _PRED_DT)
+    ctx.backtrack(_PRED_B)
+    with pytest.raises(native.MiocNativeError, match="TV_p"):
+        ctx.pred()
+    t = lambda a: torch.tensor(np.ascontiguousarray(a.T[None]), dtype=torch.float64, device="cuda")  # noqa: E731
+    ctx.bellman_batch_tensors(t(df), t(uo), _PRED_B, _PRED_DT)
+    ctx.backtrack_batch_tensors(_PRED_B, torch.empty(1, 64, 2, dtype=torch.float64, device="cuda"))
+    ctx.pred_batch_tensors(*[torch.empty(1, dtype=torch.float64, device="cuda") for _ in range(4)])
+    with pytest.raises(native.MiocNativeError, match="TV_p"):
+        ctx.synchronize()
+    ctx.close()
+
+
 def test_pred_errors():
     """Integer p with an off-grid u_old whose jump key exceeds the host table, and pred before a backtrack."""
     cfg = dataclasses.replace(CONFIGS["C5"], p=2)
