@@ -524,6 +524,64 @@ int32_t mioc_ode_eval_device(mioc_ctx *ctx, int32_t problem, int64_t K, const do
  *   NULL, d_params NULL with nparams > 0, d_data NULL with ndata > 0, and a program compiled with scen == 0.  The three
  *   older eval entries refuse a scenario program (MIOC_EINVAL).  A refused call leaves the context usable.
  *
+ * Sensitivities.  mioc_ode_program_create_sens(..., scen, sens, ...) makes the gradient of J in the numbers the caller
+ * put into params and state0 an output of an evaluation: sens bit MIOC_ODE_SENS_P for dJ/dparams, MIOC_ODE_SENS_Y0 for
+ * dJ/dstate0.  The head #defines MIOC_SENS <sens> behind MIOC_SCEN* only when sens != 0; every piece of the skeleton
+ * that serves it is a macro that is empty without it, so with sens == 0 the text is _create_scen's byte for byte and
+ * such a program is the program it was.  mioc_ode_program_create_scen(...) is _sens(..., sens = 0, ...).  The four
+ * integrators with an exact discrete adjoint carry it; MIOC_ODE_INT_EULER does not: the reference scheme's df is its
+ * own adjoint formula and not the derivative of its trapezoid J, so a parameter gradient consistent with it is not
+ * defined (sens != 0 with Euler is MIOC_EINVAL).
+ *   outputs    the kernel takes two more pointers behind d_Y: d_Jp, K x nparams doubles [k][e] = dJ_k/dp_e, and d_Jy0,
+ *              K x ny doubles [k][r] = dJ_k/dstate0_r.  Plain derivatives: no division by tau.  Only the nparams
+ *              parameters are differentiated; the data entries p[NP + e] are not.  With scenarios restart q's rows are
+ *              the derivatives in scenario q % S's own parameters and state0.  A restart whose Newton iteration fails
+ *              (implicit schemes) has NaN in both rows, no other restart is affected.  They must not overlap the
+ *              other arrays.
+ *   sweep      the backward sweep runs when any of d_df, d_Jp, d_Jy0 is given: the forward sweep stores its states and
+ *              the scratch is grown under the same condition; df is stored only with d_df.  After the sweep the vector
+ *              w the adjoint carries is dJ/dstate0.  dJ/dparams is one more accumulator beside xbar, pbar, which is
+ *              never reset between intervals.  With both pointers NULL J, df and Y are the sens == 0 program's bit for
+ *              bit, and df does not change when d_Jp or d_Jy0 is added.
+ *   hooks      with MIOC_ODE_SENS_P the text also defines (unless derived)
+ *                __device__ void Fp(const double *p, int i, double t, const double *y, const double *x, double (*fp)[NP]);
+ *                __device__ void Gp(const double *p, int i, double t, const double *y, const double *x, double *gp);
+ *                __device__ void Ep(const double *p, double t, const double *y, double *ep);     MIOC_ODE_TERMINAL only
+ *              fp[r][e] = dF_r/dp_e, gp[e] = dG/dp_e, ep[e] = dE/dp_e, e < NP.  fp, gp and ep are zeroed once per
+ *              evaluation like fu and gu: an entry written once is written always.  Fp and Gp are called only when d_Jp
+ *              is given, after Fy, Gy, Fu, Gu (in this order: Fy, Gy, Fu, Gu, Fp, Gp) with the same (i, t, y, x) and the
+ *              same data row: every stage s = S..1 of every substep backwards (Heun, RK4), the stored stage state of
+ *              every substep backwards (backward Euler, midpoint).  Ep is called once when d_Jp is given, after Ey, at
+ *              the last state with the data of column nt-1 and the end time t that E sees.
+ *   derived    the derive bits MIOC_ODE_DERIVE_FP / _GP / _EP (only with MIOC_ODE_SENS_P; _EP only with
+ *              MIOC_ODE_TERMINAL; none is part of MIOC_ODE_DERIVE_ALL) generate Fp, Gp, Ep by forward-mode AD.  A
+ *              function named by one of them (F by _FP, G by _GP, E by _EP) is a template over the state type and the
+ *              parameter type,
+ *                template <class T, class P> __device__ void F(const P *p, int i, double t, const T *y, const T *x, T *f);
+ *                template <class T, class P> __device__ T    G(const P *p, int i, double t, const T *y, const T *x);
+ *                template <class T, class P> __device__ T    E(const P *p, double t, const T *y);
+ *              and so every helper that takes p.  The skeleton and the other generated hooks call it with P = double
+ *              as before: the same expressions, the same bits.  The generated Fp / Gp / Ep call it once with
+ *              P = T = mioc_ad::Dual<NP>: p[e] = (p_e, e-th unit tangent) for e < NP; the data entries p[NP + e], y and
+ *              x carry zero tangents; every output entry is written.  The head #defines MIOC_DERIVE_FP / _GP / _EP 1
+ *              for `#ifndef` guards; a hook both written by hand and derived is MIOC_ECOMPILE; the second
+ *              (MIOC_AD_NOINLINE) compile applies to them too.  The dual type needs no new rule.
+ *   rounding   every sum left to right, no contraction; pbar[e] = 0.0 at the start of the sweep, or ep[e] with
+ *              MIOC_ODE_TERMINAL and d_Jp;
+ *                Heun / RK4, stage s:  pbar[e] = pbar[e] + (((fp[0][e]*kbar_s[0] + fp[1][e]*kbar_s[1]) + ...) + (b_s h)*gp[e])
+ *                theta schemes:        pbar[e] = pbar[e] + (((fp[0][e]*mu[0] + fp[1][e]*mu[1]) + ...) + h*gp[e])
+ *                after substep 0:      d_Jp[k*NP + e] = pbar[e];   d_Jy0[k*NY + r] = w[r]
+ *   MIOC_EINVAL from _create_sens and _source_sens: sens bits outside 3; sens != 0 with MIOC_ODE_INT_EULER;
+ *              MIOC_ODE_SENS_P with nparams == 0 or ny * nparams > 64 (fp lives in registers); a _FP / _GP / _EP bit
+ *              without MIOC_ODE_SENS_P; _EP without MIOC_ODE_TERMINAL (and every case of _create_scen).
+ * mioc_ode_program_eval_sens_device is the body of every eval entry.  S == 0: the program has no scenarios, state0 and
+ *   params are host arrays and the checks are those of mioc_ode_program_eval_bolza_device; S >= 1: a scenario program,
+ *   state0 and params are device arrays and the checks are those of mioc_ode_program_eval_scen_device.  MIOC_EINVAL
+ *   also for d_Jp on a program without MIOC_ODE_SENS_P, d_Jy0 on one without MIOC_ODE_SENS_Y0, and S not matching the
+ *   program's scen.  The four older eval entries accept a sens program and give no sensitivities.  Gate, stream and
+ *   error behaviour as for mioc_ode_program_eval_scen_device: a closed gate leaves d_Jp and d_Jy0 untouched, a refused
+ *   call leaves the context usable.
+ *
  * mioc_ode_program_create needs no context and no GPU: it compiles for gfx950 and keeps the code object.  Limits:
  *   1 <= ny <= 8, 1 <= nx <= 8, 0 <= nparams <= 32, source text of at most 1 MiB (else MIOC_EINVAL).  A compile
  *   failure returns MIOC_ECOMPILE; the compiler's log (also the warnings of a successful compile) is copied into
@@ -588,6 +646,19 @@ int32_t mioc_ode_program_create_scen(const char *hooks, int32_t ny, int32_t nx, 
 int64_t mioc_ode_program_source_scen(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
                                      int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t scen,
                                      int32_t noinline, char *text, int64_t text_cap);
+/* _create_scen and _source_scen for a program that can return dJ/dparams and dJ/dstate0 (see "Sensitivities" above);
+ * sens == 0 is _create_scen, and _source_scen's text byte for byte. */
+#define MIOC_ODE_SENS_P   1      /* sens: dJ/dparams; the text defines Fp, Gp (and Ep with a terminal cost) unless derived */
+#define MIOC_ODE_SENS_Y0  2      /* sens: dJ/dstate0 */
+#define MIOC_ODE_DERIVE_FP 32    /* derive bits, valid only with MIOC_ODE_SENS_P; not part of MIOC_ODE_DERIVE_ALL */
+#define MIOC_ODE_DERIVE_GP 64
+#define MIOC_ODE_DERIVE_EP 128   /* only with MIOC_ODE_TERMINAL */
+int32_t mioc_ode_program_create_sens(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
+                                     int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t scen,
+                                     int32_t sens, mioc_ode_program **out, char *log, int64_t log_cap);
+int64_t mioc_ode_program_source_sens(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
+                                     int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t scen,
+                                     int32_t sens, int32_t noinline, char *text, int64_t text_cap);
 int32_t mioc_ode_program_destroy(mioc_ode_program *prog);
 int32_t mioc_ode_program_eval_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t K, const double *d_x, int64_t nt,
                                      double T0, double T1, const double *state0, const double *params, double *d_J,
@@ -646,6 +717,10 @@ int32_t mioc_ode_program_eval_scen_device(mioc_ctx *ctx, mioc_ode_program *prog,
                                           const double *d_x, int64_t nt, double T0, double T1, int64_t S,
                                           const double *d_state0, const double *d_params, const double *d_data,
                                           double *d_J, double *d_df, double *d_Y);
+int32_t mioc_ode_program_eval_sens_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K,
+                                          const double *d_x, int64_t nt, double T0, double T1, int64_t S,
+                                          const double *state0, const double *params, const double *d_data,
+                                          double *d_J, double *d_df, double *d_Y, double *d_Jp, double *d_Jy0);
 int32_t mioc_rows_copy_device(mioc_ctx *ctx, int64_t K, int64_t nt, double *d_dst, int64_t dst_nx, int64_t dst_row0,
                               const double *d_src, int64_t src_nx, int64_t src_row0, int64_t nrows);
 int64_t mioc_mixed_state_bytes(int64_t K);

@@ -405,6 +405,57 @@ function ode_program_eval_scen_device!(ctx::Context, prog::Ptr{Cvoid}, nu::Integ
     nothing
 end
 
+# ---- sensitivities: dJ/dparams and dJ/dstate0 as outputs of an evaluation (include/mioc.h, "Sensitivities").  Thin
+# wrappers of the two entries, like those of the scenarios; they have not been run under Julia.
+const MIOC_ODE_SENS_P = Int32(1)
+const MIOC_ODE_SENS_Y0 = Int32(2)
+const MIOC_ODE_DERIVE_FP = Int32(32)
+const MIOC_ODE_DERIVE_GP = Int32(64)
+const MIOC_ODE_DERIVE_EP = Int32(128)
+
+"""
+    ode_program_create_sens(hooks, ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen, sens) -> Ptr{Cvoid}
+
+mioc_ode_program_create_sens with the C entry's own integer arguments (`sens`: `MIOC_ODE_SENS_P`, `MIOC_ODE_SENS_Y0` or
+both; 0 is `ode_program_create_scen`; not with the integrator `:euler`).  With `MIOC_ODE_SENS_P` the text also defines
+Fp, Gp (and Ep with a terminal cost), or `derive` carries `MIOC_ODE_DERIVE_FP` / `_GP` / `_EP` and F, G, E are
+templates over the state type and the parameter type.
+"""
+function ode_program_create_sens(hooks::String, ny::Integer, nx::Integer, nparams::Integer, ndata::Integer,
+                                 integrator::Integer, substeps::Integer, derive::Integer, flags::Integer,
+                                 scen::Integer, sens::Integer)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    log = zeros(UInt8, 1 << 16)
+    rc = ccall((:mioc_ode_program_create_sens, libmioc), Int32,
+               (Cstring, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Ptr{Ptr{Cvoid}},
+                Ptr{UInt8}, Int64), hooks, ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen, sens, r,
+               log, length(log))
+    rc == MIOC_OK || error("mioc_ode_program_create_sens failed with $rc:\n" * unsafe_string(pointer(log)))
+    r[]
+end
+
+"""
+    ode_program_eval_sens_device!(ctx, prog, nu, K, d_x, nt, T0, T1, S, state0, params, d_data, d_J, d_df, d_Y,
+                                  d_Jp, d_Jy0)
+
+The eval entry with the sensitivities (mioc_ode_program_eval_sens_device): `d_Jp` K × nparams and `d_Jy0` K × ny
+doubles on the device, each or C_NULL.  `S = 0`: a program without scenarios, `state0` and `params` are host
+`Vector{Float64}` as for `ode_program_eval_bolza_device!`; `S ≥ 1`: a scenario program, they are device pointers as for
+`ode_program_eval_scen_device!`, and restart q's rows are the derivatives in scenario q % S's own values.
+"""
+function ode_program_eval_sens_device!(ctx::Context, prog::Ptr{Cvoid}, nu::Integer, K::Integer, d_x::Ptr{Float64},
+                                       nt::Integer, T0::Float64, T1::Float64, S::Integer,
+                                       state0::Union{Vector{Float64},Ptr{Float64}},
+                                       params::Union{Vector{Float64},Ptr{Float64}}, d_data::Ptr{Float64},
+                                       d_J::Ptr{Float64}, d_df::Ptr{Float64}, d_Y::Ptr{Float64}, d_Jp::Ptr{Float64},
+                                       d_Jy0::Ptr{Float64})
+    check(ctx, ccall((:mioc_ode_program_eval_sens_device, libmioc), Int32,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Float64, Float64, Int64, Ptr{Float64},
+                      Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                     ctx.ptr, prog, nu, K, d_x, nt, T0, T1, S, state0, params, d_data, d_J, d_df, d_Y, d_Jp, d_Jy0))
+    nothing
+end
+
 # ---- mixed controls: nu continuous controls in front of the DP's integer ones (include/mioc.h, "Mixed controls").
 # Thin wrappers of the six entries; they have not been run under Julia (none is installed where this was written).
 

@@ -9,7 +9,8 @@
 // so libmioc.so carries no link-time dependency on it and loads as before where it is absent.
 //
 // The assembled text: the head's #defines (NY, NX, NP; NS, the stage count, for Heun / RK4 or TH, theta, for the
-// implicit schemes; ND, MIOC_TERMINAL, MIOC_STATES, MIOC_SCEN, MIOC_SCEN_DATA and MIOC_DERIVE_* only when asked for),
+// implicit schemes; ND, MIOC_TERMINAL, MIOC_STATES, MIOC_SCEN, MIOC_SCEN_DATA, MIOC_SENS and MIOC_DERIVE_* only when
+// asked for),
 // the dual type kAdPrelude
 // (derive != 0), the caller's text, the generated hooks kAdHooks (derive != 0), then kSkeletonHead and the integrator's
 // body: kBodyEuler, kBodyRK (Heun, RK4) or kBodyTheta (backward Euler, implicit midpoint).  A program that does not ask
@@ -34,7 +35,7 @@ namespace {
 
 using namespace mioc_kernel_text;
 
-constexpr int kMaxNY = 8, kMaxNX = 8, kMaxNP = 32, kMaxND = 16, kMaxSubsteps = 64;
+constexpr int kMaxNY = 8, kMaxNX = 8, kMaxNP = 32, kMaxND = 16, kMaxSubsteps = 64, kMaxFp = 64;
 constexpr size_t kMaxSource = 1u << 20;
 const char *const kKernelName = "mioc_ode_program_kernel";
 const char *const kNoinlineNote =
@@ -126,7 +127,7 @@ std::string without_remarks(const std::string &log) {
 }  // namespace
 
 struct mioc_ode_program {
-  int ny = 0, nx = 0, np = 0, nd = 0, flags = 0, scen = 0;
+  int ny = 0, nx = 0, np = 0, nd = 0, flags = 0, scen = 0, sens = 0;
   int integrator = MIOC_ODE_INT_EULER, substeps = 1;
   std::vector<char> code;  // the gfx950 code object
   struct Loaded {
@@ -142,7 +143,7 @@ namespace {
 
 // What a program is compiled from, besides the caller's text.
 struct ProgramSpec {
-  int ny, nx, np, nd, integrator, substeps, derive, flags, scen;
+  int ny, nx, np, nd, integrator, substeps, derive, flags, scen, sens;
   bool euler() const { return integrator == MIOC_ODE_INT_EULER; }
   bool implicit() const { return integrator == MIOC_ODE_INT_BEULER || integrator == MIOC_ODE_INT_MIDPOINT; }
 };
@@ -154,8 +155,13 @@ int validate(const ProgramSpec &s, const char *hooks, size_t *len) {
   if (!s.euler() && s.integrator != MIOC_ODE_INT_HEUN && s.integrator != MIOC_ODE_INT_RK4 && !s.implicit())
     return MIOC_EINVAL;
   if (s.substeps < 1 || s.substeps > kMaxSubsteps || (s.euler() && s.substeps != 1)) return MIOC_EINVAL;
-  if (s.derive & ~(MIOC_ODE_DERIVE_ALL | MIOC_ODE_DERIVE_EY)) return MIOC_EINVAL;
-  if ((s.derive & MIOC_ODE_DERIVE_EY) && !(s.flags & MIOC_ODE_TERMINAL)) return MIOC_EINVAL;
+  constexpr int kDeriveP = MIOC_ODE_DERIVE_FP | MIOC_ODE_DERIVE_GP | MIOC_ODE_DERIVE_EP;
+  if (s.derive & ~(MIOC_ODE_DERIVE_ALL | MIOC_ODE_DERIVE_EY | kDeriveP)) return MIOC_EINVAL;
+  if ((s.derive & (MIOC_ODE_DERIVE_EY | MIOC_ODE_DERIVE_EP)) && !(s.flags & MIOC_ODE_TERMINAL)) return MIOC_EINVAL;
+  // sensitivities: not for the reference's Euler scheme; fp[NY][NP] lives in registers
+  if ((s.sens & ~(MIOC_ODE_SENS_P | MIOC_ODE_SENS_Y0)) || (s.sens && s.euler())) return MIOC_EINVAL;
+  if ((s.sens & MIOC_ODE_SENS_P) && (s.np == 0 || s.ny * s.np > kMaxFp)) return MIOC_EINVAL;
+  if ((s.derive & kDeriveP) && !(s.sens & MIOC_ODE_SENS_P)) return MIOC_EINVAL;
   // per-scenario data need per-scenario state0 and parameters, and data
   if ((s.scen & ~(MIOC_ODE_SCEN | MIOC_ODE_SCEN_DATA)) || s.scen == MIOC_ODE_SCEN_DATA) return MIOC_EINVAL;
   if ((s.scen & MIOC_ODE_SCEN_DATA) && s.nd == 0) return MIOC_EINVAL;
@@ -188,12 +194,16 @@ std::string assemble(const ProgramSpec &s, const char *hooks, size_t len, bool n
   if (s.flags & MIOC_ODE_STATES) define("MIOC_STATES", "1");
   if (s.scen & MIOC_ODE_SCEN) define("MIOC_SCEN", "1");
   if (s.scen & MIOC_ODE_SCEN_DATA) define("MIOC_SCEN_DATA", "1");
+  if (s.sens) define("MIOC_SENS", std::to_string(s.sens));
   if (s.derive) {  // the guard macros and the dual type in front of the caller's text; derive == 0 adds no byte
     if (s.derive & MIOC_ODE_DERIVE_FY) define("MIOC_DERIVE_FY", "1");
     if (s.derive & MIOC_ODE_DERIVE_FU) define("MIOC_DERIVE_FU", "1");
     if (s.derive & MIOC_ODE_DERIVE_GY) define("MIOC_DERIVE_GY", "1");
     if (s.derive & MIOC_ODE_DERIVE_GU) define("MIOC_DERIVE_GU", "1");
     if (s.derive & MIOC_ODE_DERIVE_EY) define("MIOC_DERIVE_EY", "1");
+    if (s.derive & MIOC_ODE_DERIVE_FP) define("MIOC_DERIVE_FP", "1");
+    if (s.derive & MIOC_ODE_DERIVE_GP) define("MIOC_DERIVE_GP", "1");
+    if (s.derive & MIOC_ODE_DERIVE_EP) define("MIOC_DERIVE_EP", "1");
     src += "#line 1 \"mioc_ad\"";
     src += kAdPrelude;
   }
@@ -290,10 +300,17 @@ int32_t mioc_ode_program_create_bolza(const char *hooks, int32_t ny, int32_t nx,
 int32_t mioc_ode_program_create_scen(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
                                      int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t scen,
                                      mioc_ode_program **out, char *log, int64_t log_cap) {
+  return mioc_ode_program_create_sens(hooks, ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen, 0, out,
+                                      log, log_cap);
+}
+
+int32_t mioc_ode_program_create_sens(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
+                                     int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t scen,
+                                     int32_t sens, mioc_ode_program **out, char *log, int64_t log_cap) {
   put_log(log, log_cap, "", 0);
   if (!out) return MIOC_EINVAL;
   *out = nullptr;
-  const ProgramSpec spec{ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen};
+  const ProgramSpec spec{ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen, sens};
   size_t len = 0;
   if (validate(spec, hooks, &len) != MIOC_OK) return MIOC_EINVAL;
   const Rtc &R = rtc();
@@ -306,7 +323,7 @@ int32_t mioc_ode_program_create_scen(const char *hooks, int32_t ny, int32_t nx, 
   // each however many stages call it.
   try {
     std::unique_ptr<mioc_ode_program> p(new mioc_ode_program);
-    p->ny = ny, p->nx = nx, p->np = nparams, p->nd = ndata, p->flags = flags, p->scen = scen;
+    p->ny = ny, p->nx = nx, p->np = nparams, p->nd = ndata, p->flags = flags, p->scen = scen, p->sens = sens;
     p->integrator = integrator, p->substeps = substeps;
     bool over = false;
     int ret = compile(assemble(spec, hooks, len, false), derive != 0, "", &p->code, &over, log, log_cap);
@@ -329,8 +346,15 @@ int64_t mioc_ode_program_source(const char *hooks, int32_t ny, int32_t nx, int32
 int64_t mioc_ode_program_source_scen(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
                                      int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t scen,
                                      int32_t noinline, char *text, int64_t text_cap) {
+  return mioc_ode_program_source_sens(hooks, ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen, 0,
+                                      noinline, text, text_cap);
+}
+
+int64_t mioc_ode_program_source_sens(const char *hooks, int32_t ny, int32_t nx, int32_t nparams, int32_t ndata,
+                                     int32_t integrator, int32_t substeps, int32_t derive, int32_t flags, int32_t scen,
+                                     int32_t sens, int32_t noinline, char *text, int64_t text_cap) {
   put_log(text, text_cap, "", 0);
-  const ProgramSpec spec{ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen};
+  const ProgramSpec spec{ny, nx, nparams, ndata, integrator, substeps, derive, flags, scen, sens};
   size_t len = 0;
   if (validate(spec, hooks, &len) != MIOC_OK) return MIOC_EINVAL;
   try {
@@ -362,10 +386,12 @@ int32_t mioc_ode_program_destroy(mioc_ode_program *prog) {
 // The body of every eval entry.  nu = 0: every control is the DP's (mioc_ode_program_eval_device); nu >= 1: the first
 // nu controls are continuous and the levels describe the other nx - nu (mioc_ode_program_eval_mixed_device).  S = 0:
 // state0 and params are host arrays, passed by value to a program without scenarios; S >= 1: they are the device
-// arrays of S scenarios for a program compiled with them (mioc_ode_program_eval_scen_device).
+// arrays of S scenarios for a program compiled with them (mioc_ode_program_eval_scen_device).  d_Jp, d_Jy0: the
+// sensitivities of a program compiled with them (mioc_ode_program_eval_sens_device), NULL from every other entry.
 static int32_t program_eval(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K, const double *d_x, int64_t nt,
                             double T0, double T1, int64_t S, const double *state0, const double *params,
-                            const double *d_data, double *d_J, double *d_df, double *d_Y) {
+                            const double *d_data, double *d_J, double *d_df, double *d_Y, double *d_Jp = nullptr,
+                            double *d_Jy0 = nullptr) {
   if (!ctx) return MIOC_EINVAL;
   MIOC_JOIN_BT(ctx);
   if (!prog) return fail(ctx, MIOC_EINVAL, "no ODE program");
@@ -379,6 +405,10 @@ static int32_t program_eval(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, i
   if (prog->nd > 0 && !d_data) return fail(ctx, MIOC_EINVAL, "the program reads sampled data: d_data missing");
   if (d_Y && !(prog->flags & MIOC_ODE_STATES))
     return fail(ctx, MIOC_EINVAL, "the program was not created with MIOC_ODE_STATES");
+  if (d_Jp && !(prog->sens & MIOC_ODE_SENS_P))
+    return fail(ctx, MIOC_EINVAL, "the program was not created with MIOC_ODE_SENS_P");
+  if (d_Jy0 && !(prog->sens & MIOC_ODE_SENS_Y0))
+    return fail(ctx, MIOC_EINVAL, "the program was not created with MIOC_ODE_SENS_Y0");
   if (nu < 0 || nu >= prog->nx) return fail(ctx, MIOC_EINVAL, "need 1 <= nu < the program's nx");
   if (ctx->have_levels && ctx->M != prog->nx - nu)
     return fail(ctx, MIOC_EINVAL, nu ? "the program's nx differs from nu + the levels' number of controls"
@@ -405,8 +435,8 @@ static int32_t program_eval(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, i
   if (euler) {  // forward states [nt][ny][K]
     const int rc = ctx->d_ode_state.grow(ctx, (size_t)K * (size_t)nt * (size_t)prog->ny * sizeof(double), "ODE states");
     if (rc) return rc;
-  } else if (d_df) {  // the state of every substep (Heun / RK4: at its start, implicit: its stage state)
-    // [nt * substeps][ny][K]; a value-only call stores nothing
+  } else if (d_df || d_Jp || d_Jy0) {  // the state of every substep (Heun / RK4: at its start, implicit: its stage state)
+    // [nt * substeps][ny][K], for the backward sweep; a value-only call stores nothing
     // K * nt < 2^62 and per <= 64 * 8 * 8: the product is taken only once it is known to stay below 2^46
     const uint64_t cells = (uint64_t)K * (uint64_t)nt, per = (uint64_t)(prog->substeps * prog->ny) * sizeof(double);
     if (cells > ((uint64_t)1 << 46) / per) return fail(ctx, MIOC_ENOMEM, "the ODE states of all substeps exceed 64 TiB");
@@ -428,7 +458,7 @@ static int32_t program_eval(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, i
   // a scenario program takes S and the two device arrays where the others take Par
   int Si = (int)S;
   void *args_euler[14] = {&Ki, &nti, &t0, &tau};
-  void *args_rk[16] = {&Ki, &nti, &ms, &t0, &tau, &h};
+  void *args_rk[18] = {&Ki, &nti, &ms, &t0, &tau, &h};
   void **args = euler ? args_euler : args_rk;
   int na = euler ? 4 : 6;
   if (prog->scen) {
@@ -439,6 +469,7 @@ static int32_t program_eval(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, i
   args[na++] = &X, args[na++] = &d_J, args[na++] = &d_df, args[na++] = &ST, args[na++] = &gate;
   if (prog->nd > 0) args[na++] = &d_data;
   if (prog->flags & MIOC_ODE_STATES) args[na++] = &d_Y;
+  if (prog->sens) args[na++] = &d_Jp, args[na++] = &d_Jy0;  // never an Euler program
   const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)((K + 63) / 64), 1, 1, 64, 1, 1, 0, ctx->stream, args, nullptr);
   if (e != hipSuccess) return fail(ctx, MIOC_EHIP, std::string("launching the ODE program: ") + hipGetErrorString(e));
   return MIOC_OK;
@@ -474,6 +505,13 @@ int32_t mioc_ode_program_eval_scen_device(mioc_ctx *ctx, mioc_ode_program *prog,
                                           double *d_J, double *d_df, double *d_Y) {
   if (ctx && S < 1) return fail(ctx, MIOC_EINVAL, "need S >= 1 scenarios and K a multiple of S");
   return program_eval(ctx, prog, nu, K, d_x, nt, T0, T1, S, d_state0, d_params, d_data, d_J, d_df, d_Y);
+}
+
+int32_t mioc_ode_program_eval_sens_device(mioc_ctx *ctx, mioc_ode_program *prog, int64_t nu, int64_t K,
+                                          const double *d_x, int64_t nt, double T0, double T1, int64_t S,
+                                          const double *state0, const double *params, const double *d_data,
+                                          double *d_J, double *d_df, double *d_Y, double *d_Jp, double *d_Jy0) {
+  return program_eval(ctx, prog, nu, K, d_x, nt, T0, T1, S, state0, params, d_data, d_J, d_df, d_Y, d_Jp, d_Jy0);
 }
 
 }  // extern "C"

@@ -10,7 +10,8 @@
 // A terminal cost, ND columns of sampled data, the state output and scenarios are compiled in only when the head
 // #defines MIOC_TERMINAL, ND, MIOC_STATES, MIOC_SCEN (and MIOC_SCEN_DATA): without them every macro and helper below
 // preprocesses to the tokens of a program that never had them, and the kernel has neither the data nor the state
-// pointer and takes state0 and the parameters by value.
+// pointer and takes state0 and the parameters by value.  The same holds for the sensitivities (MIOC_SENS, kBodyRK and
+// kBodyTheta only): MIOC_BACKWARD is DF and every other MIOC_SENS_* / MIOC_DF_* macro is empty without it.
 #pragma once
 
 namespace mioc_kernel_text {
@@ -83,6 +84,73 @@ const char *const kSkeletonHead = R"SKEL(
 #define MIOC_YO_OPEN(y)
 #define MIOC_YO_ROW(row, y)
 #endif
+// Sensitivities (MIOC_SENS, bit 1: dJ/dparams into JP[k][e], bit 2: dJ/dstate0 into JY0[k][r]; include/mioc.h,
+// "Sensitivities").  The backward sweep then runs when any of DF, JP, JY0 is given, and df is stored only with DF.
+// pbar is the accumulator beside xbar that is never reset: MIOC_SENS_STAGE adds Fp(Y)' v + wgt Gp(Y) at one stage
+// (v: kbar_s or mu, wgt: (b_s h) or h), every sum left to right.  MIOC_SENS_OUT stores pbar and w after substep 0.
+#ifdef MIOC_SENS
+#define MIOC_SENS_ARG , double *JP, double *JY0
+#define MIOC_BACKWARD (DF || JP || JY0)
+#define MIOC_DF_OPEN if (DF) {
+#define MIOC_DF_CLOSE }
+#define MIOC_SENS_NAN(nan)                                                                \
+  if (JP)                                                                                 \
+    for (int e = 0; e < NP; ++e) JP[k * NP + e] = nan;                                    \
+  if (JY0)                                                                                \
+    for (int r = 0; r < NY; ++r) JY0[k * NY + r] = nan;
+#if MIOC_SENS & 1
+#ifdef MIOC_TERMINAL  // pbar starts from Ep at the last state y, zeroed first like ey (the data row is nt - 1's)
+#define MIOC_SENS_EP(tend)                                       \
+  if (JP) {                                                      \
+    double ep[NP];                                               \
+    _Pragma("unroll") for (int e = 0; e < NP; ++e) ep[e] = 0.0;  \
+    Ep(p, tend, y, ep);                                          \
+    _Pragma("unroll") for (int e = 0; e < NP; ++e) pbar[e] = ep[e]; \
+  }
+#else
+#define MIOC_SENS_EP(tend)
+#endif
+#define MIOC_SENS_OPEN(tend)                                       \
+  double fp[NY][NP], gp[NP], pbar[NP];                             \
+  _Pragma("unroll") for (int e = 0; e < NP; ++e) {                 \
+    gp[e] = 0.0;                                                   \
+    pbar[e] = 0.0;                                                 \
+    _Pragma("unroll") for (int r = 0; r < NY; ++r) fp[r][e] = 0.0; \
+  }                                                                \
+  MIOC_SENS_EP(tend)
+#define MIOC_SENS_STAGE(t, Y, v, wgt)                                            \
+  if (JP) {                                                                      \
+    Fp(p, i, t, Y, xc, fp);                                                      \
+    Gp(p, i, t, Y, xc, gp);                                                      \
+    _Pragma("unroll") for (int e = 0; e < NP; ++e) {                             \
+      MIOC_TDOT(acc_e, fp, e, v)                                                 \
+      pbar[e] = pbar[e] + (acc_e + (wgt) * gp[e]);                               \
+    }                                                                            \
+  }
+#define MIOC_SENS_OUT_P                                                          \
+  if (JP) {                                                                      \
+    _Pragma("unroll") for (int e = 0; e < NP; ++e) JP[k * NP + e] = pbar[e];     \
+  }
+#else
+#define MIOC_SENS_OPEN(tend)
+#define MIOC_SENS_STAGE(t, Y, v, wgt)
+#define MIOC_SENS_OUT_P
+#endif
+#define MIOC_SENS_OUT                                                            \
+  MIOC_SENS_OUT_P                                                                \
+  if (JY0) {                                                                     \
+    _Pragma("unroll") for (int r = 0; r < NY; ++r) JY0[k * NY + r] = w[r];       \
+  }
+#else
+#define MIOC_SENS_ARG
+#define MIOC_BACKWARD DF
+#define MIOC_DF_OPEN
+#define MIOC_DF_CLOSE
+#define MIOC_SENS_NAN(nan)
+#define MIOC_SENS_OPEN(tend)
+#define MIOC_SENS_STAGE(t, Y, v, wgt)
+#define MIOC_SENS_OUT
+#endif
 // The lane prologue: the gate, the restart k of this lane (of KK), its parameters p and its control x.
 #define MIOC_LANE_PROLOGUE                                                                                   \
   if (gate && *gate == 0) return; /* device TRM control: no restart is inside its inner loop */              \
@@ -96,7 +164,7 @@ const char *const kSkeletonHead = R"SKEL(
 #define MIOC_KERNEL_SUBSTEPS                                                                                    \
   extern "C" __global__ __launch_bounds__(64) void mioc_ode_program_kernel(                                     \
       int K, int nt, int ms, double T0, double tau, double h, MIOC_PAR_ARG, const double *X, double *J,         \
-      double *DF, double *ST, const int *gate MIOC_DATA_ARG MIOC_STATES_ARG)
+      double *DF, double *ST, const int *gate MIOC_DATA_ARG MIOC_STATES_ARG MIOC_SENS_ARG)
 
 namespace mioc_skeleton {
 struct Par {
@@ -254,7 +322,7 @@ MIOC_KERNEL_SUBSTEPS {
     for (int j = 0; j < ms; ++j) {
       const long long n = (long long)i * ms + j;
       const double tn = T0 + (double)n * h;
-      if (DF) {
+      if (MIOC_BACKWARD) {
 #pragma unroll
         for (int r = 0; r < NY; ++r) ST[((size_t)n * NY + r) * KK + k] = y[r];
       }
@@ -283,7 +351,7 @@ MIOC_KERNEL_SUBSTEPS {
   const double tend = T0 + (double)((long long)nt * ms) * h;
 #endif
   MIOC_WRITE_J(q, tend)
-  if (!DF) return;
+  if (!MIOC_BACKWARD) return;
   // ---- backward: the scheme's discrete adjoint; df[:, i] = xbar_i / tau ----
   double *df = DF + k * (size_t)nt * NX;
   double gy[NY], gu[NX], fy[NY][NY], fu[NY][NX], w[NY], YS[NS][NY], kb[NY], Yb[NY], acc[NY], xbar[NX];
@@ -293,6 +361,7 @@ MIOC_KERNEL_SUBSTEPS {
 #pragma unroll
   for (int r = 0; r < NY; ++r) w[r] = ey[r];
 #endif
+  MIOC_SENS_OPEN(tend)
   for (int i = nt - 1; i >= 0; --i) {
 #pragma unroll
     for (int m = 0; m < NX; ++m) {
@@ -320,6 +389,7 @@ MIOC_KERNEL_SUBSTEPS {
         Gy(p, i, tn + ch[s], YS[s], xc, gy);
         Fu(p, i, tn + ch[s], YS[s], xc, fu);
         Gu(p, i, tn + ch[s], YS[s], xc, gu);
+        MIOC_SENS_STAGE(tn + ch[s], YS[s], kb, hb[s])
 #pragma unroll
         for (int c = 0; c < NY; ++c) {
           MIOC_TDOT(t, fy, c, kb)
@@ -336,9 +406,12 @@ MIOC_KERNEL_SUBSTEPS {
 #pragma unroll
       for (int c = 0; c < NY; ++c) w[c] = w[c] + acc[c];
     }
+    MIOC_DF_OPEN
 #pragma unroll
     for (int m = 0; m < NX; ++m) df[(size_t)i * NX + m] = xbar[m] / tau;
+    MIOC_DF_CLOSE
   }
+  MIOC_SENS_OUT
 }
 )SKEL";
 
@@ -441,7 +514,7 @@ MIOC_KERNEL_SUBSTEPS {
       failed = !conv;
 #pragma unroll
       for (int r = 0; r < NY; ++r) Y[r] = y[r] + th * kv[r];
-      if (DF) {
+      if (MIOC_BACKWARD) {
 #pragma unroll
         for (int r = 0; r < NY; ++r) ST[((size_t)n * NY + r) * KK + k] = Y[r];
       }
@@ -460,13 +533,14 @@ MIOC_KERNEL_SUBSTEPS {
     if (yo)
       for (size_t e = 0; e < ((size_t)nt + 1) * NY; ++e) yo[e] = nan;
 #endif
+    MIOC_SENS_NAN(nan)
     return;
   }
 #ifdef MIOC_TERMINAL
   const double tend = T0 + (double)((long long)nt * ms) * h;
 #endif
   MIOC_WRITE_J(q, tend)
-  if (!DF) return;
+  if (!MIOC_BACKWARD) return;
   // ---- backward: (I - th Fy)' mu = h w + (th h) Gy at the stored Y; df[:, i] = xbar_i / tau ----
   double *df = DF + k * (size_t)nt * NX;
   double gy[NY], gu[NX], fu[NY][NX], w[NY], kb[NY], mu[NY], xbar[NX];
@@ -484,6 +558,7 @@ MIOC_KERNEL_SUBSTEPS {
 #pragma unroll
   for (int r = 0; r < NY; ++r) w[r] = ey[r];
 #endif
+  MIOC_SENS_OPEN(tend)
   for (int i = nt - 1; i >= 0; --i) {
 #pragma unroll
     for (int m = 0; m < NX; ++m) {
@@ -507,6 +582,7 @@ MIOC_KERNEL_SUBSTEPS {
       mioc_skeleton::solve(A, kb, mu);
       Fu(p, i, ts, Y, xc, fu);
       Gu(p, i, ts, Y, xc, gu);
+      MIOC_SENS_STAGE(ts, Y, mu, h)
 #pragma unroll
       for (int m = 0; m < NX; ++m) {
         MIOC_TDOT(t, fu, m, mu)
@@ -518,9 +594,12 @@ MIOC_KERNEL_SUBSTEPS {
         w[c] = w[c] + (t + h * gy[c]);
       }
     }
+    MIOC_DF_OPEN
 #pragma unroll
     for (int m = 0; m < NX; ++m) df[(size_t)i * NX + m] = xbar[m] / tau;
+    MIOC_DF_CLOSE
   }
+  MIOC_SENS_OUT
 }
 )SKEL";
 
@@ -825,6 +904,63 @@ MIOC_AD_HOOK void Ey(const double *p, double t, const double *y, double *ey) {
   const mioc_ad::Dual<NY> e = E(p, t, (const mioc_ad::Dual<NY> *)yd);
 #pragma unroll
   for (int r = 0; r < NY; ++r) ey[r] = e.d[r];
+}
+#endif
+// The parameter derivatives of a program with sensitivities: F, G or E (templates over the state type and the parameter
+// type there) once with both = mioc_ad::Dual<NP>, the unit tangents on p[0..NP-1]; the data entries behind them, y and x
+// are constants.
+#if defined(MIOC_DERIVE_FP) || defined(MIOC_DERIVE_GP) || defined(MIOC_DERIVE_EP)
+#ifdef ND  // the head defines ND only when it is positive
+#define MIOC_AD_NPD (NP + ND)
+#else
+#define MIOC_AD_NPD NP
+#endif
+#define MIOC_AD_SEED_P(pd)                                    \
+  mioc_ad::Dual<NP> pd[MIOC_AD_NPD];                          \
+  _Pragma("unroll") for (int e = 0; e < MIOC_AD_NPD; ++e) {   \
+    pd[e] = p[e];                                             \
+    if (e < NP) pd[e].d[e] = 1.0;                             \
+  }
+#endif
+#ifdef MIOC_DERIVE_FP
+MIOC_AD_HOOK void Fp(const double *p, int i, double t, const double *y, const double *x, double (*fp)[NP]) {
+  mioc_ad::Dual<NP> yd[NY], xd[NX], fd[NY];
+  MIOC_AD_SEED_P(pd)
+#pragma unroll
+  for (int r = 0; r < NY; ++r) yd[r] = y[r];
+#pragma unroll
+  for (int m = 0; m < NX; ++m) xd[m] = x[m];
+  F((const mioc_ad::Dual<NP> *)pd, i, t, (const mioc_ad::Dual<NP> *)yd, (const mioc_ad::Dual<NP> *)xd, fd);
+#pragma unroll
+  for (int r = 0; r < NY; ++r) {
+#pragma unroll
+    for (int e = 0; e < NP; ++e) fp[r][e] = fd[r].d[e];
+  }
+}
+#endif
+#ifdef MIOC_DERIVE_GP
+MIOC_AD_HOOK void Gp(const double *p, int i, double t, const double *y, const double *x, double *gp) {
+  mioc_ad::Dual<NP> yd[NY], xd[NX];
+  MIOC_AD_SEED_P(pd)
+#pragma unroll
+  for (int r = 0; r < NY; ++r) yd[r] = y[r];
+#pragma unroll
+  for (int m = 0; m < NX; ++m) xd[m] = x[m];
+  const mioc_ad::Dual<NP> g =
+      G((const mioc_ad::Dual<NP> *)pd, i, t, (const mioc_ad::Dual<NP> *)yd, (const mioc_ad::Dual<NP> *)xd);
+#pragma unroll
+  for (int e = 0; e < NP; ++e) gp[e] = g.d[e];
+}
+#endif
+#ifdef MIOC_DERIVE_EP
+MIOC_AD_HOOK void Ep(const double *p, double t, const double *y, double *ep) {
+  mioc_ad::Dual<NP> yd[NY];
+  MIOC_AD_SEED_P(pd)
+#pragma unroll
+  for (int r = 0; r < NY; ++r) yd[r] = y[r];
+  const mioc_ad::Dual<NP> v = E((const mioc_ad::Dual<NP> *)pd, t, (const mioc_ad::Dual<NP> *)yd);
+#pragma unroll
+  for (int e = 0; e < NP; ++e) ep[e] = v.d[e];
 }
 #endif
 )SKEL";

@@ -43,6 +43,8 @@ MIOC_ODE_NEWTON_MAX, MIOC_ODE_NEWTON_TOL = 12, 1e-10
 MIOC_ODE_DERIVE_FY, MIOC_ODE_DERIVE_FU, MIOC_ODE_DERIVE_GY, MIOC_ODE_DERIVE_GU, MIOC_ODE_DERIVE_ALL = 1, 2, 4, 8, 15
 MIOC_ODE_TERMINAL, MIOC_ODE_STATES, MIOC_ODE_DERIVE_EY = 1, 2, 16  # flags of _create_bolza; the derive bit of Ey
 MIOC_ODE_SCEN, MIOC_ODE_SCEN_DATA = 1, 2  # scen of _create_scen: state0 and params per scenario; the data rows as well
+MIOC_ODE_SENS_P, MIOC_ODE_SENS_Y0 = 1, 2  # sens of _create_sens: dJ/dparams, dJ/dstate0
+MIOC_ODE_DERIVE_FP, MIOC_ODE_DERIVE_GP, MIOC_ODE_DERIVE_EP = 32, 64, 128  # derive bits of Fp, Gp, Ep (with SENS_P)
 
 EXPORTED = [
     "mioc_version", "mioc_create", "mioc_destroy", "mioc_last_error", "mioc_set_option", "mioc_set_levels",
@@ -62,6 +64,7 @@ EXPORTED = [
     "mioc_ode_program_eval_mixed_device", "mioc_rows_copy_device", "mioc_mixed_state_bytes", "mioc_mixed_fan_device",
     "mioc_mixed_select_device", "mioc_mixed_poll",
     "mioc_ode_program_create_scen", "mioc_ode_program_source_scen", "mioc_ode_program_eval_scen_device",
+    "mioc_ode_program_create_sens", "mioc_ode_program_source_sens", "mioc_ode_program_eval_sens_device",
 ]
 
 MIXED_FAN_TERMS = 2048  # slope terms per LDS chunk of mioc_mixed_fan_device (kMixedChunk)
@@ -167,6 +170,12 @@ def load_library(path=None):
         "mioc_ode_program_source_scen": (i64, [ctypes.c_char_p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
                                                ctypes.c_char_p, i64]),
         "mioc_ode_program_eval_scen_device": (i32, [vp, vp, i64, i64, vp, i64, dbl, dbl, i64, vp, vp, vp, vp, vp, vp]),
+        "mioc_ode_program_create_sens": (i32, [ctypes.c_char_p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                               ctypes.POINTER(vp), ctypes.c_char_p, i64]),
+        "mioc_ode_program_source_sens": (i64, [ctypes.c_char_p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                               ctypes.c_char_p, i64]),
+        "mioc_ode_program_eval_sens_device": (i32, [vp, vp, i64, i64, vp, i64, dbl, dbl, i64, vp, vp, vp, vp, vp, vp,
+                                                    vp, vp]),
         "mioc_ode_program_destroy": (i32, [vp]),
         "mioc_ode_program_eval_bolza_device": (i32, [vp, vp, i64, i64, vp, i64, dbl, dbl, vp, vp, vp, vp, vp, vp]),
         "mioc_ode_program_eval_device": (i32, [vp, vp, i64, vp, i64, dbl, dbl, vp, vp, vp, vp]),
@@ -483,9 +492,23 @@ class Context:
             ctypes.c_void_p(J.data_ptr()) if J is not None else None,
             ctypes.c_void_p(df.data_ptr()) if df is not None else None))
 
-    def _ode_program_eval(self, prog, nu, x, T0, T1, state0, params, J, df, data, Y):
+    @staticmethod
+    def _check_sens(prog, K, x, Jp, Jy0):
+        """The checks of the two sensitivity outputs of an evaluation: Jp (K, nparams), Jy0 (K, ny)."""
+        sens = int(getattr(prog, "sens", 0))
+        for name, t, n, bit in (("Jp", Jp, K * prog.nparams, MIOC_ODE_SENS_P), ("Jy0", Jy0, K * prog.ny, MIOC_ODE_SENS_Y0)):
+            if t is None:
+                continue
+            if not sens & bit:
+                raise ValueError(f"the program was not compiled with the sensitivities that {name} asks for")
+            if (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or t.numel() != n or
+                    t.device != x.device):
+                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries on the device of x")
+
+    def _ode_program_eval(self, prog, nu, x, T0, T1, state0, params, J, df, data, Y, Jp=None, Jy0=None):
         """The body of ode_program_eval_tensors (nu None) and ode_program_eval_mixed_tensors.  Without data and Y the
-        call goes to the entry it always went to; with either to mioc_ode_program_eval_bolza_device."""
+        call goes to the entry it always went to; with either to mioc_ode_program_eval_bolza_device; with Jp or Jy0
+        to mioc_ode_program_eval_sens_device (S = 0)."""
         if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
             raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
         K, nt, nx = x.shape
@@ -500,6 +523,7 @@ class Context:
                 raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries")
         if Y is not None and not getattr(prog, "states", False):
             raise ValueError("the program was not compiled with states=True")
+        self._check_sens(prog, K, x, Jp, Jy0)
         y0 = np.ascontiguousarray(state0, dtype=np.float64).reshape(-1)
         par = np.ascontiguousarray(() if params is None else params, dtype=np.float64).reshape(-1)
         if y0.size != prog.ny or par.size != prog.nparams:
@@ -509,30 +533,39 @@ class Context:
 
         def ptr(t):
             return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        bolza = data is not None or Y is not None
+        sens = Jp is not None or Jy0 is not None
+        bolza = data is not None or Y is not None or sens
         head = (self.h, prog.h) + ((int(nu or 0),) if nu is not None or bolza else ())
         args = (K, ptr(x), nt, float(T0), float(T1), _p(y0), _p(par) if par.size else None)
-        if bolza:
+        if sens:
+            self._check(self.lib.mioc_ode_program_eval_sens_device(*head, *args[:5], 0, *args[5:], ptr(data), ptr(J),
+                                                                   ptr(df), ptr(Y), ptr(Jp), ptr(Jy0)))
+        elif bolza:
             self._check(self.lib.mioc_ode_program_eval_bolza_device(*head, *args, ptr(data), ptr(J), ptr(df), ptr(Y)))
         elif nu is not None:
             self._check(self.lib.mioc_ode_program_eval_mixed_device(*head, *args, ptr(J), ptr(df)))
         else:
             self._check(self.lib.mioc_ode_program_eval_device(*head, *args, ptr(J), ptr(df)))
 
-    def ode_program_eval_tensors(self, prog, x, T0, T1, state0, params, J=None, df=None, data=None, Y=None):
+    def ode_program_eval_tensors(self, prog, x, T0, T1, state0, params, J=None, df=None, data=None, Y=None, Jp=None,
+                                 Jy0=None):
         """eval_f! / eval_df! of a user-defined ODE objective (mioc.ode_device.ODEProgram) for K controls x
         (K, nt, nx) float64 CUDA tensor: J (K,) and df (K, nt, nx) float64 CUDA tensors (each optional); state0 (ny)
         and params (nparams) host values; enqueued (mioc_ode_program_eval_device).  data: the (nt, ndata) float64 CUDA
         tensor of a program with sampled data; Y: a (K, nt + 1, ny) float64 CUDA tensor to receive the states at the
-        control-grid points (a program compiled with states=True); with either, mioc_ode_program_eval_bolza_device."""
-        self._ode_program_eval(prog, None, x, T0, T1, state0, params, J, df, data, Y)
+        control-grid points (a program compiled with states=True); with either, mioc_ode_program_eval_bolza_device.
+        Jp (K, nparams), Jy0 (K, ny): float64 CUDA tensors to receive dJ/dparams and dJ/dstate0 (a program compiled with
+        sensitivities; include/mioc.h, "Sensitivities"); with either, mioc_ode_program_eval_sens_device."""
+        self._ode_program_eval(prog, None, x, T0, T1, state0, params, J, df, data, Y, Jp, Jy0)
 
-    def ode_program_eval_scen_tensors(self, prog, nu, x, T0, T1, S, state0, params, data=None, J=None, df=None, Y=None):
+    def ode_program_eval_scen_tensors(self, prog, nu, x, T0, T1, S, state0, params, data=None, J=None, df=None, Y=None,
+                                      Jp=None, Jy0=None):
         """ode_program_eval_tensors (nu None or 0) / ode_program_eval_mixed_tensors (nu >= 1) for a program compiled
         with scenarios (include/mioc.h, "Scenarios"): restart k of the K controls x solves scenario k % S.  state0
         (ny, S), params (nparams, S; None with nparams == 0) and data ((nt, ndata), or (nt, ndata, S) for a program
         with per-scenario data) are contiguous float64 CUDA tensors, the scenario index fastest; enqueued
-        (mioc_ode_program_eval_scen_device)."""
+        (mioc_ode_program_eval_scen_device).  Jp (K, nparams), Jy0 (K, ny): restart k's derivatives in scenario
+        k % S's own parameters and state0 (mioc_ode_program_eval_sens_device)."""
         if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
             raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
         K, nt, nx = x.shape
@@ -557,21 +590,26 @@ class Context:
                 raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries on the device of x")
         if Y is not None and not getattr(prog, "states", False):
             raise ValueError("the program was not compiled with states=True")
+        self._check_sens(prog, K, x, Jp, Jy0)
         if not prog.h:
             raise ValueError("the ODE program is closed")
 
         def ptr(t):
             return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-        self._check(self.lib.mioc_ode_program_eval_scen_device(
-            self.h, prog.h, int(nu or 0), K, ptr(x), nt, float(T0), float(T1), S, ptr(state0), ptr(params), ptr(data),
-            ptr(J), ptr(df), ptr(Y)))
+        head = (self.h, prog.h, int(nu or 0), K, ptr(x), nt, float(T0), float(T1), S, ptr(state0), ptr(params), ptr(data),
+                ptr(J), ptr(df), ptr(Y))
+        if Jp is not None or Jy0 is not None:
+            self._check(self.lib.mioc_ode_program_eval_sens_device(*head, ptr(Jp), ptr(Jy0)))
+        else:
+            self._check(self.lib.mioc_ode_program_eval_scen_device(*head))
 
     # ---- mixed controls: the continuous step beside the DP (include/mioc.h, "Mixed controls") -----------------
-    def ode_program_eval_mixed_tensors(self, prog, nu, x, T0, T1, state0, params, J=None, df=None, data=None, Y=None):
+    def ode_program_eval_mixed_tensors(self, prog, nu, x, T0, T1, state0, params, J=None, df=None, data=None, Y=None,
+                                       Jp=None, Jy0=None):
         """ode_program_eval_tensors for a mixed control: the first nu of the program's nx controls are continuous, the
         levels describe the other nx - nu; x may hold the K*R candidates of a fan
         (mioc_ode_program_eval_mixed_device; with data or Y mioc_ode_program_eval_bolza_device)."""
-        self._ode_program_eval(prog, nu, x, T0, T1, state0, params, J, df, data, Y)
+        self._ode_program_eval(prog, nu, x, T0, T1, state0, params, J, df, data, Y, Jp, Jy0)
 
     def rows_copy_tensors(self, dst, dst_row0, src, src_row0, nrows):
         """dst[:, :, dst_row0:dst_row0 + nrows] = src[:, :, src_row0:src_row0 + nrows] for float64 CUDA tensors

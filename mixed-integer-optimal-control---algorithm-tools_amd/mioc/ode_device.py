@@ -20,6 +20,9 @@ control-grid points as an output (``DeviceODEProblem.states``).
 restarts of one call solve different problems: ``DeviceODEProblem`` / ``MixedODEProblem`` then take S initial states
 and parameter vectors (with "data" also S data tables), and restart k of ``TRM_batch`` / ``TRM_mixed_batch`` solves
 scenario k % S; ``best_per_scenario`` picks each scenario's best restart.
+``ODEProgram(..., sensitivities=True | "p" | "y0")`` (mioc_ode_program_create_sens; include/mioc.h, "Sensitivities")
+makes dJ/dparams and dJ/dstate0 outputs of an evaluation for every integrator but "euler": the text then also defines
+``Fp``, ``Gp`` (and ``Ep``), or ``derive`` names them; ``DeviceODEProblem.sensitivities`` returns them.
 
 ``EXAMPLE_SOURCES`` restates the three built-in problems as hook text, term for term as ``Hooks<...>`` of
 csrc/mioc_ode.hip has them, so each reproduces mioc_ode_eval_device bit for bit; they double as templates.  Parameter
@@ -33,8 +36,9 @@ import ctypes
 import sys
 import weakref
 
-from .native import (MIOC_ECOMPILE, MIOC_ODE_DERIVE_EY, MIOC_ODE_DERIVE_FU, MIOC_ODE_DERIVE_FY, MIOC_ODE_DERIVE_GU,
-                     MIOC_ODE_DERIVE_GY, MIOC_ODE_INT_BEULER, MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_MIDPOINT,
+from .native import (MIOC_ECOMPILE, MIOC_ODE_DERIVE_EP, MIOC_ODE_DERIVE_EY, MIOC_ODE_DERIVE_FP, MIOC_ODE_DERIVE_FU,
+                     MIOC_ODE_DERIVE_FY, MIOC_ODE_DERIVE_GP, MIOC_ODE_DERIVE_GU, MIOC_ODE_DERIVE_GY, MIOC_ODE_SENS_P,
+                     MIOC_ODE_SENS_Y0, MIOC_ODE_INT_BEULER, MIOC_ODE_INT_EULER, MIOC_ODE_INT_HEUN, MIOC_ODE_INT_MIDPOINT,
                      MIOC_ODE_INT_RK4, MIOC_ODE_SCEN, MIOC_ODE_SCEN_DATA, MIOC_ODE_STATES, MIOC_ODE_TERMINAL, MIOC_OK,
                      MiocNativeError, load_library)
 
@@ -67,19 +71,43 @@ MAX_SUBSTEPS = 64
 MAX_NDATA = 16
 DERIVE_BITS = {"Fy": MIOC_ODE_DERIVE_FY, "Fu": MIOC_ODE_DERIVE_FU, "Gy": MIOC_ODE_DERIVE_GY, "Gu": MIOC_ODE_DERIVE_GU}
 DERIVE_BITS_TERMINAL = dict(DERIVE_BITS, Ey=MIOC_ODE_DERIVE_EY)  # with a terminal cost
+DERIVE_BITS_P = {"Fp": MIOC_ODE_DERIVE_FP, "Gp": MIOC_ODE_DERIVE_GP}  # with sensitivities in the parameters
+DERIVE_BITS_EVERY = dict(DERIVE_BITS_TERMINAL, **DERIVE_BITS_P, Ep=MIOC_ODE_DERIVE_EP)
 
 
-def derive_names(derive, terminal=False):
-    """``derive`` ("all" or an iterable of hook names) as a tuple of names in the order Fy, Fu, Gy, Gu(, Ey: only a
-    program with a terminal cost has it, and "all" includes it there)."""
-    bits = DERIVE_BITS_TERMINAL if terminal else DERIVE_BITS
+def sensitivity_bits(sensitivities):
+    """``sensitivities`` (False, True, "p" or "y0") as the sens argument of mioc_ode_program_create_sens."""
+    if sensitivities is False or sensitivities is None:
+        return 0
+    if sensitivities is True:
+        return MIOC_ODE_SENS_P | MIOC_ODE_SENS_Y0
+    if isinstance(sensitivities, str) and sensitivities in ("p", "y0"):
+        return MIOC_ODE_SENS_P if sensitivities == "p" else MIOC_ODE_SENS_Y0
+    raise ValueError(f'sensitivities must be False, True, "p" or "y0", not {sensitivities!r}')
+
+
+def derive_names(derive, terminal=False, sens_p=False):
+    """``derive`` ("all", "all+p" or an iterable of hook names) as a tuple of names in the order Fy, Fu, Gy, Gu(, Ey:
+    only a program with a terminal cost has it, and "all" includes it there)(, Fp, Gp: only a program with
+    sensitivities in the parameters has them, ``sens_p``; then Ep with a terminal cost).  "all" stays the y and u hooks
+    whether or not sensitivities are on; "all+p" adds Fp, Gp (and Ep) and needs ``sens_p``."""
+    bits = dict(DERIVE_BITS_TERMINAL if terminal else DERIVE_BITS)
+    plain = tuple(bits)
+    if sens_p:
+        bits.update(DERIVE_BITS_P)
+        if terminal:
+            bits["Ep"] = MIOC_ODE_DERIVE_EP
     if isinstance(derive, str):
-        if derive != "all":
-            raise ValueError(f'derive must be "all" or an iterable of {list(bits)}, not {derive!r}')
-        return tuple(bits)
+        if derive == "all+p" and not sens_p:
+            raise ValueError('derive "all+p" needs sensitivities in the parameters (sensitivities=True or "p")')
+        if derive not in ("all", "all+p"):
+            raise ValueError(f'derive must be "all", "all+p" or an iterable of {list(bits)}, not {derive!r}')
+        return plain if derive == "all" else tuple(bits)
     names = set(derive)
-    if "Ey" in names and not terminal:
-        raise ValueError('derive "Ey" needs terminal=True')
+    if names & {"Ey", "Ep"} and not terminal:
+        raise ValueError('derive "Ey" / "Ep" needs terminal=True')
+    if names & {"Fp", "Gp", "Ep"} and not sens_p:
+        raise ValueError('derive "Fp" / "Gp" / "Ep" needs sensitivities in the parameters (sensitivities=True or "p")')
     unknown = sorted(str(n) for n in names if n not in bits)
     if unknown:
         raise ValueError(f"derive names must be among {list(bits)}, not {unknown}")
@@ -100,17 +128,20 @@ def scenario_bits(scenarios, ndata=0):
 
 
 def program_source(source, ny, nx, nparams, integrator="euler", substeps=1, derive=(), ndata=0, terminal=False,
-                   states=False, noinline=False, scenarios=False):
+                   states=False, noinline=False, scenarios=False, sensitivities=False):
     """The text the library hands to the compiler for ``ODEProgram(source, ny, ...)`` (mioc_ode_program_source; with
-    ``scenarios`` mioc_ode_program_source_scen), as a str; nothing is compiled.  noinline: the text of the second
-    compile of derived hooks (include/mioc.h)."""
+    ``scenarios`` mioc_ode_program_source_scen, with ``sensitivities`` mioc_ode_program_source_sens), as a str; nothing
+    is compiled.  noinline: the text of the second compile of derived hooks (include/mioc.h)."""
     lib = load_library()
     text = source.encode() if isinstance(source, str) else source
-    mask = sum(DERIVE_BITS_TERMINAL[n] for n in derive_names(derive, terminal))
+    sens = sensitivity_bits(sensitivities)
+    mask = sum(DERIVE_BITS_EVERY[n] for n in derive_names(derive, terminal, bool(sens & MIOC_ODE_SENS_P)))
     flags = (MIOC_ODE_TERMINAL if terminal else 0) | (MIOC_ODE_STATES if states else 0)
     scen = scenario_bits(scenarios, ndata)
     args = (text, int(ny), int(nx), int(nparams), int(ndata), INTEGRATORS[integrator], int(substeps), mask, flags)
-    if scen:
+    if sens:
+        entry, args = lib.mioc_ode_program_source_sens, args + (scen, sens, int(bool(noinline)))
+    elif scen:
         entry, args = lib.mioc_ode_program_source_scen, args + (scen, int(bool(noinline)))
     else:
         entry, args = lib.mioc_ode_program_source, args + (int(bool(noinline)),)
@@ -144,32 +175,48 @@ class ODEProgram:
     ``scenarios``: True compiles the program for S scenarios per call, each with its own state0 and parameters; "data"
     (needs ndata > 0) also with its own data table.  Restart k then solves scenario k % S (include/mioc.h,
     "Scenarios"); such a program is evaluated through a DeviceODEProblem / MixedODEProblem or
-    Context.ode_program_eval_scen_tensors.  ``ODEProgram.scenarios`` is the C entry's scen argument (0, 1 or 3)."""
+    Context.ode_program_eval_scen_tensors.  ``ODEProgram.scenarios`` is the C entry's scen argument (0, 1 or 3).
+
+    ``sensitivities``: True compiles the program so that an evaluation can return dJ/dparams and dJ/dstate0 ("p" /
+    "y0": one of them; include/mioc.h, "Sensitivities"); not with "euler".  With the parameter part the text also
+    defines ``Fp``, ``Gp`` and, with ``terminal``, ``Ep``, or ``derive`` names them: F, G, E are then templates over
+    the state type and the parameter type.  ``derive="all"`` stays the y and u hooks; ``"all+p"`` adds Fp, Gp (and
+    Ep).  ``ODEProgram.sens`` is the C entry's sens argument (0..3)."""
 
     LOG_CAP = 1 << 16
 
     def __init__(self, source, ny, nx, nparams, integrator="euler", substeps=1, derive=(), ndata=0, terminal=False,
-                 states=False, scenarios=False):
+                 states=False, scenarios=False, sensitivities=False):
         self.h = None
         self.terminal, self.states = bool(terminal), bool(states)
         if int(ndata) != ndata or not 0 <= ndata <= MAX_NDATA:
             raise ValueError(f"ndata must be an integer in 0..{MAX_NDATA}, not {ndata!r}")
         self.ndata = int(ndata)
         self.scenarios = scenario_bits(scenarios, self.ndata)
-        self.derive = derive_names(derive, self.terminal)
+        self.sens = sensitivity_bits(sensitivities)
+        self.derive = derive_names(derive, self.terminal, bool(self.sens & MIOC_ODE_SENS_P))
         if integrator not in INTEGRATORS:
             raise ValueError(f"integrator must be one of {sorted(INTEGRATORS)}, not {integrator!r}")
         if int(substeps) != substeps or not 1 <= substeps <= MAX_SUBSTEPS:
             raise ValueError(f"substeps must be an integer in 1..{MAX_SUBSTEPS}, not {substeps!r}")
         if integrator == "euler" and substeps != 1:
             raise ValueError("the reference's Euler scheme defines no substeps: use heun, rk4, beuler or midpoint")
+        if integrator == "euler" and self.sens:
+            raise ValueError("the reference's Euler scheme has no sensitivities: its df is not the derivative of its J; "
+                             "use heun, rk4, beuler or midpoint")
         self.integrator, self.substeps = integrator, int(substeps)
         self.lib = load_library()
         self.ny, self.nx, self.nparams = int(ny), int(nx), int(nparams)
         h = ctypes.c_void_p()
         log = ctypes.create_string_buffer(self.LOG_CAP)
         text = source.encode() if isinstance(source, str) else source
-        if self.scenarios:
+        if self.sens:
+            mask = sum(DERIVE_BITS_EVERY[n] for n in self.derive)
+            flags = (MIOC_ODE_TERMINAL if self.terminal else 0) | (MIOC_ODE_STATES if self.states else 0)
+            rc = self.lib.mioc_ode_program_create_sens(text, self.ny, self.nx, self.nparams, self.ndata,
+                                                       INTEGRATORS[integrator], self.substeps, mask, flags,
+                                                       self.scenarios, self.sens, ctypes.byref(h), log, self.LOG_CAP)
+        elif self.scenarios:
             mask = sum(DERIVE_BITS_TERMINAL[n] for n in self.derive)
             flags = (MIOC_ODE_TERMINAL if self.terminal else 0) | (MIOC_ODE_STATES if self.states else 0)
             rc = self.lib.mioc_ode_program_create_scen(text, self.ny, self.nx, self.nparams, self.ndata,
@@ -206,7 +253,8 @@ class ODEProgram:
         """The text this program was compiled from (mioc_ode_program_source); noinline: that of the second compile."""
         return program_source(self._source, self.ny, self.nx, self.nparams, self.integrator, self.substeps,
                               self.derive, self.ndata, self.terminal, self.states, noinline,
-                              {0: False, MIOC_ODE_SCEN: True}.get(self.scenarios, "data"))
+                              {0: False, MIOC_ODE_SCEN: True}.get(self.scenarios, "data"),
+                              {0: False, MIOC_ODE_SENS_P: "p", MIOC_ODE_SENS_Y0: "y0"}.get(self.sens, True))
 
     def close(self):
         if self.h:
@@ -262,6 +310,12 @@ class DeviceODEProblem:
         Synchronises the context."""
         return _states(self, ctx, x, None)
 
+    def sensitivities(self, ctx, x):
+        """(Jp (K, nparams), Jy0 (K, ny)): dJ/dparams and dJ/dstate0 at the controls x (K, nt, nx), as CUDA tensors;
+        a part the program was not compiled for comes back as None (with scenarios: restart k's derivatives in
+        scenario k % S's own values).  ValueError for a program without sensitivities.  Synchronises the context."""
+        return _sensitivities(self, ctx, x, None)
+
     @property
     def S(self):
         """The number of scenarios (1 for a program without them)."""
@@ -314,6 +368,10 @@ class MixedODEProblem:
     def states(self, ctx, x):
         """DeviceODEProblem.states for a mixed control."""
         return _states(self, ctx, x, self.nu)
+
+    def sensitivities(self, ctx, x):
+        """DeviceODEProblem.sensitivities for a mixed control."""
+        return _sensitivities(self, ctx, x, self.nu)
 
     @property
     def S(self):
@@ -411,11 +469,11 @@ def _scenarios_on(problem, x):
     return problem._device_data[key]
 
 
-def _eval_scenarios(problem, ctx, nu, x, J, df, Y):
+def _eval_scenarios(problem, ctx, nu, x, J, df, Y, Jp=None, Jy0=None):
     _check_restarts(problem, x.shape[0])
     d = _scenarios_on(problem, x)
     ctx.ode_program_eval_scen_tensors(problem.program, nu, x, problem.T0, problem.T1, problem._S, d["state0"],
-                                      d["params"], d["data"], J, df, Y)
+                                      d["params"], d["data"], J, df, Y, Jp, Jy0)
 
 
 def best_per_scenario(values, S):
@@ -473,6 +531,27 @@ def _states(problem, ctx, x, nu):
         ctx.ode_program_eval_mixed_tensors(prog, nu, *args, data=_data_on(problem, x), Y=Y)
     ctx.synchronize()
     return Y
+
+
+def _sensitivities(problem, ctx, x, nu):
+    import torch
+    prog = problem.program
+    sens = int(getattr(prog, "sens", 0))
+    if not sens:
+        raise ValueError("the program was not compiled with sensitivities")
+    K = x.shape[0]
+    Jp = torch.empty(K, prog.nparams, dtype=torch.float64, device=x.device) if sens & MIOC_ODE_SENS_P else None
+    Jy0 = torch.empty(K, prog.ny, dtype=torch.float64, device=x.device) if sens & MIOC_ODE_SENS_Y0 else None
+    torch.cuda.current_stream(x.device).synchronize()
+    args = (x, problem.T0, problem.T1, problem.state0, problem.params)
+    if problem._S:
+        _eval_scenarios(problem, ctx, nu, x, None, None, None, Jp, Jy0)
+    elif nu is None:
+        ctx.ode_program_eval_tensors(prog, *args, data=_data_on(problem, x), Jp=Jp, Jy0=Jy0)
+    else:
+        ctx.ode_program_eval_mixed_tensors(prog, nu, *args, data=_data_on(problem, x), Jp=Jp, Jy0=Jy0)
+    ctx.synchronize()
+    return Jp, Jy0
 
 
 _SIG = "(const double *p, int i, double t, const double *y, const double *x"
@@ -606,6 +685,24 @@ template <class T> __device__ T G@SIG@) { return y[0] * y[0] + y[1] * y[1]; }
 }
 EXAMPLE_SOURCES_AD = {k: v.replace("@SIG@", _TSIG) for k, v in EXAMPLE_SOURCES_AD.items()}
 
+# Fishing for derive="all+p" (sensitivities in the parameters): F and G as templates over the state type T and the
+# parameter type P, so that Fp and Gp are generated too.  The same parenthesisation: with T = P = double the same bits.
+_TPSIG = "(const P *p, int i, double t, const T *y, const T *x"
+EXAMPLE_SOURCES_AD_P = {
+    "fishing": """
+template <class T, class P> __device__ T fish_s1(const P *p, const T *x) { return ((0.0 + x[0] * p[6]) + x[1] * p[7]) + x[2] * p[8]; }
+template <class T, class P> __device__ T fish_s2(const P *p, const T *x) { return ((0.0 + x[0] * p[9]) + x[1] * p[10]) + x[2] * p[11]; }
+template <class T, class P> __device__ void F@SIG@, T *f) {
+  f[0] = y[0] * ((p[0] - p[1] * y[1]) - p[4] * fish_s1<T, P>(p, x));
+  f[1] = y[1] * ((-p[2] + p[3] * y[0]) - p[5] * fish_s2<T, P>(p, x));
+}
+template <class T, class P> __device__ T G@SIG@) {
+  const T a = y[0] - 1.0, b = y[1] - 1.0;
+  return 0.5 * (a * a) + 0.5 * (b * b);
+}
+""".replace("@SIG@", _TPSIG),
+}
+
 # the examples' constants (example_fishing.jl, example_doubletank.jl, example_vanderpol.jl) and shapes
 EXAMPLE_PARAMS = {"fishing": [1, 1, 1, 1, 1, 1, 0.2, 0.4, 0.01, 0.1, 0.2, 0.1], "doubletank": [2, 3, 1, 0.5, 2],
                   "vanderpol": [-1, 0.75, -2]}
@@ -623,7 +720,7 @@ def example_program(name, integrator="euler", substeps=1, ad=False):
 
 
 def check_hooks(ctx, source, ny, nx, nparams, x, T0, T1, state0, params, integrator="euler", substeps=1, ndata=0,
-                terminal=False, data=None):
+                terminal=False, data=None, sensitivities=False):
     """Which hand-written derivative hook is wrong?  The program-level counterpart of the reference's test_Fy! /
     test_Fu! (ODEObjective.jl:186-241), without finite differences.
 
@@ -637,23 +734,37 @@ def check_hooks(ctx, source, ny, nx, nparams, x, T0, T1, state0, params, integra
       "all"       the same for all four derived against all by hand.
     A wrong hook shows in its own entry and in "all" alone.  The programs are closed before returning.
     ``terminal``: the text also defines E as a template and Ey by hand under ``#ifndef MIOC_DERIVE_EY``; there is one
-    more program and the key "Ey".  ``ndata``, ``data``: the (nt, ndata) float64 CUDA tensor of a text with data."""
+    more program and the key "Ey".  ``ndata``, ``data``: the (nt, ndata) float64 CUDA tensor of a text with data.
+    ``sensitivities`` (True or "p"; not with "euler"): the text defines F, G (and E) as templates over the state type
+    and the parameter type and Fp, Gp (and Ep) by hand under ``#ifndef MIOC_DERIVE_FP`` etc.; every program is
+    compiled with the sensitivities and there is one more program per p hook and the program "all+p" (everything
+    derived).  The keys "Fp", "Gp", "Ep" and "all+p" compare Jp = dJ/dparams in place of df:
+    max|Jp(derived) - Jp(all by hand)| / max|Jp(all+p)|; a wrong y or u hook also shows in "all+p"."""
     import torch
-    masks = [("hand", ()), ("all", "all")] + [(n, (n,)) for n in (DERIVE_BITS_TERMINAL if terminal else DERIVE_BITS)]
+    sens_p = bool(sensitivity_bits(sensitivities) & MIOC_ODE_SENS_P)
+    if sensitivities and not sens_p:
+        raise ValueError('check_hooks compares the parameter hooks: sensitivities must be True or "p"')
+    names = derive_names("all+p" if sens_p else "all", terminal, sens_p)
+    masks = [("hand", ()), ("all", "all")] + ([("all+p", "all+p")] if sens_p else []) + [(n, (n,)) for n in names]
     res = {}
     for key, derive in masks:
         with ODEProgram(source, ny, nx, nparams, integrator=integrator, substeps=substeps, derive=derive, ndata=ndata,
-                        terminal=terminal) as prog:
+                        terminal=terminal, sensitivities=sensitivities) as prog:
             J = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
             df = torch.empty_like(x)
-            ctx.ode_program_eval_tensors(prog, x, T0, T1, state0, params, J, df, data=data)
+            Jp = torch.empty(x.shape[0], nparams, dtype=torch.float64, device=x.device) if sens_p else None
+            torch.cuda.current_stream(x.device).synchronize()
+            ctx.ode_program_eval_tensors(prog, x, T0, T1, state0, params, J, df, data=data, Jp=Jp)
             ctx.synchronize()
-            res[key] = (J, df)
-    J0, df0 = res["hand"]
+            res[key] = (J, df, Jp)
+    J0, df0, Jp0 = res["hand"]
     scale = float(res["all"][1].abs().max())
-    out = {"J_equal": all(bool(torch.equal(J, J0)) for J, _ in res.values())}
+    out = {"J_equal": all(bool(torch.equal(r[0], J0)) for r in res.values())}
     for key, _ in masks[1:]:
-        out[key] = float((res[key][1] - df0).abs().max()) / scale
+        if key in ("Fp", "Gp", "Ep", "all+p"):
+            out[key] = float((res[key][2] - Jp0).abs().max()) / float(res["all+p"][2].abs().max())
+        else:
+            out[key] = float((res[key][1] - df0).abs().max()) / scale
     return out
 
 
