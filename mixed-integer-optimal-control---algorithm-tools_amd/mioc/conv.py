@@ -20,7 +20,7 @@ import math
 
 import numpy as np
 
-from .iterators import product_iterator
+from .iterators import LevelTable, product_iterator
 from .objective import AbstractObjectiveLazy
 
 
@@ -68,6 +68,18 @@ class ConvProblem:
     def setup(self, ctx):
         """Hand kappa and fvec to a native.Context (mioc_conv_setup)."""
         ctx.conv_setup(self.kappa, self.fvec, self.T0, self.T1)
+
+    # the rest of what mioc.trm_batch.TRM_batch asks of a problem
+    fixes_nt = "the convolution problem fixes nt"  # kappa and fvec are sampled for it
+
+    def level_table(self):
+        return LevelTable(self.levels)
+
+    def eval_tensors(self, ctx, x, J=None, df=None):
+        ctx.conv_eval_tensors(x, J, df)
+
+    def check_restarts(self, K):
+        """Any number of restarts."""
 
 
 class ConvObj(AbstractObjectiveLazy):

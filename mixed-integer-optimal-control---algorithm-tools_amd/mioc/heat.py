@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .iterators import product_iterator
+from .iterators import LevelTable, product_iterator
 from .objective import AbstractObjectiveLazy
 
 
@@ -80,6 +80,18 @@ class HeatProblem:
     def setup(self, ctx):
         """Hand the matrices to a native.Context (mioc_heat_setup)."""
         ctx.heat_setup(self.M_invA, self.M_invF, self.M, self.state0, self.yd, self.T0, self.T1, self.gamma)
+
+    # the rest of what mioc.trm_batch.TRM_batch asks of a problem
+    fixes_nt = "the heat problem fixes nt"  # yd has nt + 1 columns
+
+    def level_table(self):
+        return LevelTable(self.levels)
+
+    def eval_tensors(self, ctx, x, J=None, df=None):
+        ctx.heat_eval_tensors(x, J, df)
+
+    def check_restarts(self, K):
+        """Any number of restarts."""
 
 
 class HeatObj(AbstractObjectiveLazy):

@@ -199,6 +199,25 @@ def _p(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
+def ptr(t):
+    """The device address of a tensor as a ``c_void_p``; None stays None (a NULL pointer)."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def check_tensor(name, t, n=None, dtype="float64", dim=None, on=None, optional=False):
+    """ValueError unless t is a contiguous CUDA tensor of torch.<dtype> -- with n entries (n given), of shape
+    (K, nt, nx) (dim=3), on the device of the tensor ``on`` (given); optional: None passes."""
+    if t is None and optional:
+        return
+    if (t is None or not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch." + dtype or
+            (dim is not None and t.dim() != dim) or (n is not None and t.numel() != n) or
+            (on is not None and t.device != on.device)):
+        raise ValueError(f"{name} must be a contiguous {dtype} CUDA tensor" +
+                         (" of shape (K, nt, nx)" if dim == 3 else "") +
+                         (f" with {n} entries" if n is not None else "") +
+                         (" on the device of x" if on is not None else ""))
+
+
 def cost_spec(p, L=None, levels=None):
     """Map the reference's ``p`` (Int, Float64 or Inf; multi-trust.jl:28) to (p_kind, p_int, table).
 
@@ -348,9 +367,8 @@ class Context:
     def bellman_batch_tensors(self, df, u_old, B, dt):
         """df, u_old: float64 CUDA tensors of shape (K, nt, nx), C-contiguous (each subproblem's nx x nt
         column-major block, the layout of mioc_bellman_batch_device)."""
-        for name, t in (("df", df), ("u_old", u_old)):
-            if t.dim() != 3 or not t.is_contiguous() or not t.is_cuda or str(t.dtype) != "torch.float64":
-                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
+        check_tensor("df", df, dim=3)
+        check_tensor("u_old", u_old, dim=3)
         if tuple(df.shape) != tuple(u_old.shape):
             raise ValueError("df and u_old must have the same shape (K, nt, nx)")
         K, nt, nx = df.shape
@@ -358,35 +376,25 @@ class Context:
 
     def backtrack_batch_tensors(self, B_use, u, phi=None, status=None):
         """u: float64 CUDA tensor (K, nt, nx), contiguous; phi: (K,) float64; status: (K,) int32."""
-        if u.dim() != 3 or not u.is_contiguous() or not u.is_cuda or str(u.dtype) != "torch.float64":
-            raise ValueError("u must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
-        for name, t, dt_ in (("phi", phi, "torch.float64"), ("status", status, "torch.int32")):
-            if t is not None and (not t.is_contiguous() or str(t.dtype) != dt_ or t.numel() != u.shape[0]):
-                raise ValueError(f"{name} must be a contiguous {dt_} tensor with K entries")
+        check_tensor("u", u, dim=3)
+        check_tensor("phi", phi, u.shape[0], optional=True)
+        check_tensor("status", status, u.shape[0], "int32", optional=True)
         self.backtrack_batch_device(B_use, u.data_ptr(), 0 if phi is None else phi.data_ptr(),
                                     0 if status is None else status.data_ptr())
 
     def backtrack_batch_budgets_tensors(self, budgets, u, phi=None, status=None):
         """eval_u_TRM! with one budget per subproblem: budgets (K,) int32 CUDA tensor (each <= B); u (K, nt, nx)
         float64 CUDA tensor; phi, status optional (mioc_backtrack_batch_budgets_device)."""
-        if u.dim() != 3 or not u.is_contiguous() or not u.is_cuda or str(u.dtype) != "torch.float64":
-            raise ValueError("u must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
-        if not budgets.is_cuda or str(budgets.dtype) != "torch.int32" or not budgets.is_contiguous() or \
-                budgets.numel() != u.shape[0]:
-            raise ValueError("budgets must be a contiguous int32 CUDA tensor with K entries")
-        for name, t, dt_ in (("phi", phi, "torch.float64"), ("status", status, "torch.int32")):
-            if t is not None and (not t.is_contiguous() or str(t.dtype) != dt_ or t.numel() != u.shape[0]):
-                raise ValueError(f"{name} must be a contiguous {dt_} tensor with K entries")
-        self._check(self.lib.mioc_backtrack_batch_budgets_device(
-            self.h, ctypes.c_void_p(budgets.data_ptr()), ctypes.c_void_p(u.data_ptr()),
-            ctypes.c_void_p(phi.data_ptr()) if phi is not None else None,
-            ctypes.c_void_p(status.data_ptr()) if status is not None else None))
+        check_tensor("u", u, dim=3)
+        check_tensor("budgets", budgets, u.shape[0], "int32")
+        check_tensor("phi", phi, u.shape[0], optional=True)
+        check_tensor("status", status, u.shape[0], "int32", optional=True)
+        self._check(self.lib.mioc_backtrack_batch_budgets_device(self.h, ptr(budgets), ptr(u), ptr(phi), ptr(status)))
 
     def ranks_tensor(self, out):
         """Level ranks (iterator order) of the last backtrack into `out`, an int32 CUDA tensor (K, nt)."""
-        if not out.is_cuda or str(out.dtype) != "torch.int32" or not out.is_contiguous():
-            raise ValueError("out must be a contiguous int32 CUDA tensor (K, nt)")
-        self._check(self.lib.mioc_get_ranks_device(self.h, ctypes.c_void_p(out.data_ptr())))
+        check_tensor("out", out, dtype="int32")
+        self._check(self.lib.mioc_get_ranks_device(self.h, ptr(out)))
 
     # -- trust-region quantities of the last backtrack (multi-trust.jl:117-158) -------------------
     def pred(self):
@@ -399,21 +407,15 @@ class Context:
         """Per-subproblem int_val / TV_p(u_old) / TV_p(u) / pred of the last batch backtrack into (K,) float64
         CUDA tensors (each optional); enqueued on the context's stream."""
         for name, t in (("int_val", int_val), ("tv_old", tv_old), ("tv_new", tv_new), ("pred", pred)):
-            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64"):
-                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor (K,)")
-        ptr = [ctypes.c_void_p(t.data_ptr()) if t is not None else None for t in (int_val, tv_old, tv_new, pred)]
-        self._check(self.lib.mioc_pred_batch_device(self.h, *ptr))
+            check_tensor(name, t, optional=True)
+        self._check(self.lib.mioc_pred_batch_device(self.h, ptr(int_val), ptr(tv_old), ptr(tv_new), ptr(pred)))
 
     def tv_tensors(self, u, out):
         """TV_p of controls u (K, nt, nx) float64 CUDA tensor into out (K,) float64; enqueued."""
-        if u.dim() != 3 or not u.is_contiguous() or not u.is_cuda or str(u.dtype) != "torch.float64":
-            raise ValueError("u must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
-        if not out.is_cuda or not out.is_contiguous() or str(out.dtype) != "torch.float64" or \
-                out.numel() != u.shape[0]:
-            raise ValueError("out must be a contiguous float64 CUDA tensor (K,)")
+        check_tensor("u", u, dim=3)
         K, nt, nx = u.shape
-        self._check(self.lib.mioc_tv_device(self.h, K, ctypes.c_void_p(u.data_ptr()), nx, nt,
-                                            ctypes.c_void_p(out.data_ptr())))
+        check_tensor("out", out, K)
+        self._check(self.lib.mioc_tv_device(self.h, K, ptr(u), nx, nt, ptr(out)))
 
     # ---- device-resident TRM control (multi-trust.jl:92-163; include/mioc.h) ----------------------------------
     def trm_state_tensor(self, K):
@@ -426,22 +428,19 @@ class Context:
 
     def trm_attach(self, state):
         """Gate the inner-loop kernels by the state's gate word (None detaches)."""
-        self._check(self.lib.mioc_trm_attach(self.h, ctypes.c_void_p(state.data_ptr()) if state is not None else None))
+        self._check(self.lib.mioc_trm_attach(self.h, ptr(state)))
 
     def trm_outer_begin(self, state, tv_u, D0, B, budgets):
         K = tv_u.numel()
-        self._check(self.lib.mioc_trm_outer_begin_device(self.h, K, ctypes.c_void_p(state.data_ptr()),
-                                                          ctypes.c_void_p(tv_u.data_ptr()), float(D0), int(B),
-                                                          ctypes.c_void_p(budgets.data_ptr())))
+        self._check(self.lib.mioc_trm_outer_begin_device(self.h, K, ptr(state), ptr(tv_u), float(D0), int(B),
+                                                          ptr(budgets)))
 
     def trm_inner_end(self, state, sigma, kmax, tau, B, int_val, tv_new, J_new, J_old, J, tv_u, budgets, trial, u,
                       u_old, decision=None):
         K = J.numel()
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         self._check(self.lib.mioc_trm_inner_end_device(
-            self.h, K, p(state), float(sigma), int(kmax), float(tau), int(B), p(int_val), p(tv_new), p(J_new),
-            p(J_old), p(J), p(tv_u), p(budgets), p(decision) if decision is not None else None,
-            u[0].numel(), p(trial), p(u), p(u_old)))
+            self.h, K, ptr(state), float(sigma), int(kmax), float(tau), int(B), ptr(int_val), ptr(tv_new), ptr(J_new),
+            ptr(J_old), ptr(J), ptr(tv_u), ptr(budgets), ptr(decision), u[0].numel(), ptr(trial), ptr(u), ptr(u_old)))
 
     def trm_state_arrays(self, state, K):
         """The state block on the host: Δᵏ, TV_old, k, flags (1 inner, 2 halved, 4 stopped), outer iterations."""
@@ -459,104 +458,88 @@ class Context:
     def trm_poll(self, state):
         """Synchronise once; (any restart inside its inner loop, any restart not stopped)."""
         out = np.zeros(2, dtype=np.int32)
-        self._check(self.lib.mioc_trm_poll(self.h, ctypes.c_void_p(state.data_ptr()), _p(out)))
+        self._check(self.lib.mioc_trm_poll(self.h, ptr(state), _p(out)))
         return bool(out[0]), bool(out[1])
 
     def trm_decide_tensors(self, J_old, J_new, tv_old, tv_new, pred, sigma, decision, ared=None):
         """multi-trust.jl:127-158 per subproblem: decision (K,) int32 = 2 stop / 1 halve / 0 accept."""
         ts = (J_old, J_new, tv_old, tv_new, pred)
         K = decision.numel()
-        for t in ts + ((ared,) if ared is not None else ()):
-            if not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or t.numel() != K:
-                raise ValueError("J_old / J_new / tv_old / tv_new / pred / ared: contiguous float64 (K,)")
-        if not decision.is_cuda or str(decision.dtype) != "torch.int32" or not decision.is_contiguous():
-            raise ValueError("decision must be a contiguous int32 CUDA tensor (K,)")
-        self._check(self.lib.mioc_trm_decide_device(
-            self.h, K, *[ctypes.c_void_p(t.data_ptr()) for t in ts], float(sigma),
-            ctypes.c_void_p(ared.data_ptr()) if ared is not None else None, ctypes.c_void_p(decision.data_ptr())))
+        for name, t in zip(("J_old", "J_new", "tv_old", "tv_new", "pred"), ts):
+            check_tensor(name, t, K)
+        check_tensor("ared", ared, K, optional=True)
+        check_tensor("decision", decision, dtype="int32")
+        self._check(self.lib.mioc_trm_decide_device(self.h, K, *[ptr(t) for t in ts], float(sigma), ptr(ared),
+                                                    ptr(decision)))
+
+    @staticmethod
+    def _check_eval(x, J, df):
+        """The checks every objective's evaluation makes: x (K, nt, nx), and J (K,) and df like x if given."""
+        check_tensor("x", x, dim=3)
+        check_tensor("J", J, x.shape[0], optional=True)
+        check_tensor("df", df, x.numel(), optional=True)
+        return x.shape
 
     def ode_eval_tensors(self, problem, x, T0, T1, J=None, df=None, params=None):
         """eval_f! / eval_df! of an ODE example for K controls x (K, nt, 3) float64 CUDA tensor: J (K,) and df
         (K, nt, 3) float64 CUDA tensors (each optional); enqueued (mioc_ode_eval_device)."""
-        if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
-            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
-        K, nt, nx = x.shape
-        for name, t, n in (("J", J, K), ("df", df, x.numel())):
-            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or
-                                  t.numel() != n):
-                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries")
+        K, nt, nx = self._check_eval(x, J, df)
         par = None if params is None else np.ascontiguousarray(params, dtype=np.float64)
         self._check(self.lib.mioc_ode_eval_device(
-            self.h, int(problem), K, ctypes.c_void_p(x.data_ptr()), nx, nt, float(T0), float(T1),
-            None if par is None else _p(par), 0 if par is None else par.size,
-            ctypes.c_void_p(J.data_ptr()) if J is not None else None,
-            ctypes.c_void_p(df.data_ptr()) if df is not None else None))
+            self.h, int(problem), K, ptr(x), nx, nt, float(T0), float(T1),
+            None if par is None else _p(par), 0 if par is None else par.size, ptr(J), ptr(df)))
 
-    @staticmethod
-    def _check_sens(prog, K, x, Jp, Jy0):
-        """The checks of the two sensitivity outputs of an evaluation: Jp (K, nparams), Jy0 (K, ny)."""
-        sens = int(getattr(prog, "sens", 0))
-        for name, t, n, bit in (("Jp", Jp, K * prog.nparams, MIOC_ODE_SENS_P), ("Jy0", Jy0, K * prog.ny, MIOC_ODE_SENS_Y0)):
-            if t is None:
-                continue
-            if not sens & bit:
-                raise ValueError(f"the program was not compiled with the sensitivities that {name} asks for")
-            if (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or t.numel() != n or
-                    t.device != x.device):
-                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries on the device of x")
-
-    def _ode_program_eval(self, prog, nu, x, T0, T1, state0, params, J, df, data, Y, Jp=None, Jy0=None):
-        """The body of ode_program_eval_tensors (nu None) and ode_program_eval_mixed_tensors.  Without data and Y the
-        call goes to the entry it always went to; with either to mioc_ode_program_eval_bolza_device; with Jp or Jy0
-        to mioc_ode_program_eval_sens_device (S = 0)."""
-        if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
-            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
-        K, nt, nx = x.shape
+    def _ode_program_eval(self, prog, nu, nu_min, x, T0, T1, S, state0, params, data, J, df, Y, Jp, Jy0):
+        """The body of ode_program_eval_tensors, ode_program_eval_mixed_tensors (S = 0: state0 and params are host
+        values) and ode_program_eval_scen_tensors (S >= 1: they are device arrays): the checks, then the one call of the
+        library's _sens eval entry, which is every older eval entry with the arguments it lacks zero."""
+        K, nt, nx = self._check_eval(x, J, df)
         if nx != prog.nx:
             raise ValueError(f"x has {nx} controls, the program {prog.nx}")
-        if nu is not None and (int(nu) != nu or not 1 <= nu < nx):
-            raise ValueError(f"nu must be an integer in 1..{nx - 1}, not {nu!r}")
-        for name, t, n in (("J", J, K), ("df", df, x.numel()), ("data", data, nt * getattr(prog, "ndata", 0)),
-                           ("Y", Y, K * (nt + 1) * prog.ny)):
-            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or
-                                  t.numel() != n):
-                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries")
+        if int(nu) != nu or not nu_min <= nu < nx:
+            raise ValueError(f"nu must be an integer in {nu_min}..{nx - 1}, not {nu!r}")
+        scen, sens, nd = int(getattr(prog, "scenarios", 0)), int(getattr(prog, "sens", 0)), getattr(prog, "ndata", 0)
         if Y is not None and not getattr(prog, "states", False):
             raise ValueError("the program was not compiled with states=True")
-        self._check_sens(prog, K, x, Jp, Jy0)
-        y0 = np.ascontiguousarray(state0, dtype=np.float64).reshape(-1)
-        par = np.ascontiguousarray(() if params is None else params, dtype=np.float64).reshape(-1)
-        if y0.size != prog.ny or par.size != prog.nparams:
-            raise ValueError(f"the program takes {prog.ny} initial states and {prog.nparams} parameters")
+        for name, t, bit in (("Jp", Jp, MIOC_ODE_SENS_P), ("Jy0", Jy0, MIOC_ODE_SENS_Y0)):
+            if t is not None and not sens & bit:
+                raise ValueError(f"the program was not compiled with the sensitivities that {name} asks for")
+        for name, t, n in (("J", J, K), ("df", df, x.numel()), ("Y", Y, K * (nt + 1) * prog.ny),
+                           ("data", data, nt * nd * (S if S and scen & MIOC_ODE_SCEN_DATA else 1)),
+                           ("Jp", Jp, K * prog.nparams), ("Jy0", Jy0, K * prog.ny)):
+            check_tensor(name, t, n, on=x, optional=True)
+        if S:  # the arrays of S scenarios, on the device
+            if not scen:
+                raise ValueError("the program was not compiled with scenarios")
+            if K % S:
+                raise ValueError(f"the number of controls, {K}, must be a multiple of the {S} scenarios")
+            if data is None and nd:
+                raise ValueError("the program reads sampled data: data missing")
+            check_tensor("state0", state0, prog.ny * S, on=x)
+            check_tensor("params", params, prog.nparams * S, on=x, optional=not prog.nparams)
+            y0, par = ptr(state0), ptr(params)
+        else:      # one state0 and one parameter vector, host values (a scenario program is refused by the library)
+            h_y0 = np.ascontiguousarray(state0, dtype=np.float64).reshape(-1)
+            h_par = np.ascontiguousarray(() if params is None else params, dtype=np.float64).reshape(-1)
+            if h_y0.size != prog.ny or h_par.size != prog.nparams:
+                raise ValueError(f"the program takes {prog.ny} initial states and {prog.nparams} parameters")
+            y0, par = _p(h_y0), _p(h_par) if h_par.size else None
         if not prog.h:
             raise ValueError("the ODE program is closed")
-
-        def ptr(t):
-            return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        sens = Jp is not None or Jy0 is not None
-        bolza = data is not None or Y is not None or sens
-        head = (self.h, prog.h) + ((int(nu or 0),) if nu is not None or bolza else ())
-        args = (K, ptr(x), nt, float(T0), float(T1), _p(y0), _p(par) if par.size else None)
-        if sens:
-            self._check(self.lib.mioc_ode_program_eval_sens_device(*head, *args[:5], 0, *args[5:], ptr(data), ptr(J),
-                                                                   ptr(df), ptr(Y), ptr(Jp), ptr(Jy0)))
-        elif bolza:
-            self._check(self.lib.mioc_ode_program_eval_bolza_device(*head, *args, ptr(data), ptr(J), ptr(df), ptr(Y)))
-        elif nu is not None:
-            self._check(self.lib.mioc_ode_program_eval_mixed_device(*head, *args, ptr(J), ptr(df)))
-        else:
-            self._check(self.lib.mioc_ode_program_eval_device(*head, *args, ptr(J), ptr(df)))
+        self._check(self.lib.mioc_ode_program_eval_sens_device(
+            self.h, prog.h, int(nu), K, ptr(x), nt, float(T0), float(T1), S, y0, par, ptr(data), ptr(J), ptr(df),
+            ptr(Y), ptr(Jp), ptr(Jy0)))
 
     def ode_program_eval_tensors(self, prog, x, T0, T1, state0, params, J=None, df=None, data=None, Y=None, Jp=None,
                                  Jy0=None):
         """eval_f! / eval_df! of a user-defined ODE objective (mioc.ode_device.ODEProgram) for K controls x
         (K, nt, nx) float64 CUDA tensor: J (K,) and df (K, nt, nx) float64 CUDA tensors (each optional); state0 (ny)
-        and params (nparams) host values; enqueued (mioc_ode_program_eval_device).  data: the (nt, ndata) float64 CUDA
-        tensor of a program with sampled data; Y: a (K, nt + 1, ny) float64 CUDA tensor to receive the states at the
-        control-grid points (a program compiled with states=True); with either, mioc_ode_program_eval_bolza_device.
-        Jp (K, nparams), Jy0 (K, ny): float64 CUDA tensors to receive dJ/dparams and dJ/dstate0 (a program compiled with
-        sensitivities; include/mioc.h, "Sensitivities"); with either, mioc_ode_program_eval_sens_device."""
-        self._ode_program_eval(prog, None, x, T0, T1, state0, params, J, df, data, Y, Jp, Jy0)
+        and params (nparams) host values; enqueued (the library's _sens eval entry with nu = 0 and S = 0, which is what
+        its plain and _bolza entries forward to).  data: the (nt, ndata) float64 CUDA tensor of a program with sampled
+        data; Y: a (K, nt + 1, ny) float64 CUDA tensor to receive the states at the control-grid points (a program
+        compiled with states=True).  Jp (K, nparams), Jy0 (K, ny): float64 CUDA tensors to receive dJ/dparams and
+        dJ/dstate0 (a program compiled with sensitivities; include/mioc.h, "Sensitivities")."""
+        self._ode_program_eval(prog, 0, 0, x, T0, T1, 0, state0, params, data, J, df, Y, Jp, Jy0)
 
     def ode_program_eval_scen_tensors(self, prog, nu, x, T0, T1, S, state0, params, data=None, J=None, df=None, Y=None,
                                       Jp=None, Jy0=None):
@@ -564,66 +547,32 @@ class Context:
         with scenarios (include/mioc.h, "Scenarios"): restart k of the K controls x solves scenario k % S.  state0
         (ny, S), params (nparams, S; None with nparams == 0) and data ((nt, ndata), or (nt, ndata, S) for a program
         with per-scenario data) are contiguous float64 CUDA tensors, the scenario index fastest; enqueued
-        (mioc_ode_program_eval_scen_device).  Jp (K, nparams), Jy0 (K, ny): restart k's derivatives in scenario
-        k % S's own parameters and state0 (mioc_ode_program_eval_sens_device)."""
-        if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
-            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
-        K, nt, nx = x.shape
-        S, scen = int(S), int(getattr(prog, "scenarios", 0))
-        if nx != prog.nx:
-            raise ValueError(f"x has {nx} controls, the program {prog.nx}")
-        if not scen:
-            raise ValueError("the program was not compiled with scenarios")
-        if S < 1 or K % S:
-            raise ValueError(f"the number of controls, {K}, must be a multiple of the {S} scenarios")
-        if nu is not None and (int(nu) != nu or not 0 <= nu < nx):
-            raise ValueError(f"nu must be an integer in 0..{nx - 1}, not {nu!r}")
-        nd = getattr(prog, "ndata", 0)
-        if (state0 is None) or (params is None and prog.nparams) or (data is None and nd):
-            raise ValueError("state0, params or data missing")
-        for name, t, n in (("J", J, K), ("df", df, x.numel()), ("state0", state0, prog.ny * S),
-                           ("params", params, prog.nparams * S),
-                           ("data", data, nt * nd * (S if scen & MIOC_ODE_SCEN_DATA else 1)),
-                           ("Y", Y, K * (nt + 1) * prog.ny)):
-            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or
-                                  t.numel() != n or t.device != x.device):
-                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries on the device of x")
-        if Y is not None and not getattr(prog, "states", False):
-            raise ValueError("the program was not compiled with states=True")
-        self._check_sens(prog, K, x, Jp, Jy0)
-        if not prog.h:
-            raise ValueError("the ODE program is closed")
-
-        def ptr(t):
-            return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-        head = (self.h, prog.h, int(nu or 0), K, ptr(x), nt, float(T0), float(T1), S, ptr(state0), ptr(params), ptr(data),
-                ptr(J), ptr(df), ptr(Y))
-        if Jp is not None or Jy0 is not None:
-            self._check(self.lib.mioc_ode_program_eval_sens_device(*head, ptr(Jp), ptr(Jy0)))
-        else:
-            self._check(self.lib.mioc_ode_program_eval_scen_device(*head))
+        (the library's _sens eval entry with S >= 1, which is what its _scen entry forwards to).
+        Jp (K, nparams), Jy0 (K, ny): restart k's derivatives in scenario k % S's own parameters and state0."""
+        if int(S) < 1:
+            raise ValueError(f"need S >= 1 scenarios, not {S!r}")
+        self._ode_program_eval(prog, nu or 0, 0, x, T0, T1, int(S), state0, params, data, J, df, Y, Jp, Jy0)
 
     # ---- mixed controls: the continuous step beside the DP (include/mioc.h, "Mixed controls") -----------------
     def ode_program_eval_mixed_tensors(self, prog, nu, x, T0, T1, state0, params, J=None, df=None, data=None, Y=None,
                                        Jp=None, Jy0=None):
-        """ode_program_eval_tensors for a mixed control: the first nu of the program's nx controls are continuous, the
-        levels describe the other nx - nu; x may hold the K*R candidates of a fan
-        (mioc_ode_program_eval_mixed_device; with data or Y mioc_ode_program_eval_bolza_device)."""
-        self._ode_program_eval(prog, nu, x, T0, T1, state0, params, J, df, data, Y, Jp, Jy0)
+        """ode_program_eval_tensors for a mixed control: the first nu >= 1 of the program's nx controls are continuous,
+        the levels describe the other nx - nu; x may hold the K*R candidates of a fan
+        (the library's _sens eval entry with S = 0, which is what its _mixed entry forwards to; that entry's refusal of
+        nu < 1 is made here)."""
+        self._ode_program_eval(prog, nu, 1, x, T0, T1, 0, state0, params, data, J, df, Y, Jp, Jy0)
 
     def rows_copy_tensors(self, dst, dst_row0, src, src_row0, nrows):
         """dst[:, :, dst_row0:dst_row0 + nrows] = src[:, :, src_row0:src_row0 + nrows] for float64 CUDA tensors
         (K, nt, dst_nx) and (K, nt, src_nx); dst may be src with disjoint rows.  Enqueued, gated by trm_attach
         (mioc_rows_copy_device); the row ranges are checked by the library."""
-        for name, t in (("dst", dst), ("src", src)):
-            if t.dim() != 3 or not t.is_contiguous() or not t.is_cuda or str(t.dtype) != "torch.float64":
-                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
+        check_tensor("dst", dst, dim=3)
+        check_tensor("src", src, dim=3)
         if tuple(dst.shape[:2]) != tuple(src.shape[:2]):
             raise ValueError("dst and src must agree in K and nt")
         K, nt, dnx = dst.shape
-        self._check(self.lib.mioc_rows_copy_device(self.h, K, nt, ctypes.c_void_p(dst.data_ptr()), dnx, int(dst_row0),
-                                                   ctypes.c_void_p(src.data_ptr()), src.shape[2], int(src_row0),
-                                                   int(nrows)))
+        self._check(self.lib.mioc_rows_copy_device(self.h, K, nt, ptr(dst), dnx, int(dst_row0), ptr(src), src.shape[2],
+                                                   int(src_row0), int(nrows)))
 
     def mixed_state_tensor(self, K, s0):
         """A device state block of the continuous step for K restarts (uint8 CUDA tensor): zeroed, the step sizes s0."""
@@ -642,12 +591,9 @@ class Context:
             raise ValueError("R must be in 1..16")
         if not 1 <= int(nu) <= nx:
             raise ValueError(f"nu must be in 1..{nx}")
-        if not mstate.is_cuda or str(mstate.dtype) != "torch.uint8" or not mstate.is_contiguous() or \
-                mstate.numel() != int(self.lib.mioc_mixed_state_bytes(K)):
-            raise ValueError("mstate must be the uint8 CUDA tensor of mixed_state_tensor(K, s0)")
+        check_tensor("mstate (of mixed_state_tensor(K, s0))", mstate, int(self.lib.mioc_mixed_state_bytes(K)), "uint8")
         for name, t, n in f64:
-            if not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or t.numel() != n:
-                raise ValueError(f"{what}: {name} must be a contiguous float64 CUDA tensor with {n} entries")
+            check_tensor(f"{what}: {name}", t, n)
 
     def mixed_fan_tensors(self, R, nu, tau, x, df, lo, hi, mstate, xfan, slope):
         """The R line-search candidates of every restart: x, df (K, nt, nx), lo, hi (nt, nu), xfan (R, K, nt, nx),
@@ -658,9 +604,8 @@ class Context:
         self._mixed_check(K, R, nu, nx, nt, mstate,
                           (("x", x, K * nt * nx), ("df", df, K * nt * nx), ("lo", lo, nt * nu), ("hi", hi, nt * nu),
                            ("xfan", xfan, R * K * nt * nx), ("slope", slope, R * K)), "mixed_fan")
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        self._check(self.lib.mioc_mixed_fan_device(self.h, K, int(R), int(nu), nx, nt, float(tau), p(x), p(df), p(lo),
-                                                   p(hi), p(mstate), p(xfan), p(slope)))
+        self._check(self.lib.mioc_mixed_fan_device(self.h, K, int(R), int(nu), nx, nt, float(tau), ptr(x), ptr(df),
+                                                   ptr(lo), ptr(hi), ptr(mstate), ptr(xfan), ptr(slope)))
 
     def mixed_select_tensors(self, R, nu, c1, smax, ctol, mstate, trm_state, xfan, slope, Jfan, J_old, x):
         """Per restart the first candidate that passes the Armijo test, the step-size update and the finality rule
@@ -672,19 +617,16 @@ class Context:
         self._mixed_check(K, R, nu, nx, nt, mstate,
                           (("x", x, K * nt * nx), ("xfan", xfan, R * K * nt * nx), ("slope", slope, R * K),
                            ("Jfan", Jfan, R * K), ("J_old", J_old, K)), "mixed_select")
-        if not trm_state.is_cuda or trm_state.numel() != int(self.lib.mioc_trm_state_bytes(K)):
-            raise ValueError("trm_state must be the CUDA tensor of trm_state_tensor(K)")
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        check_tensor("trm_state (of trm_state_tensor(K))", trm_state, int(self.lib.mioc_trm_state_bytes(K)), "uint8")
         self._check(self.lib.mioc_mixed_select_device(self.h, K, int(R), int(nu), nx, nt, float(c1), float(smax),
-                                                      float(ctol), p(mstate), p(trm_state), p(xfan), p(slope), p(Jfan),
-                                                      p(J_old), p(x)))
+                                                      float(ctol), ptr(mstate), ptr(trm_state), ptr(xfan), ptr(slope),
+                                                      ptr(Jfan), ptr(J_old), ptr(x)))
 
     def mixed_poll(self, mstate, trm_state):
         """Synchronise once; (any restart inside its inner loop, any restart that can still move)
         (mioc_mixed_poll)."""
         out = np.zeros(2, dtype=np.int32)
-        self._check(self.lib.mioc_mixed_poll(self.h, ctypes.c_void_p(mstate.data_ptr()),
-                                             ctypes.c_void_p(trm_state.data_ptr()), _p(out)))
+        self._check(self.lib.mioc_mixed_poll(self.h, ptr(mstate), ptr(trm_state), _p(out)))
         return bool(out[0]), bool(out[1])
 
     def mixed_state_arrays(self, mstate, K):
@@ -715,19 +657,10 @@ class Context:
     def heat_eval_tensors(self, x, J=None, df=None):
         """eval_f / eval_df of the heat objective for K controls x (K, nt, nx) float64 CUDA tensor into J (K,) and
         df (K, nt, nx) float64 CUDA tensors (each optional); enqueued (mioc_heat_eval_device)."""
-        if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
-            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
-        K, nt, nx = x.shape
+        K, nt, nx = self._check_eval(x, J, df)
         if getattr(self, "heat_shape", None) is None or self.heat_shape[1:] != (nx, nt):
             raise ValueError("x does not match the (nx, nt) given to heat_setup")
-        for name, t, n in (("J", J, K), ("df", df, x.numel())):
-            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or
-                                  t.numel() != n):
-                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries")
-        self._check(self.lib.mioc_heat_eval_device(
-            self.h, K, ctypes.c_void_p(x.data_ptr()),
-            ctypes.c_void_p(J.data_ptr()) if J is not None else None,
-            ctypes.c_void_p(df.data_ptr()) if df is not None else None))
+        self._check(self.lib.mioc_heat_eval_device(self.h, K, ptr(x), ptr(J), ptr(df)))
 
     def heat_eval(self, xs):
         """Host entry (mioc_heat_eval): xs (K, nx, nt) numpy controls (Julia's per-restart layout) -> J (K,),
@@ -756,19 +689,10 @@ class Context:
         """eval_f / eval_df of the convolution objective for K controls x (K, nt, 1) float64 CUDA tensor into J (K,)
         and df (K, nt, 1) float64 CUDA tensors (each optional; without df the call stops after J); enqueued
         (mioc_conv_eval_device)."""
-        if x.dim() != 3 or not x.is_contiguous() or not x.is_cuda or str(x.dtype) != "torch.float64":
-            raise ValueError("x must be a contiguous float64 CUDA tensor of shape (K, nt, nx)")
-        K, nt, nx = x.shape
+        K, nt, nx = self._check_eval(x, J, df)
         if getattr(self, "conv_shape", None) is None or self.conv_shape != (nx, nt):
             raise ValueError("x does not match the (nx = 1, nt) given to conv_setup")
-        for name, t, n in (("J", J, K), ("df", df, x.numel())):
-            if t is not None and (not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float64" or
-                                  t.numel() != n):
-                raise ValueError(f"{name} must be a contiguous float64 CUDA tensor with {n} entries")
-        self._check(self.lib.mioc_conv_eval_device(
-            self.h, K, ctypes.c_void_p(x.data_ptr()),
-            ctypes.c_void_p(J.data_ptr()) if J is not None else None,
-            ctypes.c_void_p(df.data_ptr()) if df is not None else None))
+        self._check(self.lib.mioc_conv_eval_device(self.h, K, ptr(x), ptr(J), ptr(df)))
 
     def conv_tiles_per_wave(self, nt, K):
         """1 or 2: the column tiles per wave of the product kernel that K restarts at nt run
@@ -793,13 +717,11 @@ class Context:
     def rand_start_tensor(self, out, seed, jumps=-1):
         """rand_func_int (HelpFunctions.jl:204-225) for K restarts into out, a (K, nt, M) float64 CUDA tensor;
         jumps < 0: floor(nt / 10).  Enqueued (mioc_rand_start_device)."""
-        if out.dim() != 3 or not out.is_contiguous() or not out.is_cuda or str(out.dtype) != "torch.float64":
-            raise ValueError("out must be a contiguous float64 CUDA tensor of shape (K, nt, M)")
+        check_tensor("out", out, dim=3)
         K, nt, M = out.shape
         if M != self.M:
             raise ValueError("out's last dimension must be the levels' M")
-        self._check(self.lib.mioc_rand_start_device(self.h, K, nt, int(jumps), ctypes.c_uint64(int(seed)),
-                                                    ctypes.c_void_p(out.data_ptr())))
+        self._check(self.lib.mioc_rand_start_device(self.h, K, nt, int(jumps), ctypes.c_uint64(int(seed)), ptr(out)))
 
     def synchronize(self):
         self._check(self.lib.mioc_synchronize(self.h))

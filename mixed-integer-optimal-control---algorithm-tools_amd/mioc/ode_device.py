@@ -2,27 +2,29 @@
 
 The reference's extension point is the objective (julia_opt/ODEObjective.jl:243-248: F!, Fy!, Fu!, G, Gy!, Gu!).
 ``ODEProgram`` hands the hooks to ``libmioc.so`` as text; the library compiles them into its explicit-Euler / adjoint
-sweep for gfx950 at run time (mioc_ode_program_create) and ``Context.ode_program_eval_tensors`` runs that kernel.  The
+sweep for gfx950 at run time and ``Context.ode_program_eval_tensors`` runs that kernel.  The
 hook contract (signatures, the step index each hook sees, zeroing, rounding order) is in ``include/mioc.h``.
 ``ODEProgram(..., integrator="heun" | "rk4", substeps=m)`` compiles the hooks into a Heun / classical RK4 sweep with m
-substeps per control interval instead (mioc_ode_program_create_ex): the states are integrated as accurately as needed
+substeps per control interval instead: the states are integrated as accurately as needed
 while nt, and with it the DP, follows how finely the control should switch.  ``integrator="beuler" | "midpoint"`` are
 backward Euler and the implicit midpoint rule for stiff dynamics: Newton's method per substep on the device, the
 gradient by the implicit function theorem; a restart whose Newton iteration fails returns NaN for J and its df row.
 ``ODEProgram(..., derive="all" | ("Fy", "Gy", ...))`` takes F and G as templates over the scalar type and has the
-library generate the named derivative hooks by forward-mode AD (mioc_ode_program_create_ad; include/mioc.h, "Derived
+library generate the named derivative hooks by forward-mode AD (include/mioc.h, "Derived
 hooks"); ``check_hooks`` uses that to tell which hand-written derivative hook is wrong.
-``ODEProgram(..., ndata=n, terminal=True, states=True)`` (mioc_ode_program_create_bolza; include/mioc.h, "Terminal
+``ODEProgram(..., ndata=n, terminal=True, states=True)`` (include/mioc.h, "Terminal
 cost, sampled data, state output") adds n columns of sampled data behind the parameters (``p[NP + e]``, the row of the
 hook's control column), a terminal cost ``E`` with ``Ey`` (derivable: ``derive`` takes "Ey"), and the states at the
 control-grid points as an output (``DeviceODEProblem.states``).
-``ODEProgram(..., scenarios=True | "data")`` (mioc_ode_program_create_scen; include/mioc.h, "Scenarios") lets the
+``ODEProgram(..., scenarios=True | "data")`` (include/mioc.h, "Scenarios") lets the
 restarts of one call solve different problems: ``DeviceODEProblem`` / ``MixedODEProblem`` then take S initial states
 and parameter vectors (with "data" also S data tables), and restart k of ``TRM_batch`` / ``TRM_mixed_batch`` solves
 scenario k % S; ``best_per_scenario`` picks each scenario's best restart.
-``ODEProgram(..., sensitivities=True | "p" | "y0")`` (mioc_ode_program_create_sens; include/mioc.h, "Sensitivities")
+``ODEProgram(..., sensitivities=True | "p" | "y0")`` (include/mioc.h, "Sensitivities")
 makes dJ/dparams and dJ/dstate0 outputs of an evaluation for every integrator but "euler": the text then also defines
 ``Fp``, ``Gp`` (and ``Ep``), or ``derive`` names them; ``DeviceODEProblem.sensitivities`` returns them.
+Whatever is asked for, Python always calls the library's ``_sens`` entries (create, source, eval): every older entry
+of the C ABI forwards to them with the arguments it lacks zero, so the compiler sees the same text.
 
 ``EXAMPLE_SOURCES`` restates the three built-in problems as hook text, term for term as ``Hooks<...>`` of
 csrc/mioc_ode.hip has them, so each reproduces mioc_ode_eval_device bit for bit; they double as templates.  Parameter
@@ -69,14 +71,14 @@ INTEGRATORS = {"euler": MIOC_ODE_INT_EULER, "heun": MIOC_ODE_INT_HEUN, "rk4": MI
                "beuler": MIOC_ODE_INT_BEULER, "midpoint": MIOC_ODE_INT_MIDPOINT}
 MAX_SUBSTEPS = 64
 MAX_NDATA = 16
-DERIVE_BITS = {"Fy": MIOC_ODE_DERIVE_FY, "Fu": MIOC_ODE_DERIVE_FU, "Gy": MIOC_ODE_DERIVE_GY, "Gu": MIOC_ODE_DERIVE_GU}
-DERIVE_BITS_TERMINAL = dict(DERIVE_BITS, Ey=MIOC_ODE_DERIVE_EY)  # with a terminal cost
-DERIVE_BITS_P = {"Fp": MIOC_ODE_DERIVE_FP, "Gp": MIOC_ODE_DERIVE_GP}  # with sensitivities in the parameters
-DERIVE_BITS_EVERY = dict(DERIVE_BITS_TERMINAL, **DERIVE_BITS_P, Ep=MIOC_ODE_DERIVE_EP)
+# every derivable hook and its bit: E* only with a terminal cost, *p only with sensitivities in the parameters
+DERIVE_BITS_EVERY = {"Fy": MIOC_ODE_DERIVE_FY, "Fu": MIOC_ODE_DERIVE_FU, "Gy": MIOC_ODE_DERIVE_GY,
+                     "Gu": MIOC_ODE_DERIVE_GU, "Ey": MIOC_ODE_DERIVE_EY, "Fp": MIOC_ODE_DERIVE_FP,
+                     "Gp": MIOC_ODE_DERIVE_GP, "Ep": MIOC_ODE_DERIVE_EP}
 
 
 def sensitivity_bits(sensitivities):
-    """``sensitivities`` (False, True, "p" or "y0") as the sens argument of mioc_ode_program_create_sens."""
+    """``sensitivities`` (False, True, "p" or "y0") as the sens argument of the library's create entry."""
     if sensitivities is False or sensitivities is None:
         return 0
     if sensitivities is True:
@@ -91,12 +93,8 @@ def derive_names(derive, terminal=False, sens_p=False):
     only a program with a terminal cost has it, and "all" includes it there)(, Fp, Gp: only a program with
     sensitivities in the parameters has them, ``sens_p``; then Ep with a terminal cost).  "all" stays the y and u hooks
     whether or not sensitivities are on; "all+p" adds Fp, Gp (and Ep) and needs ``sens_p``."""
-    bits = dict(DERIVE_BITS_TERMINAL if terminal else DERIVE_BITS)
-    plain = tuple(bits)
-    if sens_p:
-        bits.update(DERIVE_BITS_P)
-        if terminal:
-            bits["Ep"] = MIOC_ODE_DERIVE_EP
+    bits = [n for n in DERIVE_BITS_EVERY if (terminal or n[0] != "E") and (sens_p or n[1] != "p")]
+    plain = tuple(n for n in bits if n[1] != "p")
     if isinstance(derive, str):
         if derive == "all+p" and not sens_p:
             raise ValueError('derive "all+p" needs sensitivities in the parameters (sensitivities=True or "p")')
@@ -115,7 +113,7 @@ def derive_names(derive, terminal=False, sens_p=False):
 
 
 def scenario_bits(scenarios, ndata=0):
-    """``scenarios`` (False, True or "data") as the scen argument of mioc_ode_program_create_scen."""
+    """``scenarios`` (False, True or "data") as the scen argument of the library's create entry."""
     if scenarios is False or scenarios is None:
         return 0
     if scenarios is True:
@@ -127,30 +125,35 @@ def scenario_bits(scenarios, ndata=0):
     raise ValueError(f'scenarios must be False, True or "data", not {scenarios!r}')
 
 
-def program_source(source, ny, nx, nparams, integrator="euler", substeps=1, derive=(), ndata=0, terminal=False,
-                   states=False, noinline=False, scenarios=False, sensitivities=False):
-    """The text the library hands to the compiler for ``ODEProgram(source, ny, ...)`` (mioc_ode_program_source; with
-    ``scenarios`` mioc_ode_program_source_scen, with ``sensitivities`` mioc_ode_program_source_sens), as a str; nothing
-    is compiled.  noinline: the text of the second compile of derived hooks (include/mioc.h)."""
-    lib = load_library()
-    text = source.encode() if isinstance(source, str) else source
-    sens = sensitivity_bits(sensitivities)
-    mask = sum(DERIVE_BITS_EVERY[n] for n in derive_names(derive, terminal, bool(sens & MIOC_ODE_SENS_P)))
+def _program_args(source, ny, nx, nparams, integrator, substeps, derive, ndata, terminal, states, scen, sens):
+    """(the derive names, the arguments that the library's _create_sens and _source_sens entries share): ``derive`` as
+    derive_names takes it, ``scen`` and ``sens`` as scenario_bits and sensitivity_bits return them."""
+    names = derive_names(derive, terminal, bool(sens & MIOC_ODE_SENS_P))
+    mask = sum(DERIVE_BITS_EVERY[n] for n in names)
     flags = (MIOC_ODE_TERMINAL if terminal else 0) | (MIOC_ODE_STATES if states else 0)
-    scen = scenario_bits(scenarios, ndata)
-    args = (text, int(ny), int(nx), int(nparams), int(ndata), INTEGRATORS[integrator], int(substeps), mask, flags)
-    if sens:
-        entry, args = lib.mioc_ode_program_source_sens, args + (scen, sens, int(bool(noinline)))
-    elif scen:
-        entry, args = lib.mioc_ode_program_source_scen, args + (scen, int(bool(noinline)))
-    else:
-        entry, args = lib.mioc_ode_program_source, args + (int(bool(noinline)),)
+    text = source.encode() if isinstance(source, str) else source
+    return names, (text, int(ny), int(nx), int(nparams), int(ndata), INTEGRATORS[integrator], int(substeps), mask,
+                   flags, scen, sens)
+
+
+def _source_text(args, noinline):
+    """The text the library assembles for _program_args' ``args``: the entry is asked for the size, then the text."""
+    entry, args = load_library().mioc_ode_program_source_sens, args + (int(bool(noinline)),)
     need = entry(*args, None, 0)
     if need < 0:
-        raise MiocNativeError(need, "mioc_ode_program_source: bad arguments")
+        raise MiocNativeError(need, "the library's program source entry: bad arguments")
     buf = ctypes.create_string_buffer(need + 1)
     entry(*args, buf, need + 1)
     return buf.value.decode()
+
+
+def program_source(source, ny, nx, nparams, integrator="euler", substeps=1, derive=(), ndata=0, terminal=False,
+                   states=False, noinline=False, scenarios=False, sensitivities=False):
+    """The text the library hands to the compiler for ``ODEProgram(source, ny, ...)``, as a str; nothing is compiled
+    (the library's _source_sens entry, which every older source entry forwards to).  noinline: the text of the second
+    compile of derived hooks (include/mioc.h)."""
+    return _source_text(_program_args(source, ny, nx, nparams, integrator, substeps, derive, ndata, terminal, states,
+                                      scenario_bits(scenarios, ndata), sensitivity_bits(sensitivities))[1], noinline)
 
 
 class ODEProgram:
@@ -194,7 +197,6 @@ class ODEProgram:
         self.ndata = int(ndata)
         self.scenarios = scenario_bits(scenarios, self.ndata)
         self.sens = sensitivity_bits(sensitivities)
-        self.derive = derive_names(derive, self.terminal, bool(self.sens & MIOC_ODE_SENS_P))
         if integrator not in INTEGRATORS:
             raise ValueError(f"integrator must be one of {sorted(INTEGRATORS)}, not {integrator!r}")
         if int(substeps) != substeps or not 1 <= substeps <= MAX_SUBSTEPS:
@@ -207,54 +209,24 @@ class ODEProgram:
         self.integrator, self.substeps = integrator, int(substeps)
         self.lib = load_library()
         self.ny, self.nx, self.nparams = int(ny), int(nx), int(nparams)
+        self.derive, self._args = _program_args(source, ny, nx, nparams, integrator, substeps, derive, self.ndata,
+                                                self.terminal, self.states, self.scenarios, self.sens)
         h = ctypes.c_void_p()
         log = ctypes.create_string_buffer(self.LOG_CAP)
-        text = source.encode() if isinstance(source, str) else source
-        if self.sens:
-            mask = sum(DERIVE_BITS_EVERY[n] for n in self.derive)
-            flags = (MIOC_ODE_TERMINAL if self.terminal else 0) | (MIOC_ODE_STATES if self.states else 0)
-            rc = self.lib.mioc_ode_program_create_sens(text, self.ny, self.nx, self.nparams, self.ndata,
-                                                       INTEGRATORS[integrator], self.substeps, mask, flags,
-                                                       self.scenarios, self.sens, ctypes.byref(h), log, self.LOG_CAP)
-        elif self.scenarios:
-            mask = sum(DERIVE_BITS_TERMINAL[n] for n in self.derive)
-            flags = (MIOC_ODE_TERMINAL if self.terminal else 0) | (MIOC_ODE_STATES if self.states else 0)
-            rc = self.lib.mioc_ode_program_create_scen(text, self.ny, self.nx, self.nparams, self.ndata,
-                                                       INTEGRATORS[integrator], self.substeps, mask, flags,
-                                                       self.scenarios, ctypes.byref(h), log, self.LOG_CAP)
-        elif self.ndata or self.terminal or self.states:
-            mask = sum(DERIVE_BITS_TERMINAL[n] for n in self.derive)
-            flags = (MIOC_ODE_TERMINAL if self.terminal else 0) | (MIOC_ODE_STATES if self.states else 0)
-            rc = self.lib.mioc_ode_program_create_bolza(text, self.ny, self.nx, self.nparams, self.ndata,
-                                                        INTEGRATORS[integrator], self.substeps, mask, flags,
-                                                        ctypes.byref(h), log, self.LOG_CAP)
-        elif self.derive:
-            mask = sum(DERIVE_BITS[n] for n in self.derive)
-            rc = self.lib.mioc_ode_program_create_ad(text, self.ny, self.nx, self.nparams, INTEGRATORS[integrator],
-                                                     self.substeps, mask, ctypes.byref(h), log, self.LOG_CAP)
-        elif integrator == "euler":
-            rc = self.lib.mioc_ode_program_create(text, self.ny, self.nx, self.nparams, ctypes.byref(h), log,
-                                                  self.LOG_CAP)
-        else:
-            rc = self.lib.mioc_ode_program_create_ex(text, self.ny, self.nx, self.nparams, INTEGRATORS[integrator],
-                                                     self.substeps, ctypes.byref(h), log, self.LOG_CAP)
+        rc = self.lib.mioc_ode_program_create_sens(*self._args, ctypes.byref(h), log, self.LOG_CAP)
         self.log = log.value.decode(errors="replace")
         if rc == MIOC_ECOMPILE:
             raise MiocCompileError(rc, self.log)
         if rc != MIOC_OK:
-            raise MiocNativeError(rc, self.log or "mioc_ode_program_create: bad ny / nx / nparams / source "
+            raise MiocNativeError(rc, self.log or "the library's program create entry: bad ny / nx / nparams / source "
                                                   "(1 <= ny, nx <= 8, 0 <= nparams <= 32, 0 <= ndata <= 16, at most 1 MiB "
                                                   "of text)")
         self.h = h
-        self._source = text
         _LIVE.add(self)
 
     def source_text(self, noinline=False):
-        """The text this program was compiled from (mioc_ode_program_source); noinline: that of the second compile."""
-        return program_source(self._source, self.ny, self.nx, self.nparams, self.integrator, self.substeps,
-                              self.derive, self.ndata, self.terminal, self.states, noinline,
-                              {0: False, MIOC_ODE_SCEN: True}.get(self.scenarios, "data"),
-                              {0: False, MIOC_ODE_SENS_P: "p", MIOC_ODE_SENS_Y0: "y0"}.get(self.sens, True))
+        """The text this program was compiled from; noinline: that of the second compile."""
+        return _source_text(self._args, noinline)
 
     def close(self):
         if self.h:
@@ -278,7 +250,141 @@ class ODEProgram:
             pass
 
 
-class DeviceODEProblem:
+class _ODEProblem:
+    """What DeviceODEProblem (nu = 0) and MixedODEProblem (nu >= 1 continuous controls in front) share: the program,
+    the levels V of the integer controls and their iterator, [T0, T1], nt, the inputs state0 / params / data, and
+    everything that evaluates them.  It has the members mioc.trm_batch.TRM_batch asks of a problem."""
+
+    def __init__(self, program, nu, V, iterator, T0, T1, nt, state0, params, data):
+        import numpy as np
+        self.program, self.nu = program, int(nu)
+        self.V = [list(v) for v in V]
+        self.iterator = iterator
+        self.T0, self.T1, self.nt = float(T0), float(T1), int(nt)
+        self._device_data = {}  # per device used: {"state0", "params", "data"} as tensors; None: passed from the host
+        if not self.T1 > self.T0 or self.nt < 1:
+            raise ValueError("need T1 > T0 and nt >= 1")
+        scen, nd = getattr(program, "scenarios", 0), getattr(program, "ndata", 0)
+        if (data is None) != (nd == 0):
+            raise ValueError(f"the program reads {nd} columns of sampled data: give data of shape (nt, {nd})" if nd else
+                             "the program reads no sampled data")
+        sizes = {}
+
+        def take(name, a, shape, may_lead):
+            a = np.array(a, dtype=np.float64, order="C", copy=True)
+            if a.shape == shape:
+                return a
+            if may_lead and a.ndim == len(shape) + 1 and a.shape[1:] == shape and a.shape[0] >= 1:
+                sizes[name] = a.shape[0]
+                return a
+            lead = f" or (S,) + {shape}" if may_lead else ""
+            raise ValueError(f"{name} must have the shape {shape}{lead}, not {a.shape}" +
+                             ("" if scen else ": inputs per scenario need a program compiled with scenarios"))
+        y0 = take("state0", state0, (program.ny,), bool(scen))
+        par = take("params", np.zeros(0) if program.nparams == 0 and np.size(params) == 0 and np.ndim(params) < 2
+                   else params, (program.nparams,), bool(scen))
+        dat = None if data is None else take("data", data, (self.nt, nd), bool(scen & MIOC_ODE_SCEN_DATA))
+        if len(set(sizes.values())) > 1:
+            raise ValueError(f"the numbers of scenarios disagree: {sizes}")
+        self._scen, self._S = bool(scen), next(iter(sizes.values()), 1)
+        if scen:  # (S, ny), (S, nparams) and, per scenario, (S, nt, ndata): an input without the leading size is shared
+            y0, par = (np.array(np.broadcast_to(a, (self._S,) + a.shape[-1:]), order="C", copy=True) for a in (y0, par))
+            if dat is not None and scen & MIOC_ODE_SCEN_DATA:
+                dat = np.array(np.broadcast_to(dat, (self._S, self.nt, nd)), order="C", copy=True)
+        self.state0, self.params, self.data = (y0, par, dat) if scen else (y0.tolist(), par.tolist(), dat)
+
+    def _eval(self, ctx, x, J=None, df=None, Y=None, Jp=None, Jy0=None):
+        """One evaluation at the controls x (K, nt, nx) on ctx, into the outputs given.  The problem's arrays are
+        uploaded to the device of x at the first use there and kept; with scenarios restart k solves scenario k % S."""
+        self.check_restarts(x.shape[0])
+        if self.data is not None and x.shape[1] != self.nt:
+            raise ValueError(f"the problem's data fix nt = {self.nt}; x has {x.shape[1]} steps")
+        key = str(x.device)
+        if key not in self._device_data:
+            import torch
+            lay = self.device_layouts() if self._scen else {"state0": None, "params": None, "data": self.data}
+            self._device_data[key] = {n: None if a is None else torch.tensor(a, dtype=torch.float64, device=x.device)
+                                      for n, a in lay.items()}
+            torch.cuda.current_stream(x.device).synchronize()  # the upload before the context's stream reads it
+        d = self._device_data[key]
+        host = (x, self.T0, self.T1, self.state0, self.params, J, df, d["data"], Y, Jp, Jy0)
+        if self._scen:
+            ctx.ode_program_eval_scen_tensors(self.program, self.nu, x, self.T0, self.T1, self._S, d["state0"],
+                                              d["params"], d["data"], J, df, Y, Jp, Jy0)
+        elif self.nu:
+            ctx.ode_program_eval_mixed_tensors(self.program, self.nu, *host)
+        else:
+            ctx.ode_program_eval_tensors(self.program, *host)
+
+    def eval_tensors(self, ctx, x, J=None, df=None):
+        """J (K,) and df (K, nt, nx) at the controls x, each optional; enqueued on ctx."""
+        self._eval(ctx, x, J, df)
+
+    def states(self, ctx, x):
+        """The states (K, nt + 1, ny) of the controls x (K, nt, nx) at the control-grid points t_i = T0 + i tau; row 0
+        is state0 (with scenarios: that of scenario k % S).  The program must have been compiled with states=True.
+        Synchronises the context."""
+        import torch
+        Y = torch.empty(x.shape[0], x.shape[1] + 1, self.program.ny, dtype=torch.float64, device=x.device)
+        torch.cuda.current_stream(x.device).synchronize()
+        self._eval(ctx, x, Y=Y)
+        ctx.synchronize()
+        return Y
+
+    def sensitivities(self, ctx, x):
+        """(Jp (K, nparams), Jy0 (K, ny)): dJ/dparams and dJ/dstate0 at the controls x (K, nt, nx), as CUDA tensors;
+        a part the program was not compiled for comes back as None (with scenarios: restart k's derivatives in
+        scenario k % S's own values).  ValueError for a program without sensitivities.  Synchronises the context."""
+        import torch
+        prog = self.program
+        sens = int(getattr(prog, "sens", 0))
+        if not sens:
+            raise ValueError("the program was not compiled with sensitivities")
+        K = x.shape[0]
+        Jp = torch.empty(K, prog.nparams, dtype=torch.float64, device=x.device) if sens & MIOC_ODE_SENS_P else None
+        Jy0 = torch.empty(K, prog.ny, dtype=torch.float64, device=x.device) if sens & MIOC_ODE_SENS_Y0 else None
+        torch.cuda.current_stream(x.device).synchronize()
+        self._eval(ctx, x, Jp=Jp, Jy0=Jy0)
+        ctx.synchronize()
+        return Jp, Jy0
+
+    @property
+    def S(self):
+        """The number of scenarios (1 for a program without them)."""
+        return self._S
+
+    def device_layouts(self):
+        """The numpy arrays a scenario problem uploads, the scenario index fastest (include/mioc.h, "Scenarios"):
+        {"state0": (ny, S), "params": (nparams, S), "data": (nt, ndata), (nt, ndata, S) per scenario, or None}."""
+        import numpy as np
+        if not self._scen:
+            raise ValueError("the program was not compiled with scenarios")
+        data = self.data
+        if data is not None and data.ndim == 3:
+            data = np.ascontiguousarray(data.transpose(1, 2, 0))
+        return {"state0": np.ascontiguousarray(self.state0.T), "params": np.ascontiguousarray(self.params.T),
+                "data": data}
+
+    def check_restarts(self, K):
+        """ValueError unless K restarts divide evenly among the problem's scenarios."""
+        if self._scen and (K is None or int(K) < 1 or int(K) % self._S):
+            raise ValueError(f"K = {K} restarts do not divide among the problem's S = {self._S} scenarios: K % S != 0")
+
+    # the rest of what TRM_batch asks of a problem
+    def level_table(self):
+        from .iterators import LevelTable
+        return LevelTable(self.V, self.iterator)
+
+    @property
+    def fixes_nt(self):
+        """False, or why a caller cannot choose nt."""
+        return "the problem's sampled data fix nt" if self.data is not None else False
+
+    def setup(self, ctx):
+        """Nothing: the arrays are uploaded at the first evaluation."""
+
+
+class DeviceODEProblem(_ODEProblem):
     """An ODE-constrained problem for TRM_batch: a compiled ``ODEProgram`` with the data the Julia objective holds --
     the levels V and their iterator (None: the product grid), [T0, T1], the default number of steps nt, state0 and
     the parameters; ``data``: the (nt, ndata) samples of a program with ndata > 0, which fix nt (uploaded once per
@@ -290,47 +396,12 @@ class DeviceODEProblem:
     state0 (S, ny), params (S, nparams) and data as numpy arrays; ``device_layouts()`` are the arrays uploaded."""
 
     def __init__(self, program, V, iterator, T0, T1, nt, state0, params=(), data=None):
-        self.program = program
-        self.V = [list(v) for v in V]
-        self.iterator = iterator
-        self.T0, self.T1, self.nt = float(T0), float(T1), int(nt)
+        super().__init__(program, 0, V, iterator, T0, T1, nt, state0, params, data)
         if len(self.V) != program.nx:
-            raise ValueError("V, state0 and params must match the program's nx, ny and nparams")
-        _problem_inputs(self, state0, params, data, "V, state0 and params must match the program's nx, ny and nparams")
-
-    def eval_tensors(self, ctx, x, J=None, df=None):
-        if self._S:
-            return _eval_scenarios(self, ctx, None, x, J, df, None)
-        ctx.ode_program_eval_tensors(self.program, x, self.T0, self.T1, self.state0, self.params, J, df,
-                                     data=_data_on(self, x))
-
-    def states(self, ctx, x):
-        """The states (K, nt + 1, ny) of the controls x (K, nt, nx) at the control-grid points t_i = T0 + i tau; row 0
-        is state0 (with scenarios: that of scenario k % S).  The program must have been compiled with states=True.
-        Synchronises the context."""
-        return _states(self, ctx, x, None)
-
-    def sensitivities(self, ctx, x):
-        """(Jp (K, nparams), Jy0 (K, ny)): dJ/dparams and dJ/dstate0 at the controls x (K, nt, nx), as CUDA tensors;
-        a part the program was not compiled for comes back as None (with scenarios: restart k's derivatives in
-        scenario k % S's own values).  ValueError for a program without sensitivities.  Synchronises the context."""
-        return _sensitivities(self, ctx, x, None)
-
-    @property
-    def S(self):
-        """The number of scenarios (1 for a program without them)."""
-        return self._S or 1
-
-    def device_layouts(self):
-        """_device_layouts(self): the numpy arrays a scenario problem uploads."""
-        return _device_layouts(self)
-
-    def check_restarts(self, K):
-        """ValueError unless K restarts divide evenly among the problem's scenarios."""
-        _check_restarts(self, K)
+            raise ValueError("V must have one entry per control: the program's nx")
 
 
-class MixedODEProblem:
+class MixedODEProblem(_ODEProblem):
     """An ODE-constrained problem with mixed controls for mioc.trm_mixed.TRM_mixed_batch: a compiled ``ODEProgram``
     whose first ``nu`` controls are continuous with the pointwise bounds ``lo`` <= ``hi`` (scalars, (nu,) or (nt, nu);
     kept as (nt, nu) numpy arrays, the device layout) and whose other nx - nu controls take the levels V with their
@@ -339,16 +410,11 @@ class MixedODEProblem:
 
     def __init__(self, program, nu, lo, hi, V, iterator, T0, T1, nt, state0, params=(), data=None):
         import numpy as np
-        self.program = program
-        self.nu = int(nu)
-        self.V = [list(v) for v in V]
-        self.iterator = iterator
-        self.T0, self.T1, self.nt = float(T0), float(T1), int(nt)
-        if int(nu) != nu or not 1 <= self.nu < program.nx:
+        if int(nu) != nu or not 1 <= nu < program.nx:
             raise ValueError(f"nu must be an integer in 1..{program.nx - 1} (nu = 0: DeviceODEProblem), not {nu!r}")
+        super().__init__(program, nu, V, iterator, T0, T1, nt, state0, params, data)
         if len(self.V) != program.nx - self.nu:
             raise ValueError("V must have one entry per integer control: the program's nx - nu")
-        _problem_inputs(self, state0, params, data, "state0 and params must match the program's ny and nparams")
 
         def bound(b, name):
             b = np.asarray(b, dtype=np.float64)
@@ -358,122 +424,6 @@ class MixedODEProblem:
         self.lo, self.hi = bound(lo, "lo"), bound(hi, "hi")
         if not np.all(self.lo <= self.hi):  # also refuses a NaN bound
             raise ValueError("need lo <= hi everywhere")
-
-    def eval_tensors(self, ctx, x, J=None, df=None):
-        if self._S:
-            return _eval_scenarios(self, ctx, self.nu, x, J, df, None)
-        ctx.ode_program_eval_mixed_tensors(self.program, self.nu, x, self.T0, self.T1, self.state0, self.params, J, df,
-                                           data=_data_on(self, x))
-
-    def states(self, ctx, x):
-        """DeviceODEProblem.states for a mixed control."""
-        return _states(self, ctx, x, self.nu)
-
-    def sensitivities(self, ctx, x):
-        """DeviceODEProblem.sensitivities for a mixed control."""
-        return _sensitivities(self, ctx, x, self.nu)
-
-    @property
-    def S(self):
-        """The number of scenarios (1 for a program without them)."""
-        return self._S or 1
-
-    def device_layouts(self):
-        """_device_layouts(self): the numpy arrays a scenario problem uploads."""
-        return _device_layouts(self)
-
-    def check_restarts(self, K):
-        """ValueError unless K restarts divide evenly among the problem's scenarios."""
-        _check_restarts(self, K)
-
-
-def _problem_inputs(problem, state0, params, data, mismatch):
-    """state0, params, data and S of a problem: for a program without scenarios the lists and the (nt, ndata) array they
-    always were and S = 0 (``problem.S`` then reads 1); for a scenario program (S, ny), (S, nparams) and (nt, ndata) or
-    (S, nt, ndata) float64 arrays, inputs without the leading size broadcast."""
-    import numpy as np
-    program, nt = problem.program, problem.nt
-    problem._device_data = {}
-    if not getattr(program, "scenarios", 0):
-        try:
-            problem.state0 = [float(v) for v in state0]
-            problem.params = [float(v) for v in params]
-        except TypeError:  # rows where numbers belong: only a scenario program takes (S, ny) and (S, nparams)
-            raise ValueError(mismatch + "; state0 and params per scenario need a program compiled with scenarios")
-        if len(problem.state0) != program.ny or len(problem.params) != program.nparams:
-            raise ValueError(mismatch)
-        if not problem.T1 > problem.T0 or nt < 1:
-            raise ValueError("need T1 > T0 and nt >= 1")
-        problem.data = _problem_data(program, nt, data)
-        problem._S = 0
-        return
-    if not problem.T1 > problem.T0 or nt < 1:
-        raise ValueError("need T1 > T0 and nt >= 1")
-    nd, per_data = program.ndata, bool(program.scenarios & MIOC_ODE_SCEN_DATA)
-    if (data is None) != (nd == 0):
-        raise ValueError(f"the program reads {nd} columns of sampled data: give data of shape (nt, {nd})" if nd else
-                         "the program reads no sampled data")
-    sizes = {}
-
-    def take(name, a, shape, may_lead=True):
-        a = np.array(a, dtype=np.float64, order="C", copy=True)
-        if a.shape == shape:
-            return a
-        if may_lead and a.ndim == len(shape) + 1 and a.shape[1:] == shape and a.shape[0] >= 1:
-            sizes[name] = a.shape[0]
-            return a
-        lead = f" or (S,) + {shape}" if may_lead else ""
-        raise ValueError(f"{name} must have the shape {shape}{lead}, not {a.shape}")
-    y0 = take("state0", state0, (program.ny,))
-    par = take("params", np.zeros(0) if program.nparams == 0 and np.size(params) == 0 and np.ndim(params) < 2
-               else params, (program.nparams,))
-    dat = None if data is None else take("data", data, (nt, nd), per_data)
-    if len(set(sizes.values())) > 1:
-        raise ValueError(f"the numbers of scenarios disagree: {sizes}")
-    S = next(iter(sizes.values()), 1)
-    problem._S = S
-    problem.state0 = np.array(np.broadcast_to(y0, (S, program.ny)), order="C", copy=True)
-    problem.params = np.array(np.broadcast_to(par, (S, program.nparams)), order="C", copy=True)
-    problem.data = dat if dat is None or not per_data else np.array(np.broadcast_to(dat, (S, nt, nd)), order="C",
-                                                                    copy=True)
-
-
-def _device_layouts(problem):
-    """The numpy arrays a scenario problem uploads, the scenario index fastest (include/mioc.h, "Scenarios"):
-    {"state0": (ny, S), "params": (nparams, S), "data": (nt, ndata), (nt, ndata, S) per scenario, or None}."""
-    import numpy as np
-    if not problem._S:
-        raise ValueError("the program was not compiled with scenarios")
-    data = problem.data
-    if data is not None and data.ndim == 3:
-        data = np.ascontiguousarray(data.transpose(1, 2, 0))
-    return {"state0": np.ascontiguousarray(problem.state0.T), "params": np.ascontiguousarray(problem.params.T),
-            "data": data}
-
-
-def _check_restarts(problem, K):
-    if problem._S and (K is None or int(K) < 1 or int(K) % problem._S):
-        raise ValueError(f"K = {K} restarts do not divide among the problem's S = {problem._S} scenarios: K % S != 0")
-
-
-def _scenarios_on(problem, x):
-    """The problem's scenario arrays on the device of x: uploaded at the first use there, then kept."""
-    if x.shape[1] != problem.nt and problem.data is not None:
-        raise ValueError(f"the problem's data fix nt = {problem.nt}; x has {x.shape[1]} steps")
-    key = str(x.device)
-    if key not in problem._device_data:
-        import torch
-        problem._device_data[key] = {n: None if a is None else torch.tensor(a, dtype=torch.float64, device=x.device)
-                                     for n, a in _device_layouts(problem).items()}
-        torch.cuda.current_stream(x.device).synchronize()  # the upload before the context's stream reads it
-    return problem._device_data[key]
-
-
-def _eval_scenarios(problem, ctx, nu, x, J, df, Y, Jp=None, Jy0=None):
-    _check_restarts(problem, x.shape[0])
-    d = _scenarios_on(problem, x)
-    ctx.ode_program_eval_scen_tensors(problem.program, nu, x, problem.T0, problem.T1, problem._S, d["state0"],
-                                      d["params"], d["data"], J, df, Y, Jp, Jy0)
 
 
 def best_per_scenario(values, S):
@@ -487,71 +437,6 @@ def best_per_scenario(values, S):
         raise ValueError(f"{v.size} values do not divide among {S} scenarios")
     v = np.where(np.isnan(v), np.inf, v).reshape(-1, S)
     return np.argmin(v, axis=0) * S + np.arange(S)
-
-
-def _problem_data(program, nt, data):
-    """The (nt, ndata) float64 array of a problem's samples, None for a program without data."""
-    import numpy as np
-    nd = getattr(program, "ndata", 0)
-    if data is None:
-        if nd:
-            raise ValueError(f"the program reads {nd} columns of sampled data: give data of shape (nt, {nd})")
-        return None
-    data = np.array(data, dtype=np.float64, order="C", copy=True)
-    if nd == 0 or data.shape != (nt, nd):
-        raise ValueError(f"data must have the shape (nt, ndata) = ({nt}, {nd})")
-    return data
-
-
-def _data_on(problem, x):
-    """The problem's data on the device of x: uploaded at the first use there, then kept."""
-    if problem.data is None:
-        return None
-    if x.shape[1] != problem.nt:
-        raise ValueError(f"the problem's data fix nt = {problem.nt}; x has {x.shape[1]} steps")
-    key = str(x.device)
-    if key not in problem._device_data:
-        import torch
-        problem._device_data[key] = torch.tensor(problem.data, dtype=torch.float64, device=x.device)
-        torch.cuda.current_stream(x.device).synchronize()  # the upload before the context's stream reads it
-    return problem._device_data[key]
-
-
-def _states(problem, ctx, x, nu):
-    import torch
-    prog = problem.program
-    Y = torch.empty(x.shape[0], x.shape[1] + 1, prog.ny, dtype=torch.float64, device=x.device)
-    torch.cuda.current_stream(x.device).synchronize()
-    args = (x, problem.T0, problem.T1, problem.state0, problem.params)
-    if problem._S:
-        _eval_scenarios(problem, ctx, nu, x, None, None, Y)
-    elif nu is None:
-        ctx.ode_program_eval_tensors(prog, *args, data=_data_on(problem, x), Y=Y)
-    else:
-        ctx.ode_program_eval_mixed_tensors(prog, nu, *args, data=_data_on(problem, x), Y=Y)
-    ctx.synchronize()
-    return Y
-
-
-def _sensitivities(problem, ctx, x, nu):
-    import torch
-    prog = problem.program
-    sens = int(getattr(prog, "sens", 0))
-    if not sens:
-        raise ValueError("the program was not compiled with sensitivities")
-    K = x.shape[0]
-    Jp = torch.empty(K, prog.nparams, dtype=torch.float64, device=x.device) if sens & MIOC_ODE_SENS_P else None
-    Jy0 = torch.empty(K, prog.ny, dtype=torch.float64, device=x.device) if sens & MIOC_ODE_SENS_Y0 else None
-    torch.cuda.current_stream(x.device).synchronize()
-    args = (x, problem.T0, problem.T1, problem.state0, problem.params)
-    if problem._S:
-        _eval_scenarios(problem, ctx, nu, x, None, None, None, Jp, Jy0)
-    elif nu is None:
-        ctx.ode_program_eval_tensors(prog, *args, data=_data_on(problem, x), Jp=Jp, Jy0=Jy0)
-    else:
-        ctx.ode_program_eval_mixed_tensors(prog, nu, *args, data=_data_on(problem, x), Jp=Jp, Jy0=Jy0)
-    ctx.synchronize()
-    return Jp, Jy0
 
 
 _SIG = "(const double *p, int i, double t, const double *y, const double *x"

@@ -10,7 +10,7 @@ The control flow is multi-trust.jl:53-170 per restart, run for K restarts in loc
 
 Device kernels do all O(nt) work: the random starts (mioc_rand_start_device, HelpFunctions.jl:204-225), the ODE
 objective and adjoint gradient (mioc_ode_eval_device, ODEObjective.jl:125-184; for a user-defined ODE objective the
-kernel compiled from its hooks, mioc_ode_program_eval_device) or the PDE heat objective's
+kernel compiled from its hooks, mioc.ode_device) or the PDE heat objective's
 (mioc_heat_eval_device, PDEObjective.jl:129-199) or the convolution objective's (mioc_conv_eval_device,
 example_convolution.jl:128-141), the DP and backtrack with one budget per restart after halving
 (mioc_backtrack_batch_budgets_device), pred and TV_p -- and the control itself: Δᵏ, k, the inner / halved / stopped
@@ -23,6 +23,9 @@ return at once (the state's gate word, mioc_trm_attach).  Restarts that left the
 state update, so every restart follows exactly the sequence of the single-restart loop, including its quirks: the
 gradient of the next outer iteration is taken at the last trial u (obj.x), accepted or not, and a stop returns
 J_old + β·TV_p(u_trial).
+
+``TRM_batch`` knows a problem by its members, not by its type (its docstring lists them): HeatProblem, ConvProblem and
+DeviceODEProblem have them, and so can any other object.
 """
 from __future__ import annotations
 
@@ -44,15 +47,59 @@ def sos1_levels():
     return LevelTable(V, bounded_sum_iterator(V, 1, 1))
 
 
-def TRM_batch(problem, par, K=None, x0=None, seed=0, nt=None, device=0, log=None, inner_chunk=2,  # noqa: C901
-              stats=None):
-    """Run TRM (multi-trust.jl:53-170) for K restarts of an ODE example, or of the PDE heat example, on the device.
+class _ExampleProblem:
+    """One of the reference's three ODE examples (PROBLEMS[name]) as a problem of TRM_batch."""
+    fixes_nt = False
 
-    problem: "fishing" / "doubletank" / "vanderpol", or a mioc.heat.HeatProblem (example_heat.jl: 6 x 6 product
-    levels, gradient from mioc_heat_eval_device; its nt is the problem's), or a mioc.conv.ConvProblem / the string
-    "convolution" = ConvProblem(nt = nt or 2048) (example_convolution.jl: one control, levels -2..2, gradient from
-    mioc_conv_eval_device), or a mioc.ode_device.DeviceODEProblem (a user-defined ODE objective: levels from its V and
-    iterator, gradient from its compiled hooks, mioc_ode_program_eval_device).
+    def __init__(self, name):
+        self.code, self.nt, self.T0, self.T1 = PROBLEMS[name]
+
+    def level_table(self):
+        return sos1_levels()
+
+    def setup(self, ctx):
+        """Nothing: the example's constants are the kernel's."""
+
+    def eval_tensors(self, ctx, x, J=None, df=None):
+        ctx.ode_eval_tensors(self.code, x, self.T0, self.T1, J, df)
+
+    def check_restarts(self, K):
+        """Any number of restarts."""
+
+
+def _inner_loop(trial, poll, kmax, inner_chunk):
+    """The inner iterations of one outer iteration: ``trial()`` enqueues one, ``poll()`` synchronises and returns (any
+    restart still inside its inner loop, the caller's second flag).  At most kmax trials are enqueued, inner_chunk of
+    them between two polls, none after a poll that finds no restart inside.  Returns (polls made, the last poll's
+    second flag: True if there was none)."""
+    done, polls, flag = 0, 0, True
+    while done < kmax:
+        chunk = min(inner_chunk, kmax - done)
+        for _ in range(chunk):
+            trial()
+        done += chunk
+        inner, flag = poll()  # the one read-back per chunk
+        polls += 1
+        if not inner:
+            break
+    return polls, flag
+
+
+def TRM_batch(problem, par, K=None, x0=None, seed=0, nt=None, device=0, log=None, inner_chunk=2, stats=None):
+    """Run TRM (multi-trust.jl:53-170) for K restarts of a problem on the device.
+
+    problem: any object with the members
+      nt, T0, T1        the default number of steps and the horizon;
+      level_table()     the LevelTable of its controls;
+      fixes_nt          False, or the reason why ``nt`` cannot differ from problem.nt (the message raised);
+      setup(ctx)        hands its data to the native.Context (may do nothing);
+      eval_tensors(ctx, x, J, df)   enqueues J (K,) and / or df (K, nt, nx) at the controls x (K, nt, nx);
+      check_restarts(K) ValueError if K restarts cannot be run (may do nothing)
+    -- a mioc.heat.HeatProblem (example_heat.jl: 6 x 6 product levels, gradient from mioc_heat_eval_device), a
+    mioc.conv.ConvProblem (example_convolution.jl: one control, levels -2..2, gradient from mioc_conv_eval_device), a
+    mioc.ode_device.DeviceODEProblem (a user-defined ODE objective: levels from its V and iterator, gradient from its
+    compiled hooks) -- or one of the strings "fishing" / "doubletank" / "vanderpol" = _ExampleProblem(name) and
+    "convolution" = ConvProblem(nt = nt or 2048).
     x0: a (K, nt, nx) float64 CUDA tensor of starts, or None for K device random starts (rand_func_int with `seed`).
     log: a list to receive (inner iteration, decisions (K,)) after every inner iteration (debugging: one stream
     synchronisation each).  inner_chunk: inner iterations enqueued between two read-backs of the control flags.
@@ -61,122 +108,78 @@ def TRM_batch(problem, par, K=None, x0=None, seed=0, nt=None, device=0, log=None
     Returns (values (K,) numpy: J + β·TV_p(u) per restart, u (K, nt, nx) CUDA tensor: obj.x of each restart,
     iterations (K,) numpy)."""
     import torch
-
-    from .conv import ConvProblem
-    from .ode_device import DeviceODEProblem
-    if isinstance(problem, str) and problem == "convolution":
-        problem = ConvProblem(nt=nt or 2048)
-    if isinstance(problem, DeviceODEProblem):  # a scenario problem: restart k solves scenario k % S, so S divides K
-        problem.check_restarts(K if x0 is None else x0.shape[0])
-    ctx = Context(device)
-    if isinstance(problem, ConvProblem):  # the signal reconstruction objective (example_convolution.jl:128-141)
-        cp = problem
-        nt_def, T0, T1 = cp.nt, cp.T0, cp.T1
-        if nt is not None and int(nt) != cp.nt:
-            raise ValueError("the convolution problem fixes nt")
-        lt = LevelTable(cp.levels)
-        cp.setup(ctx)
-
-        def evalf(x, J, df):
-            ctx.conv_eval_tensors(x, J, df)
-    elif isinstance(problem, DeviceODEProblem):  # a user-defined ODE objective (mioc_ode_program_eval_device)
-        dp = problem
-        nt_def, T0, T1 = dp.nt, dp.T0, dp.T1
-        if dp.data is not None and nt is not None and int(nt) != dp.nt:
-            raise ValueError("the problem's sampled data fix nt")
-        lt = LevelTable(dp.V, dp.iterator)
-
-        def evalf(x, J, df):
-            dp.eval_tensors(ctx, x, J, df)
-    elif isinstance(problem, str):
-        prob, nt_def, T0, T1 = PROBLEMS[problem]
-        lt = sos1_levels()
-
-        def evalf(x, J, df):
-            ctx.ode_eval_tensors(prob, x, T0, T1, J, df)
-    else:  # the PDE heat objective (PDEObjective.jl:129-199, example_heat.jl)
-        hp = problem
-        nt_def, T0, T1 = hp.nt, hp.T0, hp.T1
-        if nt is not None and int(nt) != hp.nt:
-            raise ValueError("the heat problem fixes nt")
-        lt = LevelTable(hp.levels)
-        hp.setup(ctx)
-
-        def evalf(x, J, df):
-            ctx.heat_eval_tensors(x, J, df)
-
-    def _to_torch():  # the context's results are read by torch ops
-        ctx.synchronize()
-
-    def _to_ctx():  # torch's writes are read by the context's stream
-        torch.cuda.current_stream(dev).synchronize()
-
-    ctx.set_levels(lt)
-    ctx.set_cost(par.p, par.beta)
+    if isinstance(problem, str):
+        from .conv import ConvProblem
+        problem = ConvProblem(nt=nt or 2048) if problem == "convolution" else _ExampleProblem(problem)
+    problem.check_restarts(K if x0 is None else x0.shape[0])  # a scenario problem: S divides K
+    if problem.fixes_nt and nt is not None and int(nt) != problem.nt:
+        raise ValueError(problem.fixes_nt)
+    T0, T1 = problem.T0, problem.T1
+    lt = problem.level_table()
     dev = torch.device("cuda", device)
-    if x0 is None:
-        nt = nt_def if nt is None else int(nt)
-        u = torch.empty(int(K), nt, lt.M, dtype=torch.float64, device=dev)
-        ctx.rand_start_tensor(u, seed)
-    else:
-        u = x0.to(device=dev, dtype=torch.float64).contiguous().clone()
-    K, nt, _ = u.shape
-    tau = (T1 - T0) / nt
-    beta, D0, sigma, kmax, maxiter = par.beta, par.Delta0, par.sigma, par.kmax, par.maxiter
-    B = int(math.floor(D0 / tau))  # multi-trust.jl:69
-
-    f64 = dict(dtype=torch.float64, device=dev)
-    _to_torch()                            # u (random starts) from the context's stream
-    u_old = u.clone()
-    J_old = torch.empty(K, **f64)
-    tv_u = torch.empty(K, **f64)
-    J = torch.full((K,), math.inf, **f64)
-    df = torch.empty_like(u)
-    trial = torch.empty_like(u)
-    int_val, tv_o, tv_new, pred = (torch.empty(K, **f64) for _ in range(4))
-    J_new = torch.empty(K, **f64)
-    dec = torch.empty(K, dtype=torch.int32, device=dev)
-    budgets = torch.empty(K, dtype=torch.int32, device=dev)
-    state = ctx.trm_state_tensor(K)
-    _to_ctx()                              # every buffer above (torch's stream) before the context's stream
-    evalf(u, J_old, None)
-    ctx.tv_tensors(u, tv_u)                # TV of the current u; afterwards every trial's TV_new
-    ctx.trm_attach(state)
-    polls = 0
+    ctx = Context(device)
     try:
-        it = 1
-        while it <= maxiter:
-            ctx.trm_outer_begin(state, tv_u, D0, B, budgets)         # TV_old, Δᵏ, k, inner, :99-107
-            evalf(u, None, df)                                      # ∇f at obj.x = u, :102-103
-            ctx.bellman_batch_tensors(df, u_old, B, tau)
-            done, active = 0, True
-            while done < kmax:
-                for _ in range(min(inner_chunk, kmax - done)):
-                    ctx.backtrack_batch_budgets_tensors(budgets, trial)
-                    ctx.pred_batch_tensors(int_val, tv_o, tv_new, pred)
-                    evalf(trial, J_new, None)
-                    ctx.trm_inner_end(state, sigma, kmax, tau, B, int_val, tv_new, J_new, J_old, J, tv_u, budgets,
-                                      trial, u, u_old, decision=dec if log is not None else None)
-                    done += 1
-                    if log is not None:                             # debugging: one synchronisation per trial
-                        st = ctx.trm_state_arrays(state, K)
-                        d = dec.cpu().numpy().copy()
-                        log.append((it, st["k"].copy(), st["Dk"].copy(), None, d, d >= 0))
-                inner, active = ctx.trm_poll(state)                  # the one read-back per chunk
-                polls += 1
-                if not inner:
+        problem.setup(ctx)
+        ctx.set_levels(lt)
+        ctx.set_cost(par.p, par.beta)
+        if x0 is None:
+            nt = problem.nt if nt is None else int(nt)
+            u = torch.empty(int(K), nt, lt.M, dtype=torch.float64, device=dev)
+            ctx.rand_start_tensor(u, seed)
+        else:
+            u = x0.to(device=dev, dtype=torch.float64).contiguous().clone()
+        K, nt, _ = u.shape
+        tau = (T1 - T0) / nt
+        beta, D0, sigma, kmax, maxiter = par.beta, par.Delta0, par.sigma, par.kmax, par.maxiter
+        B = int(math.floor(D0 / tau))  # multi-trust.jl:69
+
+        f64 = dict(dtype=torch.float64, device=dev)
+        ctx.synchronize()                      # u (random starts) from the context's stream before torch reads it
+        u_old = u.clone()
+        J_old = torch.empty(K, **f64)
+        tv_u = torch.empty(K, **f64)
+        J = torch.full((K,), math.inf, **f64)
+        df = torch.empty_like(u)
+        trial = torch.empty_like(u)
+        int_val, tv_o, tv_new, pred = (torch.empty(K, **f64) for _ in range(4))
+        J_new = torch.empty(K, **f64)
+        dec = torch.empty(K, dtype=torch.int32, device=dev)
+        budgets = torch.empty(K, dtype=torch.int32, device=dev)
+        state = ctx.trm_state_tensor(K)
+        torch.cuda.current_stream(dev).synchronize()  # every buffer above (torch's stream) before the context's stream
+        problem.eval_tensors(ctx, u, J_old, None)
+        ctx.tv_tensors(u, tv_u)                # TV of the current u; afterwards every trial's TV_new
+        ctx.trm_attach(state)
+        polls, it = 0, 1
+
+        def one_trial():
+            ctx.backtrack_batch_budgets_tensors(budgets, trial)
+            ctx.pred_batch_tensors(int_val, tv_o, tv_new, pred)
+            problem.eval_tensors(ctx, trial, J_new, None)
+            ctx.trm_inner_end(state, sigma, kmax, tau, B, int_val, tv_new, J_new, J_old, J, tv_u, budgets, trial, u,
+                              u_old, decision=dec if log is not None else None)
+            if log is not None:                                     # debugging: one synchronisation per trial
+                st = ctx.trm_state_arrays(state, K)
+                d = dec.cpu().numpy().copy()
+                log.append((it, st["k"].copy(), st["Dk"].copy(), None, d, d >= 0))
+        try:
+            while it <= maxiter:
+                ctx.trm_outer_begin(state, tv_u, D0, B, budgets)    # TV_old, Δᵏ, k, inner, :99-107
+                problem.eval_tensors(ctx, u, None, df)              # ∇f at obj.x = u, :102-103
+                ctx.bellman_batch_tensors(df, u_old, B, tau)
+                n, active = _inner_loop(one_trial, lambda: ctx.trm_poll(state), kmax, inner_chunk)
+                polls += n
+                it += 1
+                if not active:                                      # every restart stopped, :96
                     break
-            it += 1
-            if not active:                                          # every restart stopped, :96
-                break
+        finally:
+            ctx.trm_attach(None)
+        problem.eval_tensors(ctx, u, None, df)                      # final derivative, :166-167
+        ctx.synchronize()                                           # the context's results before torch reads them
+        values = (J + beta * tv_u).cpu().numpy()                    # J + β·TV_p(u, p), :169
+        iters = ctx.trm_state_arrays(state, K)["iters"].astype(np.int64)
+        if stats is not None:
+            stats.update(polls=polls, outer=it - 1, algo=ctx.last_algo(), diagnostics=ctx.diagnostics())
     finally:
-        ctx.trm_attach(None)
-    evalf(u, None, df)                                              # final derivative, :166-167
-    _to_torch()
-    values = (J + beta * tv_u).cpu().numpy()                        # J + β·TV_p(u, p), :169
-    st = ctx.trm_state_arrays(state, K)
-    iters = st["iters"].astype(np.int64)
-    if stats is not None:
-        stats.update(polls=polls, outer=it - 1, algo=ctx.last_algo(), diagnostics=ctx.diagnostics())
-    ctx.close()
+        ctx.close()
     return values, u, iters

@@ -282,6 +282,7 @@ def TRM_mixed_batch(problem, par=None, cpar=None, K=None, x0=None, seed=0, devic
 
     from .native import Context
     from .ode_device import DeviceODEProblem, MixedODEProblem
+    from .trm_batch import _inner_loop
     if isinstance(problem, DeviceODEProblem):
         raise ValueError("a DeviceODEProblem has no continuous controls (nu == 0): use mioc.trm_batch.TRM_batch")
     if not isinstance(problem, MixedODEProblem):
@@ -337,6 +338,14 @@ def TRM_mixed_batch(problem, par=None, cpar=None, K=None, x0=None, seed=0, devic
         torch.cuda.current_stream(dev).synchronize()        # every buffer above before the context's stream
         evalf(x, J_old, None)
         polls, it = 0, 1
+
+        def one_trial():  # of the trust-region step in v, as TRM_batch runs it
+            ctx.backtrack_batch_budgets_tensors(budgets, trial_v)
+            ctx.rows_copy_tensors(x_trial, nu, trial_v, 0, nv)    # join
+            ctx.pred_batch_tensors(int_val, tv_o, tv_new, pred)
+            evalf(x_trial, J_new, None)
+            ctx.trm_inner_end(state, sigma, kmax, tau, B, int_val, tv_new, J_new, J_old, J_scr, tv_u, budgets, trial_v,
+                              v_cur, v_old)
         try:
             while it <= maxiter:
                 ctx.trm_attach(None)
@@ -351,20 +360,8 @@ def TRM_mixed_batch(problem, par=None, cpar=None, K=None, x0=None, seed=0, devic
                 ctx.trm_outer_begin(state, tv_u, D0, B, budgets)
                 ctx.trm_attach(state)
                 ctx.bellman_batch_tensors(df_v, v_old, B, tau)
-                done, live = 0, True
-                while done < kmax:
-                    for _ in range(min(inner_chunk, kmax - done)):
-                        ctx.backtrack_batch_budgets_tensors(budgets, trial_v)
-                        ctx.rows_copy_tensors(x_trial, nu, trial_v, 0, nv)    # join
-                        ctx.pred_batch_tensors(int_val, tv_o, tv_new, pred)
-                        evalf(x_trial, J_new, None)
-                        ctx.trm_inner_end(state, sigma, kmax, tau, B, int_val, tv_new, J_new, J_old, J_scr, tv_u,
-                                          budgets, trial_v, v_cur, v_old)
-                        done += 1
-                    inner, live = ctx.mixed_poll(mstate, state)       # the one read-back per chunk
-                    polls += 1
-                    if not inner:
-                        break
+                n, live = _inner_loop(one_trial, lambda: ctx.mixed_poll(mstate, state), kmax, inner_chunk)
+                polls += n
                 ctx.trm_attach(None)
                 ctx.rows_copy_tensors(x, nu, v_old, 0, nv)            # the accepted v back into x
                 it += 1
